@@ -183,6 +183,39 @@ def synth_batch(batch, n, seed, device):
     return wav.to(device).contiguous()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 stays float64), so that two builds can be compared
+    output for output.  Above DUMP_LIMIT_BYTES in all, each array keeps a fixed, seeded sample of its elements (one per stride,
+    at a seeded offset inside the stride) as a flat vector, with the flat indices of the sample beside it as <name>_index.npy
+    (float64, exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        host[name] = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    cost = sum(a.size * (a.itemsize + 8) for a in host.values())   # sampled: the value and its float64 index
+    written = {}
+    for name, a in host.items():
+        if total <= DUMP_LIMIT_BYTES:
+            np.save(os.path.join(path, name + ".npy"), a)
+            written[name] = list(a.shape)
+            continue
+        stride = -(-cost // DUMP_LIMIT_BYTES)
+        k = a.size // stride
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.arange(k, dtype=torch.int64) * stride + torch.randint(0, stride, (k,), generator=g)
+        idx = idx.numpy()
+        np.save(os.path.join(path, name + ".npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+        written[name] = {"shape": list(a.shape), "sampled_elements": int(k)}
+    return written
+
+
 def path_macs(n):
     """Algorithmic MACs of one utterance of n samples."""
     T = 1 + n // 441
@@ -638,7 +671,16 @@ def main():
                     help="test hook: rehearse the N-rank launch on CPU (gloo, no device work)")
     ap.add_argument("--dump-stacks-after", type=float, default=0.0,
                     help="development: faulthandler dumps every thread's stack to stderr after this many seconds (where is a slow run?)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's restored batch, (B, N) float32) "
+                         "as DIR/restored.npy; above %d MB a fixed, seeded sample of it (DIR/restored_index.npy: the flat indices). "
+                         "The inputs depend only on the arguments, so two builds can be compared output for output"
+                         % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.scatter or args.synth_folder or args.folder or args.dry_run):
+        ap.error("--dump-outputs covers the resident-batch workload only (not --scatter, --synth-folder, --folder or --dry-run)")
     if args.dump_stacks_after > 0:
         import faulthandler
         faulthandler.dump_traceback_later(args.dump_stacks_after, repeat=True, file=sys.stderr)
@@ -758,6 +800,9 @@ def main():
         dt = time.perf_counter() - t0
     clocks = {"timed_region": sampler.summary(t0 + 0.25 * dt, t0 + dt)}   # (the first quarter: the clock is still ramping)
     prof, ops.PROFILE = ops.PROFILE, None
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(args.dump_outputs, {"restored": out})
+        print("bench.py: --dump-outputs: %s -> %s" % (json.dumps(written), args.dump_outputs), file=sys.stderr, flush=True)
     if prof is None:
         ops.EVENT_POOL = None
         if rank == 0:

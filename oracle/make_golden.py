@@ -26,6 +26,11 @@ Fixtures
   vocoder_oracle_ref.npz  the reference's OWN Vocoder.oracle (vocoder/base.py:58-77) on 1 s of its fixture
                           test/utterance/original/p360_001_mic1.flac: PCM16 input, the conditioning its numpy front-end
                           builds (``cond``), and the int16 frames it hands to soundfile.write (``out_pcm``)
+  reference_parity.npz    what tests/test_oracle_vs_reference.py checks the oracle against: the state dicts the reference
+                          holds after loading the seeded checkpoints (key order + sha256 of every tensor), restore_inmem
+                          (mode 0) on seeded noise of 4 427 and 22 173 samples, the torchlibrosa conv-DFT magnitudes
+                          of a (2, 9000) batch, and Vocoder.forward with the weights loaded from a legacy
+                          weight_g / weight_v checkpoint (python oracle/make_golden.py --parity writes this file only)
   ref_utterance/          the reference's test utterances and FLAC goldens (test/utterance/original/*.flac,
                           target/{oracle,output_mode_0,output_mode_1}.flac) copied verbatim: inputs / targets of the
                           real-checkpoint harness (tests/test_real_checkpoints.py = test/test.py:27-95) and, together with
@@ -90,16 +95,58 @@ def write_reference_constants():
     print("fb nnz", int(nz.sum()), "sha256", sha, "sha256(|fb|)", sha_abs, "negative zeros", int(np.signbit(raw).sum()))
 
 
+def tensor_sha256(t):
+    """sha256 over dtype, shape and bytes of a CPU tensor (tests/test_oracle_vs_reference.py recomputes it)."""
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(("%s%s" % (t.dtype, tuple(t.shape))).encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+def write_reference_parity(vf, rsd):
+    """reference_parity.npz: the reference's own modules on the inputs of tests/test_oracle_vs_reference.py.
+    Must run last: the legacy-checkpoint leg re-points the imported reference at another HOME."""
+    fx = {}
+    for tag, sd in (("restorer", vf._model.generator.state_dict()), ("vocoder", vf._model.vocoder.model.state_dict())):
+        fx[tag + "_keys"] = np.array(list(sd.keys()))
+        fx[tag + "_sha256"] = np.array([tensor_sha256(v) for v in sd.values()])
+    for n in (4410 + 17, 44100 // 2 + 123):
+        g = torch.Generator().manual_seed(n)
+        wav = (0.15 * torch.randn(n, generator=g)).numpy().astype(np.float32)
+        with torch.no_grad():
+            fx["restore_%d_wav" % n] = wav
+            fx["restore_%d_out" % n] = vf.restore_inmem(wav, cuda=False, mode=0)
+    g = torch.Generator().manual_seed(3)
+    wav = torch.randn(2, 9000, generator=g) * 0.3
+    with torch.no_grad():
+        sp, _, _ = vf._model.f_helper.wav_to_spectrogram_phase(wav[:, None, :])
+    fx["stft_wav"], fx["stft_mag"] = wav.numpy(), sp.numpy()
+    legacy = weights.seeded_vocoder_state(VOC_SEED, legacy=True)
+    vf_legacy = ref_shim.build_reference_models(tempfile.mkdtemp(prefix="vfx_home_"), legacy,
+                                                {"generator." + k: v for k, v in rsd.items()})
+    g = torch.Generator().manual_seed(5)
+    mel = 10 ** (torch.rand((1, 1, 12, 128), generator=g) * 4 - 2)
+    with torch.no_grad():
+        fx["legacy_mel"], fx["legacy_out"] = mel.numpy(), vf_legacy._model.vocoder(mel, cuda=False).numpy()
+    np.savez_compressed(os.path.join(OUT, "reference_parity.npz"), voc_seed=VOC_SEED, res_seed=RES_SEED, **fx)
+    print("reference_parity", {k: v.shape for k, v in fx.items()})
+
+
 def main():
     if "--constants" in sys.argv[1:]:
         write_reference_constants()
         return
-    write_reference_constants()
+    parity_only = "--parity" in sys.argv[1:]
+    if not parity_only:
+        write_reference_constants()
     os.makedirs(OUT, exist_ok=True)
     home = tempfile.mkdtemp(prefix="vfx_home_")
     vsd = weights.seeded_vocoder_state(VOC_SEED)
     rsd = weights.seeded_restorer_state(RES_SEED)
     vf = ref_shim.build_reference_models(home, vsd, {"generator." + k: v for k, v in rsd.items()})
+    if parity_only:
+        write_reference_parity(vf, rsd)
+        return
     # the reference must have taken our weights verbatim
     ref_r = vf._model.generator.state_dict()
     ref_v = vf._model.vocoder.model.state_dict()
@@ -189,6 +236,8 @@ def main():
         shutil.copyfile(os.path.join(ref_shim.REFERENCE_ROOT, "test/utterance", rel),
                         os.path.join(dst, rel.replace("/", "_")))
     np.savez_compressed(os.path.join(OUT, "flac_original_pcm.npz"), pcm=pcm)   # == original.wav, PCM16
+
+    write_reference_parity(vf, rsd)
 
 
 if __name__ == "__main__":

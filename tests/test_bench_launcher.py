@@ -81,3 +81,25 @@ def test_clock_sampler_and_core_ranges_do_not_need_a_gpu():
     assert doc["sclk_mhz"] == {"mean": 2150.0, "min": 2100.0, "max": 2200.0, "n": 2}
     assert doc["socket_power_w"] == {"mean": 1350.0, "min": 1300.0, "max": 1400.0, "n": 2}
     assert bench._ranges([0, 1, 2, 3, 128, 129, 200]) == "0-3,128-129,200" and bench._ranges([]) is None
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: the whole array when it fits the budget; above it a fixed, seeded sample with its flat indices."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.randn(4, 1000, generator=torch.Generator().manual_seed(1))
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"restored": x}) == {"restored": [4, 1000]}
+    got = np.load(tmp_path / "whole" / "restored.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"restored": x})
+    total = sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a"))   # (128: the .npy header)
+    assert total <= 6000
+    v, i = np.load(tmp_path / "a" / "restored.npy"), np.load(tmp_path / "a" / "restored_index.npy")
+    assert v.dtype == np.float32 and i.dtype == np.float64 and len(v) == len(i) > 0
+    assert np.all(np.diff(i) > 0) and i[-1] < x.numel()
+    assert np.array_equal(v, x.numpy().reshape(-1)[i.astype(np.int64)])
+    assert np.array_equal(i, np.load(tmp_path / "b" / "restored_index.npy"))    # the same sample every run

@@ -1,71 +1,73 @@
-"""Live check of the oracle (and of the seeded-checkpoint manifests) against the
-reference's own modules.  Only runs where /root/reference exists (build container)."""
-import tempfile
+"""The oracle (and the seeded-checkpoint manifests) against the reference's own modules, through
+tests/golden/reference_parity.npz: what the reference computed on these inputs, recorded by
+``python oracle/make_golden.py --parity``.  Runs without the reference and without a GPU."""
+import hashlib
+import os
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import oracle, ref_shim
-
-pytestmark = pytest.mark.skipif(not ref_shim.reference_available(),
-                                reason="/root/reference not present")
+from conftest import GOLDEN
+from oracle import oracle
 
 
 @pytest.fixture(scope="module")
-def ref_vf(seeded_states):
-    vsd, rsd = seeded_states
-    home = tempfile.mkdtemp(prefix="vfx_home_")
-    return ref_shim.build_reference_models(home, vsd, {"generator." + k: v for k, v in rsd.items()})
+def ref():
+    return np.load(os.path.join(GOLDEN, "reference_parity.npz"))
 
 
-def test_manifests_match_reference(ref_vf, seeded_states):
+def _sha256(t):
+    """oracle/make_golden.py: tensor_sha256 -- dtype, shape and bytes."""
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(("%s%s" % (t.dtype, tuple(t.shape))).encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+def test_manifests_match_reference(ref, seeded_states):
+    """The reference took the seeded state dicts verbatim: same keys in the same order, every tensor bit-identical."""
     vsd, rsd = seeded_states
-    ref_r = ref_vf._model.generator.state_dict()
-    ref_v = ref_vf._model.vocoder.model.state_dict()
-    assert list(ref_r.keys()) == list(rsd.keys())
-    assert list(ref_v.keys()) == list(vsd.keys())
-    for k in rsd:
-        assert torch.equal(ref_r[k], rsd[k]), k
-    for k in vsd:
-        assert torch.equal(ref_v[k], vsd[k]), k
+    for tag, sd in (("restorer", rsd), ("vocoder", vsd)):
+        assert list(sd.keys()) == [str(k) for k in ref[tag + "_keys"]]
+        for k, h in zip(sd, ref[tag + "_sha256"]):
+            assert _sha256(sd[k]) == str(h), k
 
 
 @pytest.mark.parametrize("n", [4410 + 17, 44100 // 2 + 123])
-def test_restore_inmem_matches_reference(ref_vf, seeded_states, n):
+def test_restore_inmem_matches_reference(ref, seeded_states, n):
     vsd, rsd = seeded_states
     g = torch.Generator().manual_seed(n)
     wav = (0.15 * torch.randn(n, generator=g)).numpy().astype(np.float32)
+    assert np.array_equal(wav, ref["restore_%d_wav" % n])
     with torch.no_grad():
-        ref = ref_vf.restore_inmem(wav, cuda=False, mode=0)
         out = oracle.restore_inmem(wav, vsd, rsd)
-    assert ref.shape == out.shape == (1, n)
-    assert np.sqrt(np.mean((ref - out) ** 2)) < 1e-5
+    want = ref["restore_%d_out" % n]
+    assert want.shape == out.shape == (1, n)
+    assert np.sqrt(np.mean((want - out) ** 2)) < 1e-5
 
 
-def test_stft_fft_vs_conv_dft(ref_vf):
+def test_stft_fft_vs_conv_dft(ref):
     """oracle uses an FFT, the reference (torchlibrosa) a conv-DFT: same magnitudes."""
     g = torch.Generator().manual_seed(3)
     wav = torch.randn(2, 9000, generator=g) * 0.3
+    assert np.array_equal(wav.numpy(), ref["stft_wav"])
+    sp = torch.from_numpy(ref["stft_mag"])
     with torch.no_grad():
-        sp, _, _ = ref_vf._model.f_helper.wav_to_spectrogram_phase(wav[:, None, :])
         mine = oracle.stft_mag(wav)
     assert sp.shape == (2, 1, 21, 1025)
     rel = (sp[:, 0] - mine).norm() / mine.norm()
     assert rel < 5e-6
 
 
-def test_vocoder_forward_legacy_ckpt(seeded_states):
+def test_vocoder_forward_legacy_ckpt(ref):
     """The reference loads legacy weight_g/weight_v checkpoints through torch's compat
     hook; both key styles must give the same generator."""
     from voicefixer_amd import weights
     legacy = weights.seeded_vocoder_state(1234, legacy=True)
-    home = tempfile.mkdtemp(prefix="vfx_home_")
-    vf = ref_shim.build_reference_models(
-        home, legacy, {"generator." + k: v for k, v in seeded_states[1].items()})
     g = torch.Generator().manual_seed(5)
     mel = 10 ** (torch.rand((1, 1, 12, 128), generator=g) * 4 - 2)
+    assert np.array_equal(mel.numpy(), ref["legacy_mel"])
     with torch.no_grad():
-        ref = vf._model.vocoder(mel, cuda=False)
         out = oracle.vocoder_forward(mel, legacy)
-    assert (ref - out).abs().max() < 2e-5
+    assert (torch.from_numpy(ref["legacy_out"]) - out).abs().max() < 2e-5

@@ -53,7 +53,8 @@ def compare(a, b):
     return rows
 
 
-def report(results, tol, out=sys.stdout):
+def report(results, tol, out=None):
+    out = sys.stdout if out is None else out   # (resolved per call: whatever sys.stdout is now, not at import)
     base = results["direct"]
     bad = []
     print("%-10s %s" % ("stage", "  ".join("%-22s" % ("%s vs direct" % v) for v in results if v != "direct")), file=out)
