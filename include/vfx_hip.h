@@ -38,6 +38,8 @@ typedef void* vfx_stream_t; /* hipStream_t */
 #define VFX_EINVAL (-1)   /* bad argument / unsupported shape */
 #define VFX_EALIGN (-2)   /* pointer or stride alignment */
 #define VFX_ERANGE (-3)   /* tile bookkeeping overflow (tap span too large for the tile) */
+#define VFX_ENOTSUP (-4)  /* valid arguments, but a shape / activation this entry point does not take (vfx_conv1d_f16):
+                             the caller runs the launch on the fp32 entry point instead */
 
 typedef struct {
     void* ptr;
@@ -135,7 +137,9 @@ uint64_t vfx_launch_count(void);
  *   code 80           convwg4_kernel<..>                          (Winograd F(4,3), 1-D), BL = output positions
  *   code 81           convwg4p_kernel<..>                         (the same tile on persistent workgroups: the two long launches of a
  *                     ResStack layer, tap / staging / weight pipeline running across tiles)
- *   code 88           convwg4s_kernel<..>                         (Winograd F(4,3), 3x3 on a pitch map, kernel columns share one tile) */
+ *   code 88           convwg4s_kernel<..>                         (Winograd F(4,3), 3x3 on a pitch map, kernel columns share one tile)
+ *   code 32           convh_kernel                                (opt-in f16 arithmetic, vfx_conv1d_f16: direct sum on
+ *                     v_mfma_f32_32x32x16_f16, BM = 128 output channels x BL = 128 positions) */
 int vfx_last_conv_tile(void);
 
 /* ---- convolution family: implicit GEMM on v_mfma_f32_32x32x2_f32 -------------------
@@ -151,6 +155,21 @@ int vfx_last_conv_tile(void);
 int vfx_conv1d_f32(const vfx_tensor* x, const float* w_packed, const float* bias,
                    const vfx_tensor* res, const vfx_tensor* y, int B, int Cin, int Cout, int L,
                    int k, int dilation, int pad_mode, const vfx_act* act, vfx_stream_t stream);
+
+/* Opt-in f16 arithmetic for the k = 3 dilated Conv1d of the wide ResStack layers (C = Cin = Cout in {128, 256, 512}):
+ *   y[b,n,l] = post( bias[n] + res[b,n,l] + sum_{c,t} f16(w[n][c][t]) * f16(pre(x[b,c,l+(t-1)*dil])) )
+ * with both operands rounded to fp16 (round to nearest even) and the products accumulated in fp32 (direct sum on
+ * v_mfma_f32_32x32x16_f16); pre-activation, bias, residual and post-activation are fp32.  Zero padding.
+ * w_f16: fp16 weights [3][C/8][C][8], element [t][c8][n][e] = w[n][8 c8 + e][t] (packing.py::pack_f16).
+ * act: pre_act VFX_PRE_NONE / VFX_PRE_LRELU, post_act VFX_POST_NONE / LRELU / LRELU_SNAKE (math and the weight
+ * fields are ignored); NULL = no activation.  x, res and y need lstride 1; x is read only inside [0, row length)
+ * (guard 0 is legal; x->rows honoured as in vfx_conv1d_f32); res may alias y (in-place residual update), x may not.
+ * range_flag (device int32, may be NULL): set to nonzero when a staged activation operand is not finite or exceeds
+ * the fp16 range (|v| > 65504); y is then unspecified (the caller re-runs in fp32).  The flag is never cleared here.
+ * Returns VFX_ENOTSUP for a C, activation or layout it does not take. */
+int vfx_conv1d_f16(const vfx_tensor* x, const void* w_f16, const float* bias, const vfx_tensor* res,
+                   const vfx_tensor* y, int B, int C, int L, int dilation, const vfx_act* act, int32_t* range_flag,
+                   vfx_stream_t stream);
 
 /* One whole ResStack layer, fused (voicefixer/vocoder/model/modules.py:592-609, one iteration of the loop):
  *   y[b,n,l] = post( x[b,n,l] + bias2[n] + conv_k3_d1( lrelu_s( bias1 + conv_k3_dil( lrelu_s(x) ) ) )[b,n,l] )

@@ -39,6 +39,7 @@ PRE_NONE, PRE_LRELU, PRE_AFFINE_LRELU = 0, 1, 2
 POST_NONE, POST_LRELU, POST_ELU, POST_TANH, POST_SIGMOID, POST_LRELU_SNAKE = 0, 1, 2, 3, 4, 5
 PAD_ZERO, PAD_REFLECT = 0, 1
 MATH_F32, MATH_BF16X3 = 0, 1
+EINVAL, EALIGN, ERANGE, ENOTSUP = -1, -2, -3, -4
 
 _T = C.POINTER(vfx_tensor)
 _A = C.POINTER(vfx_act)
@@ -52,6 +53,7 @@ SIGNATURES = {
     "vfx_launch_count": (C.c_uint64, []),
     "vfx_last_conv_tile": (_I, []),
     "vfx_conv1d_f32": (_I, [_T, _P, _P, _T, _T, _I, _I, _I, _I, _I, _I, _I, _A, _P]),
+    "vfx_conv1d_f16": (_I, [_T, _P, _P, _T, _T, _I, _I, _I, _I, _A, _P, _P]),
     "vfx_resblock_f32": (_I, [_T, _T, C.POINTER(vfx_resblock_w), _I, _I, _I, _I, C.c_float, _I, C.c_float, _P]),
     "vfx_convtr1d_f32": (_I, [_T, _P, _P, _T, _I, _I, _I, _I, _I, _A, _P]),
     "vfx_conv2d_f32": (_I, [_T, _P, _P, _T, _T, _I, _I, _I, _I, _I, _I, _A, _P]),

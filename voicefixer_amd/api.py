@@ -145,7 +145,7 @@ class Vocoder(nn.Module):
         dev = eng.device
         m = mel.detach().to(dev, torch.float32)[:, 0].contiguous()
         T = m.shape[1]
-        wav, L = eng.forward(m, T)
+        wav, L = eng.run_f16_checked(lambda: eng.forward(m, T))
         out = wav[:, :, :L]
         return out if cuda else out.cpu()
 
@@ -165,7 +165,7 @@ class Vocoder(nn.Module):
         Tc = T + T % 2 + 4
         cond = ops.guarded(1, 128, Tc, engine.G_TILE, eng.device)
         ops.mel_to_cond_plain(mel, cond, T)      # amp_to_db - 20, normalize, pre()
-        wav_re, L = eng.forward_cond(cond, Tc)
+        wav_re, L = eng.run_f16_checked(lambda: eng.forward_cond(cond, Tc))
         audio_io.save_wave((wav_re[:, 0, :L] * 2 ** 15).cpu().numpy(), out_path, sample_rate=self.rate)
 
 
@@ -263,7 +263,8 @@ class VoiceFixer(nn.Module):
         "f32" (default): exact fp32 products on the fp32 MFMA.  "bf16x3": every fp32 operand is split into
         two bf16 terms and x*w is evaluated as xh*wh + xh*wl + xl*wh on the bf16 MFMA with fp32 accumulation
         (per-product relative error <= 2^-16; end-to-end waveform difference ~2e-6 RMS, the size of an fp32
-        summation-order change, against the 1e-3 parity bound)."""
+        summation-order change, against the 1e-3 parity bound).  (The engine's "f16" arithmetic, DESIGN.md 3.7, is not
+        offered here: it is not yet faster than either.)"""
         if math not in ("f32", "bf16x3"):
             raise ValueError("math must be 'f32' or 'bf16x3'")
         self.math = math
@@ -411,7 +412,7 @@ class VoiceFixer(nn.Module):
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
-        from .engine import GruHandoffMissed
+        from .engine import DeviceFlagRaised
         self._check_mode(mode)
         pipe = self._get_pipe()
         pool = self._streams(streams)
@@ -424,7 +425,7 @@ class VoiceFixer(nn.Module):
         try:
             try:
                 pipe.check()                  # a flag that is already set belongs to an earlier, unchecked launch (a direct
-            except GruHandoffMissed:          # pipe.restore user): check() has cleared it, and none of THIS call's work failed
+            except DeviceFlagRaised:          # pipe.restore user): check() has cleared it, and none of THIS call's work failed
                 pass
             nb = 0
 
@@ -433,20 +434,19 @@ class VoiceFixer(nn.Module):
                 rec[3].synchronize()
                 try:
                     pipe.check()
-                except GruHandoffMissed:
+                except DeviceFlagRaised as e:
                     # which of the batches in flight raised it cannot be told: drain them all, re-issue every one of
-                    # them with the recurrences on vfx_gru_bidir_f32 (nothing to miss), one after the other
+                    # them with the fallback the flags ask for (recurrences on vfx_gru_bidir_f32: nothing to miss; f16
+                    # launches in fp32), one after the other
                     torch.cuda.synchronize(pipe.device)
-                    pipe.restorer.gru_err.zero_()
-                    pipe.restorer.gru_single = True
-                    try:
+                    if pipe.restorer.gru_err is not None:
+                        pipe.restorer.gru_err.zero_()
+                    pipe.vocoder.read_f16_flag()
+                    with pipe.fallback(e):
                         for q in range(len(inflight)):
                             inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
-                    finally:
-                        pipe.restorer.gru_single = False
-                    pipe.gru_retries = getattr(pipe, "gru_retries", 0) + 1
                     rec = inflight[0]
                 inflight.popleft()
                 return rec[0][0], rec[1], rec[2]
@@ -468,6 +468,8 @@ class VoiceFixer(nn.Module):
             pipe.set_streams(1)
             if not ok and pipe.restorer.gru_err is not None:
                 pipe.restorer.gru_err.zero_()
+            if not ok:
+                pipe.vocoder.read_f16_flag()
 
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0):

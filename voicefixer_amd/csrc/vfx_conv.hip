@@ -1,6 +1,7 @@
 // vfx_conv.hip -- the convolution family of the VoiceFixer path as ONE implicit-GEMM
 // kernel on v_mfma_f32_32x32x2_f32 (exact fp32, 157 TFLOP/s peak on MI355X), plus its opt-in
-// split-bf16 sibling conv_x3_kernel (VFX_MATH_BF16X3, v_mfma_f32_32x32x16_bf16; further down).
+// split-bf16 sibling conv_x3_kernel (VFX_MATH_BF16X3, v_mfma_f32_32x32x16_bf16; further down) and the opt-in
+// f16 kernel of the wide ResStack layers (convh_kernel, vfx_conv1d_f16: vfx_convh.inc).
 //
 // Every convolution on the path (dilated Conv1d k3, reflect-padded Conv1d k7,
 // polyphase ConvTranspose1d, Conv2d 3x3/1x1 on pitch maps, ConvTranspose2d 3x3 s2,
@@ -1214,8 +1215,8 @@ static float* splitk_workspace(hipStream_t s, size_t bytes) {
 }
 
 // ---- bf16x3 launch path (opt-in per launch, vfx_act.math == VFX_MATH_BF16X3).  Returns VFX_ENOTSUP when the
-// geometry is outside what conv_x3_kernel covers; the caller then runs the fp32 kernel.
-#define VFX_ENOTSUP (-100)
+// geometry is outside what conv_x3_kernel covers; the caller then runs the fp32 kernel (the code is never returned
+// through the C ABI from here).
 
 #include "vfx_convw.inc"
 #include "vfx_convwg.inc"
@@ -1224,6 +1225,7 @@ static float* splitk_workspace(hipStream_t s, size_t bytes) {
 #include "vfx_convtw.inc"
 #include "vfx_convwg2d.inc"
 #include "vfx_resblk4.inc"
+#include "vfx_convh.inc"
 
 template <int BM, int BL, int WGM, int WGL, int NT, int MODE, int ROWS = 1>
 static int launch_x3_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {

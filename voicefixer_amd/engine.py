@@ -16,6 +16,7 @@ Data layouts in HBM (all float32):
   * mel / logmel / denoised: (B, T, 128) frame-major (the reference's (B,1,T,128));
   * GRU x-projections: (B, T, 1536) frame-major.
 """
+import contextlib
 import math
 
 import torch
@@ -25,8 +26,20 @@ from ._lib import (PRE_NONE, PRE_LRELU, PRE_AFFINE_LRELU, POST_NONE, POST_LRELU,
                    POST_SIGMOID, POST_LRELU_SNAKE, PAD_ZERO, PAD_REFLECT, VfxError)
 
 
-class GruHandoffMissed(VfxError):
+class DeviceFlagRaised(VfxError):
+    """A device-side flag of the launches of one call was found set (``Pipeline.check``); ``gru`` / ``f16`` say which ones, so
+    that a re-run can take every fallback the call needs at once."""
+    gru = False
+    f16 = False
+
+
+class GruHandoffMissed(DeviceFlagRaised):
     """The two-CU GRU's bounded spin expired (a partner workgroup was not resident in time)."""
+
+
+class F16RangeExceeded(DeviceFlagRaised):
+    """An activation operand of an f16 launch (vfx_conv1d_f16) was not finite or outside the fp16 range: the call's result
+    is unspecified and is re-run in fp32."""
 
 
 def _up4(n):
@@ -116,6 +129,11 @@ def _wg(w):
     return w if _ARITH["winograd"] else None
 
 
+MATHS = ("f32", "bf16x3", "f16")
+# channel counts whose ResStack convolutions run on vfx_conv1d_f16 under set_math("f16"); everything else stays fp32
+F16_CHANNELS = (128, 256, 512)
+
+
 class VocoderEngine:
     """TFGAN-style 44.1 kHz generator: cond (B,128,T') -> wav (B,1,441*T')."""
 
@@ -169,13 +187,64 @@ class VocoderEngine:
         self.act_last = ops.Act(post=POST_LRELU, post_slope=0.2)
 
     def set_math(self, math):
-        """"f32" (default: exact fp32 MFMA) or "bf16x3" (opt-in VFX_MATH_BF16X3: split-bf16 products with fp32
-        accumulation; bf16 weight planes are packed lazily, once per layer)."""
-        if math not in ("f32", "bf16x3"):
-            raise ValueError("math must be 'f32' or 'bf16x3'")
+        """"f32" (default: exact fp32 MFMA), "bf16x3" (opt-in VFX_MATH_BF16X3: split-bf16 products with fp32
+        accumulation; bf16 weight planes are packed lazily, once per layer) or "f16" (opt-in: the k = 3 convolutions of
+        the ResStacks with C in F16_CHANNELS on vfx_conv1d_f16 -- operands rounded to fp16, fp32 accumulation; fp16 weight
+        planes packed lazily; every other launch exactly as "f32")."""
+        if math not in MATHS:
+            raise ValueError("math must be one of %s" % ", ".join(repr(m) for m in MATHS))
         self.math = math
         if not hasattr(self, "_w3"):
             self._w3 = {}
+            self._w16 = {}
+            self.f16_flag = None      # device int32: raised by vfx_conv1d_f16 when an operand leaves the fp16 range
+            self.f16_off = False      # True while a call is re-run in fp32 after a raised flag (Pipeline.run_checked)
+            self.f16_fallbacks = 0    # calls re-run in fp32 because of the range flag
+
+    def _f16(self, w):
+        """fp16 weight planes of a ResStack convolution (packing.pack_f16, packed once), or None when the layer stays fp32."""
+        if self.math != "f16" or self.f16_off:
+            return None
+        key = w.data_ptr()
+        if key not in self._w16:
+            p = packing.pack_f16(w.cpu())
+            self._w16[key] = None if p is None else p.to(w.device)
+        return self._w16[key]
+
+    def _conv_f16(self, x, w, bias, y, L, dilation, act, res=None):
+        """One ResStack convolution on vfx_conv1d_f16 when f16 is on and the library takes it; False: run it in fp32."""
+        w16 = self._f16(w)
+        if w16 is None:
+            return False
+        if self.f16_flag is None:
+            self.f16_flag = torch.zeros(1, dtype=torch.int32, device=w.device)
+        return ops.conv1d_f16(x, w16, bias, y, L, dilation, act, res=res, flag=self.f16_flag)
+
+    def run_f16_checked(self, fn):
+        """``fn()`` (launches of this engine only: Vocoder.forward / Vocoder.oracle), then the range flag: when an f16 launch
+        left the fp16 range the result is unspecified, and ``fn`` is re-run with every launch in fp32 (counted in
+        ``f16_fallbacks``).  A flag left over from an earlier unchecked call is cleared first, so it cannot trigger a re-run."""
+        if self.math != "f16":
+            return fn()
+        self.read_f16_flag()
+        out = fn()
+        if not self.read_f16_flag():
+            return out
+        self.f16_off = True
+        try:
+            out = fn()
+            self.f16_fallbacks += 1
+            return out
+        finally:
+            self.f16_off = False
+
+    def read_f16_flag(self):
+        """True (and the flag cleared) when an f16 launch since the last read left the fp16 range (one 4-byte D2H copy)."""
+        flag = getattr(self, "f16_flag", None)
+        if flag is None or int(flag.item()) == 0:
+            return False
+        flag.zero_()
+        return True
 
     def _x3(self, w):
         if self.math != "bf16x3":
@@ -198,7 +267,7 @@ class VocoderEngine:
         for i, (w, wd, bias, wg) in enumerate(self.condnet):
             y = a if i % 2 == 0 else b
             ops.conv1d(x, w, bias, y, Tc, 3, 1, PAD_ZERO, self.act_elu, w3=self._x3(w), wd=wd,
-                       wg4=_wg(wg) if self.math == "f32" else None)
+                       wg4=_wg(wg) if self.math != "bf16x3" else None)
             x = y
         if stages is not None:
             stages["condnet"] = x[:, :, :Tc]
@@ -215,13 +284,15 @@ class VocoderEngine:
             mult *= s
             # (the fused kernel addresses one batch item with 32-bit byte offsets: rows of more than ~3 minutes at the last
             # stage fall back to the two-launch form, whose first-generation kernel has no such limit)
-            wino = layers[0][7] is not None and c >= WINO_MIN_C and self.math == "f32" and _ARITH["winograd"]
-            fused = (_FUSE and self.math == "f32" and c <= FUSE_MAX_C and not wino and
+            wino = layers[0][7] is not None and c >= WINO_MIN_C and self.math != "bf16x3" and _ARITH["winograd"]
+            # (f16 covers every C in F16_CHANNELS: those stages run as two launches per layer even without Winograd)
+            fused = (_FUSE and self.math != "bf16x3" and c <= FUSE_MAX_C and not wino and
+                     not (self.math == "f16" and c in F16_CHANNELS) and
                      c * (_up4(Lo) + 2 * (G_DIL + 4)) * 4 < 2 ** 31 - 2 ** 21)
             xs = _rows(B, c, Lo, G_DIL, dev, rows(mult))
             ys = _rows(B, c, Lo, G_DIL if fused else G_TILE, dev, rows(mult))
             ops.convtr1d(h, upw[0], upw[2], xs, L, s, self.act_none, w3=self._x3(upw[0]), wd=upw[1],
-                         wg4=_wg(upw[3]) if self.math == "f32" else None)
+                         wg4=_wg(upw[3]) if self.math != "bf16x3" else None)
             if stages is not None:
                 stages["up%d" % (j + 1)] = xs[:, :, :Lo].clone()
             # The fused C = 64 stage runs its WIDELY dilated layers (d > 27: a block of 4 d positions does not fit the fused tile) as two
@@ -249,9 +320,12 @@ class VocoderEngine:
                     continue
                 if not wino and not fused:
                     w1g4 = w2g4 = None
-                ops.conv1d(xs, w1, b1, ys, Lo, 3, 3 ** i, PAD_ZERO, self.act_c1, w3=self._x3(w1), wd=w1d, wg4=_wg(w1g4))
+                f16 = self.math == "f16" and c in F16_CHANNELS
+                if not (f16 and self._conv_f16(xs, w1, b1, ys, Lo, 3 ** i, self.act_c1)):
+                    ops.conv1d(xs, w1, b1, ys, Lo, 3, 3 ** i, PAD_ZERO, self.act_c1, w3=self._x3(w1), wd=w1d, wg4=_wg(w1g4))
                 act = self.act_none if not last else (self.act_last if j == nst - 1 else self.act_last_snake)
-                ops.conv1d(ys, w2, b2, xs, Lo, 3, 1, PAD_ZERO, act, res=xs, w3=self._x3(w2), wd=w2d, wg4=_wg(w2g4))  # residual updated in place
+                if not (f16 and self._conv_f16(ys, w2, b2, xs, Lo, 1, act, res=xs)):   # residual updated in place
+                    ops.conv1d(ys, w2, b2, xs, Lo, 3, 1, PAD_ZERO, act, res=xs, w3=self._x3(w2), wd=w2d, wg4=_wg(w2g4))
             assert len(layers) % 2 == 0  # the fused ping-pong ends in xs
             h = xs
             L = Lo
@@ -461,9 +535,11 @@ class RestorerEngine:
 
     def set_math(self, math):
         """"f32" or "bf16x3" for the UNet's 3x3 / 1x1 convolutions (the denoiser and the transposed convolutions
-        stay fp32: 1 % of the FLOPs)."""
-        if math not in ("f32", "bf16x3"):
-            raise ValueError("math must be 'f32' or 'bf16x3'")
+        stay fp32: 1 % of the FLOPs).  "f16" touches the vocoder only: the restorer runs as "f32"."""
+        if math not in MATHS:
+            raise ValueError("math must be one of %s" % ", ".join(repr(m) for m in MATHS))
+        if math == "f16":
+            math = "f32"
         for grp in list(self.enc) + [[self.center]] + [d[2] for d in self.dec] + [[self.after]]:
             for blk in grp:
                 blk.set_math(math)
@@ -549,7 +625,11 @@ class Pipeline:
         self.math = math
 
     def set_math(self, math):
-        """"f32" (default) or "bf16x3" (opt-in split-bf16 MFMA products, fp32 accumulation)."""
+        """"f32" (default), "bf16x3" (opt-in split-bf16 MFMA products, fp32 accumulation) or "f16" (opt-in
+        fp16 operands, fp32 accumulation, for the wide ResStack convolutions; DESIGN.md 3.7 -- engine level only, not yet
+        faster).  Captured graphs (enable_graphs) have the arithmetic baked in: a change of arithmetic drops them."""
+        if math != getattr(self, "math", math) and getattr(self, "_graphs", None):
+            self._drop_graphs(None)
         self.vocoder.set_math(math)
         self.restorer.set_math(math)
         self.math = math
@@ -561,34 +641,65 @@ class Pipeline:
         self.restorer.gru_group = max(1, min(ops.GRU2_MAX_B, 256 // (4 * self._n_streams)))
 
     def check(self):
-        """Read the device-side error flags (ONE 4-byte D2H copy; call it where the result crosses to the host,
-        i.e. where the API synchronises anyway).  The two-CU GRU raises its flag when a partner workgroup did not
-        answer within the bounded spin (vfx_gru.hip); the frames after that point were never written, so the
-        waveform must not be returned: ``GruHandoffMissed`` -- ``run_checked`` turns it into a re-run."""
+        """Read the device-side error flags (ONE 4-byte D2H copy, two under set_math("f16"); call it where the result
+        crosses to the host, i.e. where the API synchronises anyway).  The two-CU GRU raises its flag when a partner
+        workgroup did not answer within the bounded spin (vfx_gru.hip); the frames after that point were never written, so
+        the waveform must not be returned: ``GruHandoffMissed``.  An f16 launch raises its flag when an operand left the
+        fp16 range; its output is unspecified: ``F16RangeExceeded``.  Both carry which flags were set (``gru``, ``f16``);
+        ``run_checked`` turns them into a re-run."""
+        gru = False
         flag = self.restorer.gru_err
         if flag is not None and int(flag.item()) != 0:
             flag.zero_()
-            raise GruHandoffMissed("vfx_gru_bidir2_f32: a partner workgroup missed the bounded hand-off spin "
-                                   "(GRU output incomplete); the result of this call was discarded")
+            gru = True
+        f16 = self.vocoder.read_f16_flag()
+        if gru:
+            e = GruHandoffMissed("vfx_gru_bidir2_f32: a partner workgroup missed the bounded hand-off spin "
+                                 "(GRU output incomplete); the result of this call was discarded")
+        elif f16:
+            e = F16RangeExceeded("vfx_conv1d_f16: an activation operand left the fp16 range; the result of this call "
+                                 "was discarded")
+        else:
+            return
+        e.gru, e.f16 = gru, f16
+        raise e
+
+    @property
+    def f16_fallbacks(self):
+        """Calls re-run in fp32 because an f16 launch left the fp16 range."""
+        return self.vocoder.f16_fallbacks
+
+    @contextlib.contextmanager
+    def fallback(self, err):
+        """While the block runs, the launches take the fallback every flag of ``err`` (DeviceFlagRaised) asks for: the
+        recurrences on ``vfx_gru_bidir_f32`` (one workgroup per sequence, nothing to miss) and / or every f16 launch in
+        fp32; the counters record a re-run that completed."""
+        self.restorer.gru_single = self.restorer.gru_single or err.gru
+        self.vocoder.f16_off = self.vocoder.f16_off or err.f16
+        try:
+            yield
+            if err.gru:
+                self.gru_retries = getattr(self, "gru_retries", 0) + 1
+            if err.f16:
+                self.vocoder.f16_fallbacks += 1
+        finally:
+            self.restorer.gru_single = False
+            self.vocoder.f16_off = False
 
     def run_checked(self, fn):
-        """``fn()`` (one API call's worth of launches, returning HOST data) followed by ``check()``.  If the two-CU GRU
-        reported a missed hand-off, the call is not lost: it is issued again with the recurrences on
-        ``vfx_gru_bidir_f32`` -- one workgroup per sequence, no inter-workgroup traffic, nothing to miss (3.6 instead of
-        2.2 us per step) -- and the two-CU kernel is back for the next call."""
+        """``fn()`` (one API call's worth of launches, returning HOST data) followed by ``check()``.  If a device flag was
+        raised, the call is not lost: it is issued again with the fallback the flag asks for (``fallback``) -- for a missed
+        GRU hand-off the recurrences on ``vfx_gru_bidir_f32`` (3.6 instead of 2.2 us per step), for an f16 range overflow
+        every launch in fp32 -- and the fast kernels are back for the next call."""
         out = fn()
         try:
             self.check()
             return out
-        except GruHandoffMissed:
-            self.restorer.gru_single = True
-            try:
+        except DeviceFlagRaised as e:
+            with self.fallback(e):
                 out = fn()
                 self.check()
-                self.gru_retries = getattr(self, "gru_retries", 0) + 1
-                return out
-            finally:
-                self.restorer.gru_single = False
+            return out
 
     def stage_report(self, wav, N):
         """The path's intermediates for one batch (selfcheck / parity tests): dict of device tensors -- "mel" (B,T,128),
@@ -670,7 +781,8 @@ class Pipeline:
         # too: a captured graph has the two-CU kernel baked in (replaying it would not be the miss-proof re-run), and a
         # shape first seen during a re-run would be captured with the slower one-workgroup kernel for good.
         if graphs is not None and vocoder_func is None and ops.PROFILE is None and wav.shape[0] <= self._graph_cap[1] \
-                and N >= 1025 and getattr(self, "_n_streams", 1) == 1 and not self.restorer.gru_single:
+                and N >= 1025 and getattr(self, "_n_streams", 1) == 1 and not self.restorer.gru_single \
+                and not self.vocoder.f16_off:
             key = (wav.shape[0], N)
             ent = graphs.pop(key, None)
             if ent is None:

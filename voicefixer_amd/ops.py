@@ -144,6 +144,26 @@ def conv1d(x, w, bias, y, L, k, dilation=1, pad_mode=PAD_ZERO, act=None, res=Non
     _prof_end(e0, B * L * cin * cout * k)
 
 
+def conv1d_f16(x, w16, bias, y, L, dilation, act=None, res=None, flag=None):
+    """The opt-in f16 arithmetic of a wide ResStack convolution (vfx_conv1d_f16): x (B,C,>=L) -> y (B,C,>=L), k = 3, zero
+    padding, w16 = packing.pack_f16 on the device; ``flag`` (device int32 (1,)) is raised when an activation operand leaves
+    the fp16 range.  Returns False, launching nothing, when the library does not take the launch (VFX_ENOTSUP): the caller
+    then runs it on ``conv1d``."""
+    _need_cuda(x, w16, y, res, bias, flag)
+    assert w16.dtype == torch.float16
+    B, cn = x.shape[0], x.shape[1]
+    xd, yd = tdesc(x), tdesc(y)
+    rd = tdesc(res) if res is not None else None
+    e0 = _prof_begin()
+    rc = _lib.lib().vfx_conv1d_f16(C.byref(xd), _ptr(w16), _ptr(bias), C.byref(rd) if rd is not None else None,
+                                   C.byref(yd), B, cn, L, dilation, _act(act), _ptr(flag), _stream())
+    if rc == _lib.ENOTSUP:
+        return False
+    check(rc, "vfx_conv1d_f16")
+    _prof_end(e0, B * L * cn * cn * 3)
+    return True
+
+
 def resblock(x, y, w1d, b1, w2d, b2, L, dilation, slope=0.01, post=POST_NONE, post_slope=0.0, w2g=None, w2g4=None, w1g4=None):
     """One fused ResStack layer (vfx_resblock_f32): x (B,C,>=L) guarded view -> y (B,C,>=L), y must not alias x.
     ``w2g`` (packing.pack_wino of the second convolution, optional): its dilation-1 half runs as Winograd F(2,3);

@@ -146,3 +146,22 @@ def pack_x3(w_packed):
     planes = torch.stack([hi, lo], dim=1)                       # [slab][plane][Cin][Cout]
     planes = planes.reshape(s, 2, c16 // 16, 2, 8, cout)        # [slab][plane][chunk][k-half][k][Cout]
     return planes.permute(0, 2, 1, 3, 5, 4).contiguous()        # [slab][chunk][plane][k-half][Cout][k]
+
+
+F16_MAX = 65504.0
+
+
+def pack_f16(w_packed):
+    """[3][CinPad][Cout] float32 (tap slabs of a k = 3 Conv1d, Cin == Cout) -> the fp16 weights of vfx_conv1d_f16:
+    ``[3][C/8][C][8]`` float16, element [t][c8][n][e] = w[t][8 c8 + e][n], rounded to nearest even (the A operand of
+    v_mfma_f32_32x32x16_f16: a lane reads the 8 consecutive input channels of one output channel as 16 bytes).
+    Returns None when the shape is not C = Cin = Cout in {128, 256, 512} or a weight is outside the fp16 range (the layer
+    then stays fp32)."""
+    s, cin, cout = w_packed.shape
+    if s != 3 or cin != cout or cout not in (128, 256, 512):
+        return None
+    w = w_packed.float()
+    if not bool(torch.isfinite(w).all()) or float(w.abs().max()) > F16_MAX:
+        return None
+    w = w.reshape(3, cin // 8, 8, cout).permute(0, 1, 3, 2)        # [t][c8][n][e]
+    return w.to(torch.float16).contiguous()
