@@ -281,7 +281,9 @@ def stft_mel(wav, mel, N):
 
 
 def stft_mel_rows(wav, mel, n_rows, T):
-    """wav (B, >= max n) device float32, n_rows device int32 (B,) with 1 + n // 441 == T for every row -> mel (B, T, 128)."""
+    """wav (B, >= max n) device float32, n_rows device int32 (B,) (every n >= 1025) -> mel (B, T, 128): row b gets its own
+    1 + n_rows[b] // 441 frames; T is the row pitch of mel and must be >= every row's frame count (frames past a row's
+    own count are not written)."""
     _need_cuda(wav, mel, n_rows)
     frontend_init()
     assert wav.stride(1) == 1 and mel.is_contiguous() and n_rows.dtype == torch.int32
