@@ -134,6 +134,8 @@ uint64_t vfx_launch_count(void);
  *   code 71 / 72 / 74 convw_kernel<BM,BL,*,*,3,*,2>              (vfx_resblock_f32 with w2_wino: second half as Winograd F(2,3))
  *   code 91 / 92 / 94 convw_kernel<BM,BL,*,*,3,*,3>              (vfx_resblock_f32 with w2_wino4: second half as Winograd F(4,3))
  *   code 96           resblk4_kernel                             (vfx_resblock_f32 with w1_wino4 + w2_wino4: both halves F(4,3))
+ *   code 97           resblk4s_kernel                            (vfx_resblock_wino4_f32 at a dilation resblk4_kernel does not take:
+ *                     both halves F(4,3) on a strip tile)
  *   code 80           convwg4_kernel<..>                          (Winograd F(4,3), 1-D), BL = output positions
  *   code 81           convwg4p_kernel<..>                         (the same tile on persistent workgroups: the two long launches of a
  *                     ResStack layer, tap / staging / weight pipeline running across tiles)
@@ -199,6 +201,14 @@ typedef struct {
 } vfx_resblock_w;
 int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L,
                      int dilation, float slope, int post_act, float post_slope, vfx_stream_t stream);
+
+/* The same layer with both convolutions as Winograd F(4,3) at EVERY dilation, one launch: resblk4_kernel where
+ * vfx_resblock_f32 would take it (d = 1, 3, 9, 27), resblk4s_kernel (a strip tile: a workgroup owns one or two
+ * sub-ranges of a block of 4 d positions, the four strips a dilation apart) everywhere else.  C = 64; w1_wino4 and
+ * w2_wino4 required (the direct and F(2,3) weights are not read); rows of x and y 16-byte aligned with lstride 1; y must
+ * not alias x; x needs no guard band.  Returns VFX_ENOTSUP for anything else (the caller picks another form). */
+int vfx_resblock_wino4_f32(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L,
+                           int dilation, float slope, int post_act, float post_slope, vfx_stream_t stream);
 
 /* ConvTranspose1d(Cin, Cout, kernel 2s, stride s, padding s/2 + s%2, output_padding s%2):
  * Lin -> s*Lin.  Polyphase: s phases x 2 taps.  w_packed = [2s][CinPad][Cout], slab k is

@@ -145,6 +145,7 @@ struct ConvArgs {
     int yp;                 // row pitch of the intermediate tile (floats)
     float mid_slope;        // leaky-ReLU between the two convolutions
     int rb_nq1;             // resblk4_kernel: quads of the first (dilated) half per tile = whole blocks of 4d columns x d
+    int rs_pshift, rs_nseg; // resblk4s_kernel: log2 of the strip pitch P, segments of W = P - 4 positions per block of 4d
 };
 
 // Staging slots per thread.  The host picks KC (8 or 4) so that the activation tile never needs
@@ -1225,6 +1226,7 @@ static float* splitk_workspace(hipStream_t s, size_t bytes) {
 #include "vfx_convtw.inc"
 #include "vfx_convwg2d.inc"
 #include "vfx_resblk4.inc"
+#include "vfx_resblk4s.inc"
 #include "vfx_convh.inc"
 
 template <int BM, int BL, int WGM, int WGL, int NT, int MODE, int ROWS = 1>

@@ -22,7 +22,11 @@
 // convolution's zero padding), scattered into Y (which aliases the staging buffers: every wave is past its last fragment read).
 // Second half: see convw_kernel<.., FUSED = 3>.
 // Per-row lengths (ragged batches) as everywhere: taps and Y columns past the row's own end are zero, tiles past it return.
-__global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
+// The body is shared with resblk4s_kernel (vfx_resblk4s.inc, STRIP = true): the two differ in the tile geometry only -- which
+// quads the first half computes (quad_p / quad_ok), where their outputs go in Y (quad_col, ystep), and which output quads the second
+// half owns (qq, nown, yc2).  Staging, MFMAs, the transform between the halves, the second half and the epilogue are one code.
+template <bool STRIP>
+__device__ __forceinline__ void resblk4_body(const ConvArgs& a) {
     constexpr int C = 64, KC = 16, NSTEP = KC / 2, S = C / KC;
     constexpr int BQ = 64, CG = 256 / BQ, NSLOT = KC / CG;      // 4 channel groups, 4 staged elements per thread and chunk
     constexpr int PLANE = KC * BQ, BUF = 6 * PLANE;
@@ -42,26 +46,54 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
     const int d = a.wg_d;
     const float inv_d = 1.0f / (float)d;
     const int Lrow = a.x_rows ? __builtin_amdgcn_readfirstlane(a.x_rows[b]) : a.Lin;
-    const int q0 = bx * a.bl_step;                // first OUTPUT position of this tile (a multiple of 4)
-    if (q0 >= Lrow) return;
-    const int qend = min(Lrow, q0 + a.bl_step);
-    const int y0 = q0 - 1;                        // position of Y column 0
-    const int nq1 = a.rb_nq1;                     // quads of the first half: NB * d
     const int xcs = (int)a.x_cs;
-    auto quad_u0 = [&](int Q) {                   // Y column of output 0 of first-half quad Q (blocks of 4d columns)
+    // ---- tile geometry
+    // block tile (resblk4_kernel): Y columns [q0 - 1, q0 - 1 + W), NB whole blocks of 4d columns, outputs [q0, q0 + bl_step)
+    const int q0 = STRIP ? 0 : bx * a.bl_step;    // first OUTPUT position of this tile (a multiple of 4)
+    const int nq1 = a.rb_nq1;                     // quads of the first half: NB * d
+    // strip tile (resblk4s_kernel): G = 64 / P segments, segment n = G bx + g of the row covers r in [r0, r0 + W) of block blk
+    const int pshift = STRIP ? a.rs_pshift : 6, P = 1 << pshift, W = P - 4;
+    int sstart[2] = {0, 0}, sr0[2] = {0, 0};      // per segment of the tile: first output position of strip 0, r0
+    if constexpr (STRIP) {
+        const int nseg = a.rs_nseg;
+        const float inv_nseg = 1.0f / (float)nseg;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int n = (bx << (6 - pshift)) + g;
+            const int blk = fast_div(n, nseg, inv_nseg);
+            sr0[g] = (n - blk * nseg) * W;
+            sstart[g] = 4 * d * blk + sr0[g];
+        }
+    }
+    if ((STRIP ? sstart[0] : q0) >= Lrow) return;
+    auto quad_u0 = [&](int Q) {                   // block tile: Y column of output 0 of first-half quad Q (blocks of 4d columns)
         const int blk = fast_div(Q, d, inv_d);
         return 4 * d * blk + (Q - blk * d);
     };
+    auto quad_p = [&](int Q) {                    // position of output 0 of first-half quad Q
+        if constexpr (STRIP) return (Q >> pshift ? sstart[1] : sstart[0]) - 1 + (Q & (P - 1));   // segment Q >> pshift, column Q & (P - 1)
+        else return q0 - 1 + quad_u0(Q);
+    };
+    auto quad_ok = [&](int Q) {                   // (strip: W + 2 quads per segment)
+        if constexpr (STRIP) return (Q & (P - 1)) < P - 2;
+        else return Q < nq1;
+    };
+    auto quad_col = [&](int Q) {                  // Y column of its output 0; output i lies ystep columns further (strip: Y strip 4 g + i)
+        if constexpr (STRIP) return ((Q >> pshift) << (pshift + 2)) + (Q & (P - 1));
+        else return quad_u0(Q);
+    };
+    const int ystep = STRIP ? P : d;
 
     // ================================================================ first half: conv_k3_dil as F(4,3) along the dilated axis
     const int sq = tid % BQ, cg = tid / BQ;
     int xvoff[6];
     {
-        const int p0 = y0 + quad_u0(sq);
+        const int p0 = quad_p(sq);
+        const bool qok = quad_ok(sq);
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             const int p = p0 + (j - 1) * d;
-            xvoff[j] = (sq < nq1 && p >= 0 && p < Lrow) ? (cg * xcs + p) * 4 : VFX_W_OOB;   // outside the row: reads 0 = the zero padding
+            xvoff[j] = (qok && p >= 0 && p < Lrow) ? (cg * xcs + p) * 4 : VFX_W_OOB;   // outside the row: reads 0 = the zero padding
         }
     }
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -211,15 +243,36 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
         }
     };
     const int Qi = 32 * wq + lo;                  // second half: output quad of this lane within the tile
-    const int qq = q0 + 4 * Qi;                   // its first output position
-    const bool full = qq + 3 < qend;
-    const bool has_tail = (qend & 3) != 0;        // (uniform) the tile ends inside a quad
+    int qq, nown, yc2;                            // its first output position, how many of its 4 outputs the tile owns, its Y column
+    bool has_tail;                                // (wave-uniform) some quad is partly owned
+    if constexpr (STRIP) {
+        // quad jq of strip t (strip i = t & 3 of segment g = t >> 2), W / 4 quads per strip.  Its four positions are consecutive
+        // but not 16-byte aligned (d is odd): residual and stores are unaligned dwordx4 accesses.  An output belongs to this tile
+        // when its r = r0 + 4 jq + e < d (r >= d is the next strip's, computed by another tile) and it lies inside the row.
+        const int nq2s = W >> 2;
+        int t = fast_div(Qi, nq2s, 1.0f / (float)nq2s);
+        const int jq = Qi - t * nq2s;
+        const bool sok = t < (4 << (6 - pshift));
+        t = sok ? t : 0;
+        const int rr = ((t >> 2) ? sr0[1] : sr0[0]) + 4 * jq;
+        qq = ((t >> 2) ? sstart[1] : sstart[0]) + (t & 3) * d + 4 * jq;
+        nown = sok ? min(Lrow - qq, d - rr) : 0;
+        has_tail = __any(nown > 0 && nown < 4);
+        yc2 = (t << pshift) + 4 * jq;
+    } else {
+        const int qend = min(Lrow, q0 + a.bl_step);
+        qq = q0 + 4 * Qi;
+        nown = qend - qq;
+        has_tail = (qend & 3) != 0;               // (uniform) the tile ends inside a quad
+        yc2 = 4 * Qi;
+    }
+    const bool full = nown >= 4;
     const int rvq = full ? (4 * hi * xcs + qq) * 4 : VFX_W_OOB;
     const int yvq = full ? (4 * hi * (int)a.y_cs + qq) * 4 : VFX_W_OOB;
-    int rv1[4], yv1[4];                           // single elements: the straddling quad only
+    int rv1[4], yv1[4];                           // single elements: the partly owned quads only
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const bool one = !full && qq + i < qend;
+        const bool one = !full && i < nown;
         rv1[i] = one ? (4 * hi * xcs + qq + i) * 4 : VFX_W_OOB;
         yv1[i] = one ? (4 * hi * (int)a.y_cs + qq + i) * 4 : VFX_W_OOB;
     }
@@ -244,15 +297,15 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
     {
         const float ms = a.mid_slope;
         const int Q1 = 32 * wq + lo;              // first-half quad of this lane's accumulator column
-        const int u0 = quad_u0(Q1);
+        const int p1 = quad_p(Q1);
         bool ok[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int p = y0 + u0 + i * d;
+            const int p = p1 + i * d;
             ok[i] = p >= 0 && p < Lrow;           // conv-2's zero padding: Y is zero outside the sequence
         }
-        if (Q1 < nq1) {
-            float* ycol = Y + (row1 + 4 * hi) * yp + u0;
+        if (quad_ok(Q1)) {
+            float* ycol = Y + (row1 + 4 * hi) * yp + quad_col(Q1);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float p12 = acc[1][r] + acc[2][r], m12 = acc[1][r] - acc[2][r];
@@ -264,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
                 v[3] = fmaf(8.f, m34, m12) + acc[5][r];
                 float* yr = ycol + ((r & 3) + 8 * (r >> 2)) * yp;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) yr[i * d] = ok[i] ? fmaxf(v[i], v[i] * ms) : 0.f;
+                for (int i = 0; i < 4; ++i) yr[i * ystep] = ok[i] ? fmaxf(v[i], v[i] * ms) : 0.f;
             }
         }
     }
@@ -308,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
             accq[5][r] = t3 - m1 - 8.f * m3;
         }
     }
-    const float* yb = Y + hi * yp + 4 * Qi;
+    const float* yb = Y + hi * yp + yc2;
     auto group = [&](auto set_tag, int grp, int nxt) {
         constexpr int SET = decltype(set_tag)::value;
         const float* yg = yb + grp * 8 * yp;
@@ -401,19 +454,16 @@ __global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) {
     }
 }
 
-// vfx_resblock_f32 (include/vfx_hip.h): one ResStack layer, fused.  With both F(4,3) transforms offered, C = 64, a dilation whose
-// blocks of 4d positions fill a 256-column tile (d <= 32 with at least 48 of the 64 quad columns used: the stage's d = 1, 3, 9, 27)
-// and 16-byte aligned rows: resblk4_kernel.  Anything else: resblock_convw (vfx_convw.inc) decides.
-extern "C" int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L,
-                                int dilation, float slope, int post_act, float post_slope, vfx_stream_t stream) {
-    if (!w) return VFX_EINVAL;
-    const float *w1_direct = w->w1_direct, *bias1 = w->bias1, *w2_direct = w->w2_direct, *bias2 = w->bias2;
-    const float *w2_wino = w->w2_wino, *w2_wino4 = w->w2_wino4, *w1_wino4 = w->w1_wino4;
-    static const bool off = (VFX_DEV_ENV("VFX_FUSE_WINO44") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO44")) == 0) ||
-                            (VFX_DEV_ENV("VFX_FUSE_WINO4") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO4")) == 0) ||
-                            (VFX_DEV_ENV("VFX_FUSE_WINO") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO")) == 0);   // development
-    bool ok = !off && x && y && x->ptr && y->ptr && w1_wino4 && w2_wino4 && C == 64 && B > 0 && B <= 65535 && L > 0 && dilation >= 1 &&
-              dilation <= 32 && x->ptr != y->ptr;
+__global__ __launch_bounds__(256, 2) void resblk4_kernel(const ConvArgs a) { resblk4_body<false>(a); }
+
+
+// Argument checks and kernel arguments shared by resblk4_kernel and resblk4s_kernel (vfx_resblk4s.inc): C = 64, both F(4,3)
+// weight sets, 16-byte aligned rows with unit stride, x and y distinct, every byte offset of a batch item within 32 bits.
+static bool resblk4_args_ok(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L, int dilation,
+                            float slope, int post_act, float post_slope) {
+    const float *bias1 = w->bias1, *bias2 = w->bias2, *w2_wino4 = w->w2_wino4, *w1_wino4 = w->w1_wino4;
+    bool ok = x && y && x->ptr && y->ptr && w1_wino4 && w2_wino4 && C == 64 && B > 0 && B <= 65535 && L > 0 && dilation >= 1 &&
+              x->ptr != y->ptr;
     if (ok) {
         ok = vfx_aligned16(w1_wino4) && vfx_aligned16(w2_wino4) && vfx_aligned16(x->ptr) && vfx_aligned16(y->ptr) && x->lstride == 1 &&
              y->lstride == 1 && ((x->cstride | x->bstride | y->cstride | y->bstride) & 3) == 0 &&
@@ -421,18 +471,17 @@ extern "C" int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const 
              !(post_act == VFX_POST_LRELU && !(post_slope >= 0.f && post_slope <= 1.f)) &&
              ((long long)C * x->cstride + L) * 4 < (1ll << 31) - (1ll << 20) && ((long long)C * y->cstride + L) * 4 < (1ll << 31) - (1ll << 20);
     }
-    const int nb = ok ? 256 / (4 * dilation) : 0;
-    if (!ok || nb < 1 || nb * dilation < 48) {
-        return resblock_convw(x, y, w1_direct, bias1, w2_direct, bias2, w2_wino, w2_wino4, B, C, L, dilation, slope, post_act,
-                              post_slope, stream);
-    }
-    ConvArgs a;
+    return ok;
+}
+
+static void resblk4_fill_args(ConvArgs& a, const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L,
+                              int dilation, float slope, int post_act, float post_slope) {
     std::memset(&a, 0, sizeof(a));
     a.x = (const float*)x->ptr;
-    a.wd = w1_wino4;
-    a.wd2 = w2_wino4;
-    a.bias = bias1;
-    a.bias2 = bias2;
+    a.wd = w->w1_wino4;
+    a.wd2 = w->w2_wino4;
+    a.bias = w->bias1;
+    a.bias2 = w->bias2;
     a.y = (float*)y->ptr;
     a.B = B; a.Cin = C; a.CinPad = C; a.Cout = C;
     a.Lin = L; a.Lq = L; a.Lout = L;
@@ -445,11 +494,25 @@ extern "C" int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const 
     a.post_act = post_act;
     a.post_slope = post_slope;
     a.wg_d = dilation;
+    a.yp = 260;
+}
+
+// The 64-column F(4,3) tile takes a dilation whose blocks of 4d positions fill a 256-column tile: d <= 32 with at least 48 of
+// the 64 quad columns used (the stage's d = 1, 3, 9, 27).
+static bool resblk4_takes(int dilation) {
+    const int nb = 256 / (4 * dilation);
+    return dilation <= 32 && nb >= 1 && nb * dilation >= 48;
+}
+
+static int resblk4_launch(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L, int dilation,
+                          float slope, int post_act, float post_slope, vfx_stream_t stream) {
+    ConvArgs a;
+    resblk4_fill_args(a, x, y, w, B, C, L, dilation, slope, post_act, post_slope);
+    const int nb = 256 / (4 * dilation);
     const int W = 4 * dilation * nb;              // Y columns a tile computes
     const int nq2 = (W - 2) / 4;                  // output quads of the second half
     a.rb_nq1 = nb * dilation;
     a.bl_step = 4 * nq2;
-    a.yp = 260;
     const int ntiles = (L + a.bl_step - 1) / a.bl_step;
     const size_t lds = (size_t)C * a.yp * sizeof(float);   // 66 560 bytes (the staging buffers, 49 152, alias it)
     const dim3 grid(convw_grid_x(a, ntiles), 1, B);
@@ -466,4 +529,19 @@ extern "C" int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const 
     hipLaunchKernelGGL(resblk4_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
     VFX_LAUNCHED();
     return vfx_last_error();
+}
+
+// vfx_resblock_f32 (include/vfx_hip.h): one ResStack layer, fused.  With both F(4,3) transforms offered, C = 64, a dilation
+// resblk4_takes() and 16-byte aligned rows: resblk4_kernel.  Anything else: resblock_convw (vfx_convw.inc) decides.
+extern "C" int vfx_resblock_f32(const vfx_tensor* x, const vfx_tensor* y, const vfx_resblock_w* w, int B, int C, int L,
+                                int dilation, float slope, int post_act, float post_slope, vfx_stream_t stream) {
+    if (!w) return VFX_EINVAL;
+    static const bool off = (VFX_DEV_ENV("VFX_FUSE_WINO44") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO44")) == 0) ||
+                            (VFX_DEV_ENV("VFX_FUSE_WINO4") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO4")) == 0) ||
+                            (VFX_DEV_ENV("VFX_FUSE_WINO") && atoi(VFX_DEV_ENV("VFX_FUSE_WINO")) == 0);   // development
+    if (off || !resblk4_takes(dilation) || !resblk4_args_ok(x, y, w, B, C, L, dilation, slope, post_act, post_slope)) {
+        return resblock_convw(x, y, w->w1_direct, w->bias1, w->w2_direct, w->bias2, w->w2_wino, w->w2_wino4, B, C, L, dilation, slope,
+                              post_act, post_slope, stream);
+    }
+    return resblk4_launch(x, y, w, B, C, L, dilation, slope, post_act, post_slope, stream);
 }

@@ -102,6 +102,10 @@ _FUSE = _dev_env("VFX_FUSE", "1") != "0"
 # half is a direct sum there (a block of 4 d positions does not fit its tile): 18 GB instead of 10 GB through HBM per layer, but half the
 # products in the dilated half -- step 219.2 -> 217.6 ms alternating on one box (VFX_UNFUSE_WIDE=0 restores the fused form).
 _UNFUSE_WIDE = _dev_env("VFX_UNFUSE_WIDE", "1") != "0"
+# The C = 64 stage with both Winograd weight sets runs ALL its layers as one launch each with both halves F(4,3)
+# (vfx_resblock_wino4_f32: resblk4_kernel for d <= 27, the strip tile resblk4s_kernel for d >= 81), at every batch size;
+# VFX_WINO4_STAGE=0 restores the dispatch above (d >= 81 as two launches when B * Lo >= 2^18).
+_WINO4_STAGE = _dev_env("VFX_WINO4_STAGE", "1") != "0"
 FUSE_MAX_C = 128  # ResStack stages with at most this many channels CAN run one fused launch per layer
 # ResStack stages with at least this many channels run their two k = 3 convolutions per layer as two Winograd F(4,3)
 # launches (convwg4_kernel: half the fp32 MFMAs of the direct sum; the dilation-1 one moves its quads as 16-byte
@@ -295,13 +299,18 @@ class VocoderEngine:
                          wg4=_wg(upw[3]) if self.math != "bf16x3" else None)
             if stages is not None:
                 stages["up%d" % (j + 1)] = xs[:, :, :Lo].clone()
-            # The fused C = 64 stage runs its WIDELY dilated layers (d > 27: a block of 4 d positions does not fit the fused tile) as two
+            # The C = 64 stage with both Winograd weight sets (the default): every layer one launch with both halves F(4,3)
+            # (vfx_resblock_wino4_f32), ping-ponging xs / ys, at every launch size -- the strip tile has no minimum size, and batch 1
+            # and the long-form B = 8 x 30 s geometry were measured no slower than the dispatch below.
+            # Without it (VFX_WINO4_STAGE=0, or the weight sets missing) the round-6 dispatch: the WIDELY dilated layers (d > 27) as two
             # Winograd F(4,3) launches each, in place on xs, from the first such layer on.  Decided once per stage: the index must be
             # even (the fused ping-pong has the data back in xs there, and everything after it runs in place), and the launch must be
             # large enough for convwg4_kernel to take it (it declines fewer than 512 tiles: B * Lo / 256) -- a short single utterance
             # keeps the fused layer instead of falling to two non-Winograd launches.
+            wino4_stage = (fused and _WINO4_STAGE and c == 64 and _ARITH["winograd"] and
+                           all(l[7] is not None and l[8] is not None for l in layers))
             first_unfused = None
-            if (fused and _UNFUSE_WIDE and c == 64 and _ARITH["winograd"] and all(l[7] is not None and l[8] is not None for l in layers)
+            if (fused and not wino4_stage and _UNFUSE_WIDE and c == 64 and _ARITH["winograd"] and all(l[7] is not None and l[8] is not None for l in layers)
                     and B * Lo >= 1 << 18):
                 wide = [i for i in range(len(layers) - 1) if 3 ** i > 27 and i % 2 == 0]
                 first_unfused = wide[0] if wide else None
@@ -315,6 +324,9 @@ class VocoderEngine:
                     if last:
                         post, pslope = (POST_LRELU if j == nst - 1 else POST_LRELU_SNAKE), 0.2
                     src, dst = (xs, ys) if i % 2 == 0 else (ys, xs)
+                    if wino4_stage:
+                        ops.resblock_wino4(src, dst, _wg(w1g4), b1, _wg(w2g4), b2, Lo, 3 ** i, 0.01, post, pslope)
+                        continue
                     ops.resblock(src, dst, w1d, b1, w2d, b2, Lo, 3 ** i, 0.01, post, pslope, w2g=_wg(w2g), w2g4=_wg(w2g4),
                                  w1g4=_wg(w1g4))
                     continue

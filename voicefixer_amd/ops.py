@@ -181,6 +181,21 @@ def resblock(x, y, w1d, b1, w2d, b2, L, dilation, slope=0.01, post=POST_NONE, po
     _prof_end(e0, 2 * B * L * Cn * Cn * 3)
 
 
+def resblock_wino4(x, y, w1g4, b1, w2g4, b2, L, dilation, slope=0.01, post=POST_NONE, post_slope=0.0):
+    """One C = 64 ResStack layer with both convolutions as Winograd F(4,3) at any dilation, one launch (vfx_resblock_wino4_f32):
+    x (B,64,>=L) -> y (B,64,>=L), y must not alias x.  ``w1g4`` / ``w2g4``: packing.pack_wino4 of the two convolutions.
+    Raises where the kernel does not take the layer (alignment, 32-bit offsets, y aliasing x)."""
+    _need_cuda(x, y, w1g4, b1, w2g4, b2)
+    B, Cn = x.shape[0], x.shape[1]
+    xd, yd = tdesc(x), tdesc(y)
+    e0 = _prof_begin()
+    wts = _lib.vfx_resblock_w(None, _ptr(b1), None, _ptr(b2), None, _ptr(w2g4), _ptr(w1g4))
+    rc = _lib.lib().vfx_resblock_wino4_f32(C.byref(xd), C.byref(yd), C.byref(wts), B, Cn, L, dilation, float(slope), post,
+                                           float(post_slope), _stream())
+    check(rc, "vfx_resblock_wino4_f32")
+    _prof_end(e0, 2 * B * L * Cn * Cn * 3)
+
+
 def convtr1d(x, w, bias, y, Lin, stride, act=None, w3=None, wd=None, wg4=None):
     """``wg4`` (packing.pack_wino32_tr on the device) offers the launch the Winograd F(3,2) kernel (convtw_kernel)."""
     _need_cuda(x, w, y, bias)
