@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the MI355X VoiceFixer restore path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--seconds 10] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: it builds the pipeline and the resident inputs, runs the W warm-up
+and the K timed steps, writes ``--dump-outputs`` if asked and prints the JSON line (``value``, ``ms_per_step`` and the description
+of the run).  ``--full`` adds everything else the line can carry (``host_to_host``, ``roofline``, ``clocks``, ``single_stream``,
+``bf16x3_optin``, ``cpu_baseline``, ``one_rank_leg``, below), after the timed steps, which are the same in both modes.
 
 Launched PLAIN with ``--gpus N`` (N > 1, no WORLD_SIZE in the environment) the script starts the ranks itself: it
 re-executes under ``torch.distributed.run --nnodes=1 --nproc-per-node min(N, visible devices)`` on 127.0.0.1 (one
@@ -16,7 +21,7 @@ take DIFFERENT batches (a ring of three resident batches).  With N > 1 each rank
 batches (utterances shard embarrassingly; no data-path collective): weak scaling,
 ``value`` = all ranks' audio seconds / max-over-ranks wall time.
 
-``host_to_host`` (same JSON line) is the metric as SURVEY.md 8(d) defines it: pinned host waveforms in,
+``host_to_host`` (``--full``, same JSON line) is the metric as SURVEY.md 8(d) defines it: pinned host waveforms in,
 pinned host waveforms out, H2D and D2H on copy streams, the compute alternating over the same HIP streams as the timed
 region, everything inside the timed region.  The host runs up to THREE steps ahead of the oldest unfinished D2H (three slots of
 pinned input / output and device input, what ``VoiceFixer.restore_batches`` keeps in flight: one batch per stream running and one
@@ -28,7 +33,7 @@ figure therefore sits beside it as ``value_host_to_host``.
 ``dist.restore_sharded`` scatters them over RCCL (backend "nccl"), every rank restores its 256 in batches of
 ``--batch``, rank 0 gathers; the JSON line then reports the whole job (scatter + compute + gather).
 
-The JSON line also carries
+With ``--full`` the JSON line also carries
   roofline      -- the dominant kernel FAMILY (what one regex over rocprofv3's kernel names selects; at batch 32 the
                    Winograd F(4,3) ResStack convolutions convwg4[p]_kernel<4,1,...>): executed FLOPs per launch / average
                    launch duration from HIP events on the launch stream (single-stream leg: un-overlapped durations),
@@ -41,10 +46,11 @@ The JSON line also carries
                    N = 1 only); ``reference_over_port`` = the measured time ratio of the reference's own modules to the port
                    (tools/cpu_reference_vs_port.py, build container, where /root/reference exists).  Test infrastructure
                    used as a reported baseline, never shipped.
-With N > 1 ranks the line also carries ``one_rank_leg`` (rank 0 alone, the other ranks idle at a barrier, same K steps) and
+With ``--full`` and N > 1 ranks the line also carries ``one_rank_leg`` (rank 0 alone, the other ranks idle at a barrier, same K steps) and
 ``scaling_efficiency_self_measured`` = value / (N x that leg's value): a convenience for reading a log, the driver computes its own.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -637,6 +643,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the single-stream leg and the "
+                         "roofline, clocks, the bf16x3 timing, the host-to-host leg, the CPU baseline and (N > 1) the one-rank leg; "
+                         "--no-cpu-baseline, --no-bf16x3 and --no-host-leg leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--streams", type=int, default=2,
                     help="issue consecutive steps (one batch each) round-robin on this many HIP streams: 2 = the product "
@@ -772,10 +782,10 @@ def main():
         streams = SINGLE
     out = run_steps(args.warmup)
     barrier()
-    # ---- (N > 1 ranks) one-rank leg: rank 0 runs the K steps ALONE while the other ranks wait at the barrier -- the N = 1 rate of
-    # this very job on this very node, so that the line can say what N ranks made of it (no events, same streams)
+    # ---- (--full, N > 1 ranks) one-rank leg: rank 0 runs the K steps ALONE while the other ranks wait at the barrier -- the N = 1
+    # rate of this very job on this very node, so that the line can say what N ranks made of it (no events, same streams)
     one_rank = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         if rank == 0:
             t1 = time.perf_counter()
             run_steps(args.steps)
@@ -785,9 +795,11 @@ def main():
                         "ms_per_step": round(d1 / args.steps * 1e3, 3), "steps": args.steps,
                         "note": "rank 0 alone on its device, every other rank idle at a barrier; same build, same streams"}
         barrier()
-    sampler = ClockSampler(dev.index)
+    sampler = ClockSampler(dev.index) if args.full else contextlib.nullcontext()
     if not args.no_events:
-        # pre-created timing events (creating one costs ~10 us of host time: visible in a launch-bound batch-1 run)
+        # the timed steps bracket every conv-family launch with HIP events in both modes (what they cost is part of ms_per_step);
+        # only --full reads them.  Pre-created timing events (creating one costs ~10 us of host time: visible in a launch-bound
+        # batch-1 run)
         ops.EVENT_POOL = [torch.cuda.Event(enable_timing=True) for _ in range(800 * max(args.steps, 1) * (2 if len(streams) > 1 else 1))]
         for e in ops.EVENT_POOL[:8]:
             e.record()  # first use of an event allocates its backing object
@@ -798,7 +810,8 @@ def main():
         out = run_steps(args.steps)
         barrier()
         dt = time.perf_counter() - t0
-    clocks = {"timed_region": sampler.summary(t0 + 0.25 * dt, t0 + dt)}   # (the first quarter: the clock is still ramping)
+    if args.full:
+        clocks = {"timed_region": sampler.summary(t0 + 0.25 * dt, t0 + dt)}   # (the first quarter: the clock is still ramping)
     prof, ops.PROFILE = ops.PROFILE, None
     if args.dump_outputs and rank == 0:
         written = dump_outputs(args.dump_outputs, {"restored": out})
@@ -810,6 +823,57 @@ def main():
         return
     assert torch.isfinite(out).all()
     pipe.check()  # device-side error flags (two-CU GRU hand-off)
+
+    per_rank = [{"rank": 0, "device": "cuda:%d" % dev.index, "wall_s": round(dt, 4)}]
+    if dist is not None:
+        xdev = dev if dist.get_backend() == "nccl" else None      # (the --oversubscribe rehearsal runs its collectives on gloo: host tensors)
+        mine = torch.tensor([dt, float(dev.index)], device=xdev, dtype=torch.float64)
+        allr = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(allr, mine)
+        per_rank = [{"rank": r, "device": "cuda:%d" % int(x[1]), "wall_s": round(float(x[0]), 4)}
+                    for r, x in enumerate(allr)]
+        dt = max(float(x[0]) for x in allr)   # max over ranks
+    audio_seconds = world * args.batch * args.seconds * args.steps
+    value = audio_seconds / dt
+    line = {
+        "metric": "seconds-of-44.1kHz-audio restored per wall-second",
+        # n_gpus counts DISTINCT devices (an --oversubscribe rehearsal puts several ranks on one); `ranks` = processes that ran
+        "value": round(value, 2), "unit": "x real-time", "n_gpus": len({pr["device"] for pr in per_rank}), "ranks": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.math, "data": "synthetic",
+        "value_definition": ("whole-job audio seconds per wall second with the inputs resident in HBM when the timed region "
+                             "starts and the outputs left there (the bench contract); value_host_to_host (--full) = the same from "
+                             "pinned host waveforms to pinned host waveforms, H2D / D2H inside the timed region (SURVEY.md 8(d))"),
+        "config": {"workload": ("batched folder restore (BASELINE configs[2]): one batch of %d x %.0f s 44.1 kHz "
+                                "utterances per step, VoiceFixer.restore mode 0, seeded random weights"
+                                % (args.batch, args.seconds)) if args.batch > 1 else
+                               ("VoiceFixer.restore mode 0, single %.0f s 44.1 kHz mono utterance per step (BASELINE configs[1]%s), "
+                                "seeded random weights" % (args.seconds, "" if abs(args.seconds - 10.0) < 1e-9 else " at another length")),
+                   "batch_per_gpu": args.batch, "utterance_seconds": args.seconds, "frames": 1 + n // 441,
+                   "arithmetic": ("fp32 operands, fp32 MFMA accumulation everywhere; k=3 / 3x3 convolutions evaluated as Winograd "
+                                  "F(4,3) (the C=64 stage: one fused launch per layer with both halves F(4,3) for dilations <= 27, two F(4,3) launches for the wider ones): half "
+                                  "of the direct sum's products, rounding ~3x the direct sum's (DESIGN.md 3.0b; engine.set_winograd(False) / --selfcheck run the direct sums)") if args.math == "f32"
+                                 else "opt-in split-bf16 products (three bf16 MFMAs per fp32 product), fp32 accumulation",
+                   "parallelism": "utterance sharding x%d (no data-path collective)" % world},
+        "streams": len(streams),
+        "path_tflops": round(2.0 * path_macs(n) * args.batch * world * args.steps / dt / 1e12, 2),
+        "requested_gpus": requested, "visible_devices": torch.cuda.device_count(),
+        "rccl": {"backend": dist.get_backend() if dist is not None else None, "world_size": world},
+        "per_rank": per_rank,
+        "lib_build_id": build_id,
+        "full": args.full,
+    }
+    if requested != world:
+        line["note_gpus"] = ("--gpus %d was requested, %d rank(s) ran (visible HIP devices: %d)"
+                             % (requested, world, torch.cuda.device_count()))
+    if not args.full:
+        ops.EVENT_POOL = None
+        if rank == 0:
+            _json_line_last(line)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # ---- second leg (only when the timed region ran on several streams): the same K steps on ONE stream.  Its wall time is
     # `single_stream`; its per-launch HIP events are what the roofline is computed from -- in the multi-stream timed region the
     # kernels of two batches share the chip, so an event bracket there also contains the other stream's work (reported beside
@@ -830,16 +894,6 @@ def main():
         pipe.set_streams(len(streams))
     ops.EVENT_POOL = None
     last_idx = (args.steps - 1) % NRING  # ``out`` is the restoration of ring[last_idx]
-
-    per_rank = [{"rank": 0, "device": "cuda:%d" % dev.index, "wall_s": round(dt, 4)}]
-    if dist is not None:
-        xdev = dev if dist.get_backend() == "nccl" else None      # (the --oversubscribe rehearsal runs its collectives on gloo: host tensors)
-        mine = torch.tensor([dt, float(dev.index)], device=xdev, dtype=torch.float64)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [{"rank": r, "device": "cuda:%d" % int(x[1]), "wall_s": round(float(x[0]), 4)}
-                    for r, x in enumerate(allr)]
-        dt = max(float(x[0]) for x in allr)   # max over ranks
 
     # ---- roofline bookkeeping for the dominant MFMA kernel family (this rank) ----
     # vfx_last_conv_tile() = BM*100000 + BL*100 + code; code 51/52/54: convw_kernel (1-D, chunk depth 8/16/32),
@@ -1008,40 +1062,11 @@ def main():
                                        "hbm_gbps": round(stft_bytes / stft_secs / 1e9, 1),
                                        "hbm_frac_of_8TBps": round(stft_bytes / stft_secs / 8.0e12, 4),
                                        "avg_launch_ms": round(stft_secs / stft_n * 1e3, 4)}
-    audio_seconds = world * args.batch * args.seconds * args.steps
-    value = audio_seconds / dt
-    line = {
-        "metric": "seconds-of-44.1kHz-audio restored per wall-second",
-        # n_gpus counts DISTINCT devices (an --oversubscribe rehearsal puts several ranks on one); `ranks` = processes that ran
-        "value": round(value, 2), "unit": "x real-time", "n_gpus": len({pr["device"] for pr in per_rank}), "ranks": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.math, "data": "synthetic",
-        "value_definition": ("whole-job audio seconds per wall second with the inputs resident in HBM when the timed region "
-                             "starts and the outputs left there (the bench contract); value_host_to_host = the same from "
-                             "pinned host waveforms to pinned host waveforms, H2D / D2H inside the timed region (SURVEY.md 8(d))"),
-        "config": {"workload": ("batched folder restore (BASELINE configs[2]): one batch of %d x %.0f s 44.1 kHz "
-                                "utterances per step, VoiceFixer.restore mode 0, seeded random weights"
-                                % (args.batch, args.seconds)) if args.batch > 1 else
-                               ("VoiceFixer.restore mode 0, single %.0f s 44.1 kHz mono utterance per step (BASELINE configs[1]%s), "
-                                "seeded random weights" % (args.seconds, "" if abs(args.seconds - 10.0) < 1e-9 else " at another length")),
-                   "batch_per_gpu": args.batch, "utterance_seconds": args.seconds, "frames": 1 + n // 441,
-                   "arithmetic": ("fp32 operands, fp32 MFMA accumulation everywhere; k=3 / 3x3 convolutions evaluated as Winograd "
-                                  "F(4,3) (the C=64 stage: one fused launch per layer with both halves F(4,3) for dilations <= 27, two F(4,3) launches for the wider ones): half "
-                                  "of the direct sum's products, rounding ~3x the direct sum's (DESIGN.md 3.0b; engine.set_winograd(False) / --selfcheck run the direct sums)") if args.math == "f32"
-                                 else "opt-in split-bf16 products (three bf16 MFMAs per fp32 product), fp32 accumulation",
-                   "parallelism": "utterance sharding x%d (no data-path collective)" % world},
-        "streams": len(streams),
-        "path_tflops": round(2.0 * path_macs(n) * args.batch * world * args.steps / dt / 1e12, 2),
-        "requested_gpus": requested, "visible_devices": torch.cuda.device_count(),
-        "rccl": {"backend": dist.get_backend() if dist is not None else None, "world_size": world},
-        "per_rank": per_rank,
-        "lib_build_id": build_id,
-        "roofline": roofline,
-        "clocks": dict(clocks, note="shader clock / socket power of rank 0's device while the K timed steps ran (first quarter of the "
-                                    "region dropped: ramp).  The convolution families run at the package power cap, so achieved = "
-                                    "busy share x granted clock and boxes differ by what clock the cap buys them (DESIGN.md 3.0): "
-                                    "compare rounds at equal sclk, or normalise by it"),
-    }
+    line["roofline"] = roofline
+    line["clocks"] = dict(clocks, note="shader clock / socket power of rank 0's device while the K timed steps ran (first quarter of the "
+                                       "region dropped: ramp).  The convolution families run at the package power cap, so achieved = "
+                                       "busy share x granted clock and boxes differ by what clock the cap buys them (DESIGN.md 3.0): "
+                                       "compare rounds at equal sclk, or normalise by it")
     if one_rank is not None:
         line["one_rank_leg"] = one_rank
         line["scaling_efficiency_self_measured"] = round(value / (world * one_rank["value"]), 4)
@@ -1056,9 +1081,6 @@ def main():
                                  "two_streams_over_single": round(dts / dt, 4),
                                  "note": "the same K steps issued on one stream (what `value` was before round 5); the roofline's "
                                          "launch durations are this leg's"}
-    if requested != world:
-        line["note_gpus"] = ("--gpus %d was requested, %d rank(s) ran (visible HIP devices: %d)"
-                             % (requested, world, torch.cuda.device_count()))
 
     if world == 1 and args.math == "f32" and not args.no_bf16x3:
         # auxiliary, NOT the headline: the same workload with the opt-in split-bf16 contraction (three bf16 MFMA

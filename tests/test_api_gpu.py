@@ -969,7 +969,7 @@ def test_bench_oversubscribed_folder_job_two_ranks_on_one_device(tmp_path):
 
 
 def test_bench_oversubscribed_weak_scaling_line_carries_the_one_rank_leg():
-    """``bench.py --gpus 2 --oversubscribe`` (no folder): the weak-scaling line the driver runs at N > 1, rehearsed with two launcher ranks on
+    """``bench.py --gpus 2 --oversubscribe --full`` (no folder): the N > 1 weak-scaling line with its one-rank leg, rehearsed with two launcher ranks on
     this box's one GPU (gloo for the collectives): rank 0 first runs the K steps alone (``one_rank_leg``), the line carries the self-measured
     efficiency beside ``value`` and counts distinct devices."""
     import json
@@ -979,7 +979,7 @@ def test_bench_oversubscribed_weak_scaling_line_carries_the_one_rank_leg():
         pytest.skip("the rehearsal is for one-GPU boxes (test_bench_two_devices_... covers the real thing)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--oversubscribe", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--no-bf16x3"], cwd=root, capture_output=True, text=True, timeout=900, env=dict(os.environ, PYTHONPATH=root))
+                        "--warmup", "1", "--no-bf16x3", "--full"], cwd=root, capture_output=True, text=True, timeout=900, env=dict(os.environ, PYTHONPATH=root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -989,10 +989,40 @@ def test_bench_oversubscribed_weak_scaling_line_carries_the_one_rank_leg():
     assert j["value"] > 10 and "roofline" in j and "clocks" in j
 
 
+def test_bench_plain_run_reports_the_headline_and_full_adds_the_rest():
+    """A plain ``bench.py`` run times the steps and prints the headline only; ``--full`` adds the legs and figures that take runs or
+    bookkeeping of their own (roofline, clocks, single-stream leg, bf16x3, host to host, CPU baseline) to a line with the same
+    headline fields."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--seconds", "1", "--steps", "2",
+                            "--warmup", "1", "--cpu-reps", "1", *extra], cwd=root, capture_output=True, text=True, timeout=900,
+                           env=dict(os.environ, PYTHONPATH=root))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    plain, full = line(), line("--full")
+    same = ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "streams", "n_gpus", "config", "lib_build_id")
+    assert {k: plain[k] for k in same} == {k: full[k] for k in same}
+    assert plain["full"] is False and full["full"] is True
+    for j in (plain, full):
+        assert j["value"] > 1 and j["ms_per_step"] > 0 and j["dtype"] == "f32" and j["higher_is_better"] is True
+        assert abs(j["value"] - 2 * 1.0 / (j["ms_per_step"] * 1e-3)) < 0.01 * j["value"]
+    extras = ("roofline", "clocks", "single_stream", "bf16x3_optin", "host_to_host", "value_host_to_host", "cpu_baseline")
+    assert not [k for k in extras if k in plain] and not [k for k in extras if k not in full]
+    assert full["roofline"]["achieved"] > 0 and full["cpu_baseline"]["rms_vs_gpu"] < 1e-3
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two HIP devices (the first real N > 1 run: lights up on a multi-GPU lease)")
 def test_bench_two_devices_on_rccl_folder_and_weak_scaling_lines():
     """On a node with >= 2 GPUs: ``bench.py --gpus 2 --synth-folder 32`` (BASELINE configs[3] disk to disk, RCCL for the counters) and
-    ``bench.py --gpus 2`` (the weak-scaling line the driver runs) -- one rank per device, backend nccl, every file written once,
+    ``bench.py --gpus 2 --full`` (the weak-scaling line with its one-rank leg) -- one rank per device, backend nccl, every file written once,
     and the second line carries the one-rank leg + the self-measured efficiency."""
     import json
     import subprocess
@@ -1011,7 +1041,7 @@ def test_bench_two_devices_on_rccl_folder_and_weak_scaling_lines():
     assert j["n_gpus"] == 2 and j["ranks"] == 2 and j["rccl"] == {"backend": "nccl", "world_size": 2}
     assert sorted(pr["device"] for pr in j["per_rank"]) == ["cuda:0", "cuda:1"] and [pr["files"] for pr in j["per_rank"]] == [32, 32]
     assert all(pr["cpu"]["pinned"] for pr in j["per_rank"]) or os.cpu_count() < 4
-    j = line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-bf16x3"])
+    j = line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-bf16x3", "--full"])
     assert j["n_gpus"] == 2 and j["rccl"]["backend"] == "nccl" and sorted(pr["device"] for pr in j["per_rank"]) == ["cuda:0", "cuda:1"]
     assert j["one_rank_leg"]["value"] > 0 and 0.5 < j["scaling_efficiency_self_measured"] < 1.2
 

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 # its launch durations from a single-stream leg for the same reason, and the two must agree
 BENCH="python $PWD/bench.py --batch 32 --streams 1 --no-cpu-baseline --no-bf16x3 --no-host-leg $*"
 cd /tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o r -- $BENCH --steps 3 --warmup 1 > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o r -- $BENCH --full --steps 3 --warmup 1 > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 rocprofv3 --output-format csv --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc -o fetch -- $BENCH --steps 1 --warmup 1 > /dev/null 2> $OUT/fetch.log
 rocprofv3 --output-format csv --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc -o write -- $BENCH --steps 1 --warmup 1 > /dev/null 2> $OUT/write.log
 rocprofv3 --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace -d $OUT/pmc -o m -- $BENCH --steps 1 --warmup 1 > /dev/null 2> $OUT/m.log
