@@ -364,6 +364,35 @@ int vfx_post_rows_f32(const float* y, int64_t y_bstride, int Ly, const int32_t* 
                       int64_t out_bstride, const int32_t* n_rows, int n_max, int B, uint32_t* peak_ws,
                       vfx_stream_t stream);
 
+/* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
+
+/* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into
+ * the affine of torch's train-mode batch_norm: scale[b*G+g] = gamma[g]/sqrt(var+eps), shift[b*G+g] = beta[g] - mean*scale.
+ *   pitch_log2 in 1..7 (map form, G = C): channel c of a (B,C,L = H*P) pitch map, over the rows below x->rows[b] (an
+ *                       element count, a multiple of P; NULL: all of L) and the first P-1 columns -- the spare column
+ *                       P-1 never counts;
+ *   pitch_log2 == 0    (1-D form, G = 1): all C channels of a (B,C,L) activation together, over positions < x->rows[b].
+ * Guard slack and positions past a row's extent are never summed.  Two launches: per-chunk (count, mean, M2) partials
+ * into ws (vfx_bn_stats_workspace_bytes(B,C,L,pitch_log2) bytes, 8-byte aligned), then a finalize that folds them in a
+ * fixed order in fp64 -- bit-reproducible.  x needs lstride 1, a 16-byte aligned ptr, cstride/bstride % 4 == 0. */
+size_t vfx_bn_stats_workspace_bytes(int B, int C, int L, int pitch_log2);
+int vfx_bn_stats_f32(const vfx_tensor* x, int B, int C, int L, int pitch_log2, const float* gamma, const float* beta,
+                     float eps, float* scale, float* shift, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
+/* y = act(x*scale[b*G+g] + shift[b*G+g]) over the positions below x->rows[b] (NULL: L) of every channel c, with g = c
+ * (groups == C) or g = 0 (groups == 1); act VFX_POST_NONE or VFX_POST_LRELU(slope) (slope 0: ReLU).  Map form
+ * (pitch_log2 > 0): column P-1 is written 0 (the structural zero of the 3x3 convolutions).  In place (y == x) or not;
+ * y's positions past a row's extent are unspecified afterwards. */
+int vfx_bn_apply_f32(const vfx_tensor* x, const vfx_tensor* y, int B, int C, int L, int pitch_log2, int groups,
+                     const float* scale, const float* shift, int act, float slope, vfx_stream_t stream);
+
+/* Seeded nn.Dropout(0.5), in place on a (B,C,T) channel-major activation (C % 4 == 0), positions below x->rows[b]
+ * (NULL: T).  rowkey: device uint32[3*B] = (segment index, key lo, key hi) per row.  Element (t, c) of row b uses word
+ * i % 4 of Philox4x32-10(counter = (i / 4, segment, layer, 0), key), i = t*C + c: dropped (0) if the word is < 2^31,
+ * else kept x2.  relu != 0 applies max(.,0) afterwards.  Specification: voicefixer_amd/dropout.py. */
+int vfx_dropout_f32(const vfx_tensor* x, int B, int C, int T, const uint32_t* rowkey, int layer, int relu,
+                    vfx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,9 @@ Differences, all deliberate:
     ``VoiceFixer.restore_folder``: length-sorted ragged batches, decode || restore || encode pipelined;
   * ``--disable-cuda`` cannot move compute to the CPU (there is no CPU implementation in this package): it is accepted and
     only selects host tensors at the API boundary, exactly like ``cuda=False`` everywhere else in voicefixer_amd;
-  * mode 2 (train-mode BatchNorm + Dropout) is not built: ``--mode 2`` raises NotImplementedError, ``--mode all`` writes
-    modes 0 and 1 and says that mode 2 was skipped;
+  * mode 2 (train-mode BatchNorm + Dropout) needs ``--seed N`` (extension): its dropout masks are then a function of the
+    seed (voicefixer_amd/dropout.py), so a run can be repeated.  Without ``--seed``, ``--mode 2`` raises NotImplementedError
+    and ``--mode all`` writes modes 0 and 1 and says that mode 2 was skipped; with it, ``--mode all`` writes all three;
   * ``--weight_prepare`` cannot download (no network): it only reports whether both checkpoints are in place;
   * ``--gpus N`` (extension, folder mode): the folder is sharded over N MI355X, one process per GPU -- the command
     re-executes itself under ``torch.distributed.run`` on 127.0.0.1 (N clamped, loudly, to the visible devices), every
@@ -29,7 +30,7 @@ import re
 import sys
 import time
 
-MODES_BUILT = (0, 1)
+MODES_BUILT = (0, 1)          # without --seed; with it, mode 2 as well
 
 
 def check_output_format(outfile):
@@ -67,12 +68,12 @@ def mode_outfile(outfile, mode, append_mode):
     return os.path.join(os.path.dirname(outfile), "{}-mode{}{}".format(base, mode, ext))
 
 
-def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False):
+def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
     start = time.time()
-    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode))
+    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 
@@ -86,7 +87,10 @@ def build_parser():
                         help="Output folder. The processed files will be stored in this folder.")
     parser.add_argument("--mode", choices=["0", "1", "2", "all"], default="0",
                         help="0: Original Model (default), 1: Add preprocessing module (remove higher frequencies), "
-                             "2: Train mode (not built in this package), all: one output per built mode (0 and 1).")
+                             "2: Train mode (needs --seed), all: one output per mode (0 and 1; 2 as well with --seed).")
+    parser.add_argument("--seed", type=_seed, default=None,
+                        help="(extension) seed of mode 2's dropout masks, an int in [0, 2**64): makes mode 2 reproducible "
+                             "and available (every rank of a --gpus N job uses it)")
     parser.add_argument("--disable-cuda", default=False, action="store_true",
                         help="Accepted for compatibility: compute always runs on the MI355X, results are handed over on the host.")
     parser.add_argument("--silent", default=False, action="store_true",
@@ -104,6 +108,13 @@ def build_parser():
     parser.add_argument("--io-threads", type=int, default=0,
                         help="(extension) folder mode: decode / encode workers per rank (default: host cores / (2 * ranks), 2..8)")
     return parser
+
+
+def _seed(text):
+    v = int(text, 0)
+    if not 0 <= v < 2 ** 64:
+        raise argparse.ArgumentTypeError("seed must be in [0, 2**64)")
+    return v
 
 
 def folder_ranks(args, argv):
@@ -164,9 +175,9 @@ def main(argv=None):
         if audioext.lower() not in (".wav", ".flac"):   # (the reference accepts .wav only; FLAC is what its own test reads)
             raise ValueError("Error: Error processing the input file. We only support the .wav format currently. "
                              "Please convert your %s format to .wav. Thanks." % audioext)
-    if args.mode == "2":
+    if args.mode == "2" and args.seed is None:
         raise NotImplementedError("mode 2 (train-mode BatchNorm + Dropout, voicefixer/base.py:114-115) is nondeterministic "
-                                  "and not built in voicefixer_amd; modes 0 and 1 are")
+                                  "and not built in voicefixer_amd without --seed N; modes 0 and 1 are")
     import torch
     from . import api
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -192,13 +203,17 @@ def main(argv=None):
     voicefixer = api.VoiceFixer()
     if not args.silent:
         print("Start processing the input file %s." % args.infile)
-    modes = list(MODES_BUILT) if args.mode == "all" else [int(args.mode)]
+    built = MODES_BUILT + ((2,) if args.seed is not None else ())
+    modes = list(built) if args.mode == "all" else [int(args.mode)]
     append = args.mode == "all"
     if append and not args.silent:
-        print("--mode all: writing modes 0 and 1 (mode 2 is not built in this package)")
+        if args.seed is None:
+            print("--mode all: writing modes 0 and 1 (mode 2 is not built in this package without --seed)")
+        else:
+            print("--mode all: writing modes 0, 1 and 2 (seed %d)" % args.seed)
     if process_file:
         for m in modes:
-            writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent)
+            writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -211,7 +226,8 @@ def main(argv=None):
             try:
                 voicefixer.restore_folder(args.infolder, args.outfolder, mode=m, batch_size=args.batch_size,
                                           name_suffix="-mode%d" % m if append else "", stats=st,
-                                          skip_existing=args.skip_existing, io_threads=args.io_threads or None)
+                                          skip_existing=args.skip_existing, io_threads=args.io_threads or None,
+                                          seed=args.seed)
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

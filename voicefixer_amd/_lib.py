@@ -81,6 +81,10 @@ SIGNATURES = {
     "vfx_gru_layout": (None, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vfx_mel_to_cond_f32": (_I, [_P, _T, _I, _I, _P]),
     "vfx_post_f32": (_I, [_P, C.c_int64, _I, _P, C.c_int64, _I, _I, _P, _P]),
+    "vfx_bn_stats_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "vfx_bn_stats_f32": (_I, [_T, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.c_size_t, _P]),
+    "vfx_bn_apply_f32": (_I, [_T, _T, _I, _I, _I, _I, _I, _P, _P, _I, C.c_float, _P]),
+    "vfx_dropout_f32": (_I, [_T, _I, _I, _I, _P, _I, _I, _P]),
 }
 
 _lib = None

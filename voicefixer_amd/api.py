@@ -14,8 +14,9 @@ in libvfx_hip on the MI355X; there is NO CPU implementation behind this API:
     compute on the CPU; numerically equivalent within the parity tolerance).  Without a visible
     device either setting raises -- nothing silently falls back.
   * ``mode=0`` and ``mode=1`` (``remove_higher_frequency`` pre-filter, base.py:87-104, run on the
-    device by ``vfx_hf_cut_f32``).  ``mode=2`` (train-mode BatchNorm/Dropout, nondeterministic and
-    exempt from the reference's own check, test/test.py:58) raises NotImplementedError.
+    device by ``vfx_hf_cut_f32``).  ``mode=2`` (train-mode BatchNorm/Dropout, base.py:114-115) needs
+    ``seed=``: its dropout masks are then a documented function of the seed (dropout.py), so mode 2 is
+    reproducible; without a seed it raises NotImplementedError, as the unseeded form is not built.
 """
 import os
 
@@ -280,20 +281,28 @@ class VoiceFixer(nn.Module):
         return audio_io.load_wav(path, sample_rate)
 
     @staticmethod
-    def _check_mode(mode):
+    def _check_mode(mode, seed=None):
+        """Modes 0 and 1 always (``seed`` is ignored); mode 2 (train-mode BatchNorm + Dropout) only with a seed."""
         if mode in (0, 1):
             return
         if mode == 2:
-            raise NotImplementedError(
-                "mode=2 (train-mode BatchNorm + Dropout) is nondeterministic in the reference and outside "
-                "the MI355X path; modes 0 and 1 are implemented")
+            if seed is None:
+                raise NotImplementedError(
+                    "mode=2 (train-mode BatchNorm + Dropout) draws unseeded dropout masks in the reference; here it needs "
+                    "seed= (an int in [0, 2**64)), which makes its masks reproducible")
+            from . import dropout
+            dropout.check_seed(seed)
+            return
         raise ValueError("mode must be 0, 1 or 2")
 
     @torch.no_grad()
-    def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None):
+    def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
-        30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138)."""
-        self._check_mode(mode)
+        30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
+        ``mode=2`` with ``seed`` (int in [0, 2**64)): the restorer in train mode -- batch statistics per segment, seeded
+        dropout (dropout.py; segment s of the file draws the masks of (seed, s)); always fp32.  A segment of <= 64 frames
+        (< 28224 samples: a short file, or the short tail of a long one) raises ValueError, as the reference does."""
+        self._check_mode(mode, seed)
         pipe = self._get_pipe()
         wav = np.asarray(wav_10k, dtype=np.float32)
         n = wav.shape[0]
@@ -315,19 +324,22 @@ class VoiceFixer(nn.Module):
             for i in range(0, len(full), self.segment_batch):
                 grp = full[i:i + self.segment_batch]
                 seg = torch.from_numpy(np.stack([wav[a:b] for a, b in grp])).to(pipe.device)
-                out = self._restore_segments(pipe, seg, SEG_LENGTH, mode, your_vocoder_func)
+                out = self._restore_segments(pipe, seg, SEG_LENGTH, mode, your_vocoder_func, seed, range(i, i + len(grp)))
                 res.extend(out[k:k + 1] for k in range(len(grp)))
             for a, b in tail:
                 seg = torch.from_numpy(np.ascontiguousarray(wav[a:b]))[None].to(pipe.device)
-                res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func))
+                res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)]))
             return torch.cat(res, -1).cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
 
     @staticmethod
-    def _restore_segments(pipe, seg, n, mode, your_vocoder_func):
+    def _restore_segments(pipe, seg, n, mode, your_vocoder_func, seed=None, segments=None):
         """One batch of equal-length segments through the path; mode 1 first shortens every segment to
-        512*(n//512) samples by the device-side high-frequency cut (base.py:121-122)."""
+        512*(n//512) samples by the device-side high-frequency cut (base.py:121-122); mode 2 runs the train-mode
+        restorer, row b being segment ``segments[b]`` of its file."""
+        if mode == 2:
+            return pipe.restore_train(seg, [n] * seg.shape[0], list(segments), seed, your_vocoder_func)
         if mode == 1:
             from . import ops
             seg, _ = ops.hf_cut(seg, n, 0.95)
@@ -345,7 +357,7 @@ class VoiceFixer(nn.Module):
             self._stream_pool.append(torch.cuda.Stream(device=pipe.device))
         return self._stream_pool[:max(1, int(streams))]
 
-    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func):
+    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None):
         """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, the launch sequence, D2H of the result into
         a pinned tensor, an event.  Nothing here waits for the device."""
         from . import ops
@@ -384,12 +396,14 @@ class VoiceFixer(nn.Module):
                             done[q] = True
                     lens = new_lens
                     seg = cut
-                full = pipe.restore_rows(seg, lens)
+                # (a ragged batch holds files of at most 30 s: every row is segment 0 of its file)
+                full = pipe.restore_train(seg, lens, [0] * len(lens), seed) if mode == 2 else pipe.restore_rows(seg, lens)
                 lens_out = lens
             else:
                 n = lens[0]
                 parts = [self._restore_segments(pipe, seg[:, s0:s0 + SEG_LENGTH], min(SEG_LENGTH, n - s0), mode,
-                                                your_vocoder_func) for s0 in range(0, n, SEG_LENGTH)]
+                                                your_vocoder_func, seed, [s0 // SEG_LENGTH] * len(lens))
+                         for s0 in range(0, n, SEG_LENGTH)]
                 full = parts[0] if len(parts) == 1 else torch.cat(parts, -1)
                 lens_out = [full.shape[-1]] * len(lens)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
@@ -399,7 +413,7 @@ class VoiceFixer(nn.Module):
         return [item, out_host, lens_out, ev]
 
     @torch.no_grad()
-    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0):
+    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -409,11 +423,12 @@ class VoiceFixer(nn.Module):
         UNet levels -- overlap the convolutions of the next) and the host runs one batch per stream AHEAD of the device:
         H2D, the ~600 launches and the D2H of a batch are queued while earlier batches compute, so the device never waits
         for the host and the caller (restore_folder: decode / encode workers) works on other batches meanwhile.
+        ``mode=2`` needs ``seed`` (restore_inmem): a row's result equals restoring that file alone with the same seed.
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
         from .engine import DeviceFlagRaised
-        self._check_mode(mode)
+        self._check_mode(mode, seed)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -444,7 +459,7 @@ class VoiceFixer(nn.Module):
                     pipe.vocoder.read_f16_flag()
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
-                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func)
+                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
@@ -452,7 +467,7 @@ class VoiceFixer(nn.Module):
                 return rec[0][0], rec[1], rec[2]
 
             for item in batches:
-                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func))
+                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -472,7 +487,7 @@ class VoiceFixer(nn.Module):
                 pipe.vocoder.read_f16_flag()
 
     @torch.no_grad()
-    def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0):
+    def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -484,8 +499,9 @@ class VoiceFixer(nn.Module):
         length, one batched launch sequence per segment index.  The batches run through ``restore_batches`` (round-robin
         on ``streams`` HIP streams, pinned staging in both directions, the host one batch per stream ahead).
         ``mode=1``: every file (every 30 s segment of it) first goes through the device-side high-frequency cut
-        (base.py:121-122, ``vfx_hf_cut_f32``) exactly as ``restore_inmem(mode=1)`` does it."""
-        self._check_mode(mode)
+        (base.py:121-122, ``vfx_hf_cut_f32``) exactly as ``restore_inmem(mode=1)`` does it.  ``mode=2`` needs ``seed``:
+        every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it."""
+        self._check_mode(mode, seed)
         order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
         outs = [None] * len(wavs)
         plan = plan_batches([len(wavs[k]) for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None)
@@ -503,7 +519,7 @@ class VoiceFixer(nn.Module):
                     hv[r, lens[r]:] = 0.0
                 yield idx, kind, host, lens
 
-        for idx, out_host, lens_out in self.restore_batches(staged(), your_vocoder_func, streams, mode):
+        for idx, out_host, lens_out in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed):
             ov = out_host.numpy()
             for r, k in enumerate(idx):
                 outs[k] = ov[r:r + 1, :lens_out[r]].copy()   # (the pinned block goes back to torch's host cache)
@@ -520,7 +536,8 @@ class VoiceFixer(nn.Module):
         ``mode=1``: the high-frequency cut (base.py:121-122) runs per chunk; it returns 512 * (len // 512) samples
         aligned at the chunk's start, so the chunk length is rounded down to a multiple of 512 (every full chunk keeps
         its length) and only the last chunk loses its sub-512 tail -- the output is that much shorter, as the
-        reference's mode-1 output is.  Returns float32 numpy (1, N')."""
+        reference's mode-1 output is.  Modes 0 and 1 only: ``mode=2`` raises NotImplementedError (its per-segment
+        statistics have no overlap-add form).  Returns float32 numpy (1, N')."""
         self._check_mode(mode)
         pipe = self._get_pipe()
         wav = np.asarray(wav, dtype=np.float32)
@@ -557,15 +574,18 @@ class VoiceFixer(nn.Module):
             i += len(grp)
         return out[:, :n_out]
 
-    MIN_SAMPLES = {0: 1025, 1: 1536}   # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512))
+    # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
+    # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
+    MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
-    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode):
+    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
         the stream of batches continues; the job loses the failing file, nothing else (the reference's serial loop,
         voicefixer/__main__.py:187-212, keeps every file it finished before a bad one)."""
         from collections import deque
+        kw = {"seed": seed} if mode == 2 else {}
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -584,7 +604,7 @@ class VoiceFixer(nn.Module):
 
         while True:
             try:
-                for tag, out_host, lens_out in self.restore_batches(feed(), your_vocoder_func, streams, mode):
+                for tag, out_host, lens_out in self.restore_batches(feed(), your_vocoder_func, streams, mode, **kw):
                     pending.popleft()
                     yield tag, out_host, lens_out
                 if src_exc:
@@ -604,7 +624,7 @@ class VoiceFixer(nn.Module):
                     for r in range(len(tag)):
                         one = (tag[r:r + 1], kind, host[r:r + 1, :max(int(lens[r]), 1)], [lens[r]])
                         try:
-                            for t1, o1, l1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode):
+                            for t1, o1, l1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
                                 yield t1, o1, l1
                         except (KeyboardInterrupt, GeneratorExit):
                             raise
@@ -613,7 +633,7 @@ class VoiceFixer(nn.Module):
 
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
-                       skip_existing=False):
+                       skip_existing=False, seed=None):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -636,7 +656,7 @@ class VoiceFixer(nn.Module):
         to a temporary name and renamed, so a file in ``outfolder`` is always complete; ``skip_existing`` leaves files
         whose output already exists alone (resume after an interrupted job; listed in ``stats["skipped"]``).
 
-        ``mode`` 0 or 1 (restore_batch); ``name_suffix`` goes between base name and extension (the CLI's ``-mode<k>``
+        ``mode`` 0, 1 or 2 (2 with ``seed``, restore_batch); ``name_suffix`` goes between base name and extension (the CLI's ``-mode<k>``
         naming for ``--mode all``).  ``extensions``: which files of the folder are taken -- the reference's loop takes
         ``.wav`` only (the default, and what the CLI passes); ``(".wav", ".flac")`` adds FLAC inputs, written back as
         FLAC (the workers decode / resample / encode in libvfx_audio.so, several thousand x real time).
@@ -649,7 +669,7 @@ class VoiceFixer(nn.Module):
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as vdist, flac
-        self._check_mode(mode)
+        self._check_mode(mode, seed)
         rank, world = vdist.rank_world(rank, world)
         if io_threads is None:
             io_threads = vdist.default_io_threads(world)
@@ -802,7 +822,8 @@ class VoiceFixer(nn.Module):
 
             source_error = None
             try:
-                for idx, out_host, lens_out in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func, streams, mode):
+                for idx, out_host, lens_out in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func, streams, mode,
+                                                                               **({"seed": seed} if mode == 2 else {})):
                     ov = out_host.numpy()
                     writes.append([(i, pool.submit(encode_from, ov[r:r + 1, :lens_out[r]], i)) for r, i in enumerate(idx)])
                     drain(ahead + 2)       # bounded backlog: pinned results do not pile up behind a slow disk
@@ -829,7 +850,7 @@ class VoiceFixer(nn.Module):
     def _pin_memory():
         return torch.cuda.is_available()
 
-    def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None):
+    def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None):
         wav_10k = self._load_wav(input, sample_rate=44100)
-        out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func)
+        out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed)
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=44100)

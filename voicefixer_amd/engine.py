@@ -19,6 +19,8 @@ Data layouts in HBM (all float32):
 import contextlib
 import math
 
+import numpy as np
+
 import torch
 
 from . import ops, packing, weights
@@ -60,6 +62,13 @@ def _rows(B, Cn, L, guard, dev, rows=None):
     if rows is not None:
         ops.with_rows(v, rows)
     return v
+
+
+def _head(v, n):
+    """The first ``n`` channels of a guarded (B, C, L) view, keeping its guard and row tags."""
+    h = v[:, :n]
+    h._vfx_guard = getattr(v, "_vfx_guard", 0)
+    return ops.with_rows(h, getattr(v, "_vfx_rows", None))
 
 
 class RaggedRows:
@@ -390,6 +399,8 @@ class _ConvBlock:
         self.w2g4 = _dev(packing.pack_wino4_2d(wp2), device) if wino4 and self.cout % cin_step4 == 0 else None
         self.act1 = ops.Act(pre=PRE_AFFINE_LRELU, pre_slope=0.01, scale=_dev(s1, device), shift=_dev(sh1, device),
                             post=POST_LRELU, post_slope=0.01)
+        self._raw = (sd, p, pad_cin)   # unfolded weights for the train-mode forward (packed on first use: train_w)
+        self._train = None
         self.shortcut = None
         if (p + ".shortcut.weight") in sd:
             self.shortcut = (_dev(packing.pack_conv2d(sd[p + ".shortcut.weight"]), device),
@@ -408,6 +419,45 @@ class _ConvBlock:
             self._x3_planes = (pk(self.w1), pk(self.w2), pk(self.shortcut[0]) if self.shortcut is not None else None)
         self.x3 = self._x3_planes
 
+    def train_w(self):
+        """Unfolded weights of the train-mode forward, packed once on first use: raw conv1 (no bn2 fold, no bias) with its
+        direct and Winograd layouts, and gamma / beta of bn1 (padded with 1 / 0 over the zero filler input channels) and bn2."""
+        if self._train is None:
+            sd, p, pad_cin = self._raw
+            dev = self.w2.device
+            wp1 = packing.pack_conv2d(sd[p + ".conv1.weight"].float())
+            w1, w1d = _wpair(wp1, dev)
+            g1, b1 = sd[p + ".bn1.weight"].float(), sd[p + ".bn1.bias"].float()
+            if pad_cin is not None and pad_cin > g1.numel():
+                extra = pad_cin - g1.numel()
+                g1, b1 = torch.cat([g1, torch.ones(extra)]), torch.cat([b1, torch.zeros(extra)])
+            self._train = (w1, w1d, _dev(packing.pack_wino4_2d(wp1), dev) if self.w1g4 is not None else None,
+                           _dev(g1, dev), _dev(b1, dev), _dev(sd[p + ".bn2.weight"], dev), _dev(sd[p + ".bn2.bias"], dev))
+        return self._train
+
+    def run_train(self, x, z, y1, out, H, lp):
+        """ConvBlockRes with batch statistics (restorer/modules.py:68-76 in .train()): z = lrelu(bn1(x)) into scratch z
+        (B,>=Cin,HP) -- x stays raw for the residual / shortcut --, y1 = conv1(z), y1 = lrelu(bn2(y1)) in place, out =
+        conv2(y1) + residual.  Every launch fp32; statistics per batch row over its own map extent (x._vfx_rows)."""
+        w1, w1d, w1g4, g1, b1, g2, b2 = self.train_w()
+        B, HP, dev = x.shape[0], H << lp, x.device
+        sc = torch.empty((B * self.cin,), device=dev)
+        sh = torch.empty((B * self.cin,), device=dev)
+        ops.bn_stats(x, HP, lp, g1, b1, sc, sh)
+        zv = _head(z, self.cin)
+        ops.bn_apply(x, zv, HP, lp, sc, sh, slope=0.01)
+        if self.shortcut is not None:
+            ops.conv2d(x, self.shortcut[0], self.shortcut[1], out, H, lp, 1, None, cin=self.cin)
+            res = out
+        else:
+            res = x
+        ops.conv2d(zv, w1, None, y1, H, lp, 3, None, cin=self.cin, wd=w1d, wg4=_wg(w1g4))
+        sc2 = torch.empty((B * self.cout,), device=dev)
+        sh2 = torch.empty((B * self.cout,), device=dev)
+        ops.bn_stats(y1, HP, lp, g2, b2, sc2, sh2)
+        ops.bn_apply(y1, y1, HP, lp, sc2, sh2, slope=0.01)
+        ops.conv2d(y1, self.w2, None, out, H, lp, 3, None, res=res, wd=self.w2d, wg4=_wg(self.w2g4))
+
     def run(self, x, y1, out, H, lp):
         """x (B,Cin,HP) -> out (B,Cout,HP); y1 scratch (B,Cout,HP).  ``out`` may alias ``x`` when there
         is no shortcut (the residual is read and written at the same position by the same thread)."""
@@ -420,6 +470,19 @@ class _ConvBlock:
         ops.conv2d(y1, self.w2, None, out, H, lp, 3, None, res=res, w3=self.x3[1], wd=self.w2d, wg4=_wg(self.w2g4))
 
 
+TRAIN_MIN_FRAMES = 65
+
+
+def check_train_frames(frames, center_channels):
+    """Train-mode BatchNorm needs more than one value per channel; a segment of T <= 64 frames leaves the UNet's centre
+    block one (1 x 1 map), where torch raises (torch/nn/functional.py _verify_batch_size) -- checked on the host before
+    anything launches, with torch's message for the reference's batch of 1."""
+    for t in frames:
+        if t < TRAIN_MIN_FRAMES:
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             "torch.Size([1, %d, 1, 1])" % center_channels)
+
+
 class RestorerEngine:
     """mel (B,T,128) -> (logmel, denoised mel), both (B,T,128)."""
 
@@ -427,6 +490,8 @@ class RestorerEngine:
         sd = {k: v for k, v in state.items()}
         weights.check_state(sd, weights.restorer_manifest(), "restorer")
         self.device = device
+        self._sd = sd                 # raw tensors of the train-mode forward (train_w packs them on first mode-2 use)
+        self._train = None
         f = lambda k: sd[k].float()
 
         def bn_scalar(p):
@@ -555,6 +620,145 @@ class RestorerEngine:
         for grp in list(self.enc) + [[self.center]] + [d[2] for d in self.dec] + [[self.after]]:
             for blk in grp:
                 blk.set_math(math)
+
+    # -- train mode (the reference's mode 2) --------------------------------------------
+    def train_w(self):
+        """Unfolded denoiser weights of the train-mode forward, packed on first use: raw Linear 1 / 4 / 11 and the raw
+        layer-0 W_ih of both BN_GRUs, and gamma / beta of the six BatchNorm2d(1) (denoiser.0, .3, .7.bn, .8.bn, .9, .13)."""
+        if self._train is None:
+            sd, dev = self._sd, self.device
+            f = lambda k: sd[k].float()
+            lin = lambda i: (_dev(packing.pack_linear(f("denoiser.%d.weight" % i)), dev), _dev(f("denoiser.%d.bias" % i), dev))
+            bn = {k: (_dev(f("denoiser.%s.weight" % k), dev), _dev(f("denoiser.%s.bias" % k), dev))
+                  for k in ("0", "3", "7.bn", "8.bn", "9", "13")}
+            wih0 = []
+            for idx in (7, 8):
+                p = "denoiser.%d.gru." % idx
+                wih0.append((_dev(packing.pack_linear(torch.cat([f(p + "weight_ih_l0"), f(p + "weight_ih_l0_reverse")], 0)), dev),
+                             _dev(torch.cat([f(p + "bias_ih_l0"), f(p + "bias_ih_l0_reverse")], 0), dev)))
+            dec = [(_dev(f("unet.decoder_block%d.bn1.weight" % b), dev), _dev(f("unet.decoder_block%d.bn1.bias" % b), dev))
+                   for b in range(1, 7)]
+            self._train = {"l1": lin(1), "l2": lin(4), "l3": lin(11), "bn": bn, "wih0": wih0, "dec": dec}
+        return self._train
+
+    def _bn1d(self, x, T, key, slope=None):
+        """BatchNorm2d(1) with batch statistics over each row's T_b frames x all features, in place on x (B,C,T)."""
+        g, b = self.train_w()["bn"][key]
+        B = x.shape[0]
+        sc = torch.empty((B,), device=x.device)
+        sh = torch.empty((B,), device=x.device)
+        ops.bn_stats(x, T, 0, g, b, sc, sh)
+        ops.bn_apply(x, x, T, 0, sc, sh, slope=slope)
+
+    def denoiser_train(self, mel, T, rowkey, t_rows=None):
+        """restorer/model.py:69-99 in .train(), literally: every BatchNorm2d(1) normalises with the row's own statistics,
+        the two Dropout(0.5) draw the seeded masks of dropout.py (``rowkey``: device int32 (B,3) = segment, key lo, key hi).
+        mel (B,T,128) -> mask channel-major (B,128,Tp4)."""
+        tw = self.train_w()
+        B, dev = mel.shape[0], mel.device
+        rw = lambda v: ops.with_rows(v, t_rows)
+        x0 = rw(_rows(B, 128, T, G_TILE, dev))
+        ops.tm_to_cm(mel, x0, T, 128)
+        self._bn1d(x0, T, "0")
+        x1 = rw(_rows(B, 256, T, G_TILE, dev))
+        ops.conv1d(x0, tw["l1"][0], tw["l1"][1], x1, T, 1, act=self.act_relu)
+        self._bn1d(x1, T, "3")
+        x = rw(_rows(B, 512, T, G_TILE, dev))
+        ops.conv1d(x1, tw["l2"][0], tw["l2"][1], x, T, 1)
+        ops.dropout(x, T, rowkey, 0, relu=True)                     # denoiser.5 + ReLU (the x2 mask and ReLU commute)
+        gi = torch.empty((B, T, 1536), device=dev)
+        for gru, key, (wih0, bih0) in zip(self.grus, ("7.bn", "8.bn"), tw["wih0"]):
+            self._bn1d(x, T, key)
+            for layer, (wih, bih, whh_packed, bhh, whh_t) in enumerate(gru):
+                if layer == 0:
+                    wih, bih = wih0, bih0
+                ops.conv1d(x, wih, bih, gi.transpose(1, 2), T, 1)
+                y = rw(_rows(B, 512, T, G_TILE, dev))
+                ops.gru_bidir(gi, whh_packed, bhh, y, T)
+                x = y
+        self._bn1d(x, T, "9", slope=0.0)                             # denoiser.9 + ReLU
+        x3 = rw(_rows(B, 512, T, G_TILE, dev))
+        ops.conv1d(x, tw["l3"][0], tw["l3"][1], x3, T, 1)
+        ops.dropout(x3, T, rowkey, 1)                                # denoiser.12
+        self._bn1d(x3, T, "13", slope=0.0)                           # denoiser.13 + ReLU
+        mask = torch.empty((B, 128, _up4(T)), device=dev)
+        ops.conv1d(x3, self.l4[0], self.l4[1], mask, T, 1, act=self.act_sigmoid)
+        return rw(mask)
+
+    def unet_train(self, u, Tp, ragged=None):
+        """``unet`` with every BatchNorm on batch statistics: ConvBlockRes.run_train, and the decoders' bn1 + ReLU into
+        scratch ahead of an unfused transposed convolution.  Same buffers and row tags as ``unet``."""
+        tw = self.train_w()
+        B, dev = u.shape[0], u.device
+        lv = (lambda lp: ragged.unet[7 - lp]) if ragged is not None else (lambda lp: None)
+        x = u
+        cats = []
+        H, lp = Tp, 7
+        for blocks in self.enc:
+            cout = blocks[0].cout
+            HP = H << lp
+            G = (1 << lp) + 1 + G_TILE
+            cat = _rows(B, 2 * cout, HP, G, dev, lv(lp))
+            skip = cat[:, cout:]
+            a = _rows(B, cout, HP, G, dev, lv(lp))
+            y1 = _rows(B, cout, HP, G, dev, lv(lp))
+            z = _rows(B, max(cout, blocks[0].cin), HP, G, dev, lv(lp))
+            blocks[0].run_train(x, z, y1, a, H, lp)
+            blocks[1].run_train(a, z, y1, a, H, lp)
+            blocks[2].run_train(a, z, y1, a, H, lp)
+            blocks[3].run_train(a, z, y1, skip, H, lp)
+            cats.append((cat, H, lp))
+            pooled = _rows(B, cout, (H // 2) << (lp - 1), (1 << (lp - 1)) + 1 + G_TILE, dev, lv(lp - 1))
+            ops.avgpool2x2(skip, pooled, H, lp)
+            x = pooled
+            H //= 2
+            lp -= 1
+        G = (1 << lp) + 1 + G_TILE
+        y1 = _rows(B, x.shape[1], H << lp, G, dev, lv(lp))
+        z = _rows(B, x.shape[1], H << lp, G, dev, lv(lp))
+        self.center.run_train(x, z, y1, x, H, lp)
+        for (wt, _, blocks), (g, b) in zip(self.dec, tw["dec"]):
+            cat, Hs, lps = cats.pop()
+            cout = blocks[0].cout
+            sc = torch.empty((B * x.shape[1],), device=dev)
+            sh = torch.empty((B * x.shape[1],), device=dev)
+            ops.bn_stats(x, H << lp, lp, g, b, sc, sh)
+            xa = _rows(B, x.shape[1], H << lp, (1 << lp) + 1 + G_TILE, dev, lv(lp))
+            ops.bn_apply(x, xa, H << lp, lp, sc, sh, slope=0.0)     # relu(bn1(x)) (modules.py:150)
+            ops.convtr2d_3x3s2(xa, wt, cat[:, :cout], H, lp, None)
+            H, lp = Hs, lps
+            HP = H << lp
+            G = (1 << lp) + 1 + G_TILE
+            a = _rows(B, cout, HP, G, dev, lv(lp))
+            y1 = _rows(B, cout, HP, G, dev, lv(lp))
+            z = _rows(B, 2 * cout, HP, G, dev, lv(lp))
+            blocks[0].run_train(cat, z, y1, a, H, lp)
+            for blk in blocks[1:]:
+                blk.run_train(a, z, y1, a, H, lp)
+            x = a
+        self.after.run_train(x, z, y1, x, H, lp)
+        out = torch.empty((B, 1, H << lp), device=dev)
+        ops.conv1d_cout1(x, self.after2[0], self.after2[1], out, H << lp, 1, PAD_ZERO, POST_NONE, lp)
+        return out
+
+    def forward_train(self, mel, T, rowkey, debug=None, ragged=None):
+        """``forward`` in train mode (mode 2): same arguments plus ``rowkey`` (device int32 (B,3): segment, key lo, key hi
+        of every row).  Always fp32, whatever set_math says.  Nothing of the engine's state changes (no running statistics)."""
+        if ragged is None:          # (ragged batches: Pipeline.restore_train checks every row's frames on the host)
+            check_train_frames([T], self.center.cin)
+        B, dev = mel.shape[0], mel.device
+        Tp = (T + 63) // 64 * 64
+        mask = self.denoiser_train(mel, T, rowkey, None if ragged is None else ragged.T)
+        u = _rows(B, 8, Tp * 128, 128 + 1 + G_TILE, dev, None if ragged is None else ragged.unet[0])
+        ops.unet_input(mel, mask, u, T, Tp)
+        uo = self.unet_train(u, Tp, ragged)
+        logmel = torch.empty((B, T, 128), device=dev)
+        den = torch.empty((B, T, 128), device=dev)
+        ops.unet_output(uo, u, mel, mask, logmel, den, T, Tp)
+        if debug is not None:
+            debug["mask"] = mask[:, :, :T]
+            debug["unet_out"] = uo[:, 0, :Tp * 128].reshape(B, Tp, 128)[:, :T]
+        return logmel, den
 
     # -- ResUNet ---------------------------------------------------------------------
     def unet(self, u, Tp, ragged=None):
@@ -841,6 +1045,62 @@ class Pipeline:
         ws = torch.empty((B,), dtype=torch.int32, device=wav.device)
         ops.post_rows(y[:, 0], Ly, out, rg.n, rg.n_max, ws, ly_rows=rg.voc[441])
         return out
+
+    @contextlib.contextmanager
+    def _fp32_vocoder(self):
+        """Mode 2 runs in fp32 whatever set_math says: the vocoder's arithmetic is switched for the block (the restorer's
+        train-mode launches never take the bf16x3 planes)."""
+        math = self.vocoder.math
+        self.vocoder.math = "f32"
+        try:
+            yield
+        finally:
+            self.vocoder.math = math
+
+    def restore_train(self, wav, lengths, segments, seed, vocoder_func=None):
+        """Mode 2 (the reference's restorer in .train(), voicefixer/base.py:114-115) for a batch of segments: wav device
+        float32 (B, >= max(lengths)); row b is segment ``segments[b]`` (its index within its file) of ``lengths[b]``
+        samples.  Every BatchNorm normalises with the row's own statistics, the two dropout layers draw the masks of
+        dropout.py for (seed, segment) -- so row b equals that segment restored alone.  Always fp32 and eager (never a
+        captured graph); no running statistic is updated.  Returns device (B, max(lengths)) (equal lengths: (B, N))."""
+        from . import dropout
+        B = wav.shape[0]
+        if len(lengths) != B or len(segments) != B:
+            raise VfxError("restore_train: %d lengths / %d segment indices for %d rows" % (len(lengths), len(segments), B))
+        if min(lengths) < 1025:
+            raise VfxError("segment of %d samples is too short for the reflect-padded STFT (needs > 1024)" % min(lengths))
+        check_train_frames([1 + n // 441 for n in lengths], self.restorer.center.cin)
+        k0, k1 = dropout.key_of(seed)
+        rk = np.array([[int(sg), k0, k1] for sg in segments], dtype=np.uint32).view(np.int32)   # (B,3), uint32 bits
+        rowkey = torch.from_numpy(rk).to(wav.device)
+        with self._fp32_vocoder():
+            if min(lengths) == max(lengths):
+                N = lengths[0]
+                mel, T = self.wav_to_mel(wav, N)
+                _, den = self.restorer.forward_train(mel, T, rowkey)
+                if vocoder_func is None:
+                    y, Ly = self.vocoder.forward(den, T)
+                    y = y[:, 0]
+                else:
+                    y = vocoder_func(den[:, None]).to(wav.device).float().contiguous()[:, 0]
+                    Ly = y.shape[-1]
+                n_out = min(N, Ly)
+                out = torch.empty((B, n_out), device=wav.device)
+                ws = torch.empty((B,), dtype=torch.int32, device=wav.device)
+                ops.post(y, Ly, out, n_out, ws)
+                return out
+            if vocoder_func is not None:
+                raise VfxError("restore_train: a plugin vocoder takes rows of one length")
+            rg = RaggedRows(lengths, wav.device)
+            T = rg.T_max
+            mel = torch.empty((B, T, 128), device=wav.device)
+            ops.stft_mel_rows(wav, mel, rg.n, T)
+            _, den = self.restorer.forward_train(mel, T, rowkey, ragged=rg)
+            y, Ly = self.vocoder.forward(den, T, ragged=rg)
+            out = torch.zeros((B, rg.n_max), device=wav.device)
+            ws = torch.empty((B,), dtype=torch.int32, device=wav.device)
+            ops.post_rows(y[:, 0], Ly, out, rg.n, rg.n_max, ws, ly_rows=rg.voc[441])
+            return out
 
     def _restore_eager(self, wav, N, vocoder_func=None):
         if N < 1025:

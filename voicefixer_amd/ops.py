@@ -426,3 +426,42 @@ def post(y, Ly, out, N, peak_ws):
     _need_cuda(y, out, peak_ws)
     check(_lib.lib().vfx_post_f32(_ptr(y), y.stride(0), Ly, _ptr(out), out.stride(0), N, y.shape[0],
                                   _ptr(peak_ws), _stream()), "vfx_post_f32")
+
+
+# ---- train-mode restorer (mode 2) --------------------------------------------------------------------------------
+def bn_stats(x, L, pitch_log2, gamma, beta, scale, shift, eps=1e-5):
+    """Batch statistics of train-mode BatchNorm -> scale / shift (device float32 (B*G,)).  ``pitch_log2`` > 0: x is a
+    (B,C,L = H*P) pitch map, one BN channel per map channel, over each row's x._vfx_rows extent and the first P-1
+    columns; 0: x is a (B,C,L) activation and one BN channel spans all C channels (BatchNorm2d(1) on (B,1,T,C)).
+    The workspace comes from torch's caching allocator (stream-ordered: it is not reused before the launches ran)."""
+    _need_cuda(x, gamma, beta, scale, shift)
+    B, Cn = x.shape[0], x.shape[1]
+    h = _lib.lib()
+    nb = h.vfx_bn_stats_workspace_bytes(B, Cn, L, pitch_log2)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    xd = tdesc(x)
+    check(h.vfx_bn_stats_f32(C.byref(xd), B, Cn, L, pitch_log2, _ptr(gamma), _ptr(beta), float(eps), _ptr(scale),
+                             _ptr(shift), _ptr(ws), nb, _stream()), "vfx_bn_stats_f32")
+
+
+def bn_apply(x, y, L, pitch_log2, scale, shift, slope=None, groups=None):
+    """y = act(x * scale + shift) over x's valid region (x._vfx_rows); ``slope`` None: identity, else leaky ReLU with
+    that slope (0.0: ReLU).  ``groups`` defaults to the channel count for maps (pitch_log2 > 0) and to 1 otherwise."""
+    _need_cuda(x, y, scale, shift)
+    B, Cn = x.shape[0], x.shape[1]
+    if groups is None:
+        groups = Cn if pitch_log2 > 0 else 1
+    xd, yd = tdesc(x), tdesc(y)
+    act, s = (POST_NONE, 0.0) if slope is None else (POST_LRELU, float(slope))
+    check(_lib.lib().vfx_bn_apply_f32(C.byref(xd), C.byref(yd), B, Cn, L, pitch_log2, groups, _ptr(scale), _ptr(shift),
+                                      act, s, _stream()), "vfx_bn_apply_f32")
+
+
+def dropout(x, T, rowkey, layer, relu=False):
+    """Seeded dropout (voicefixer_amd/dropout.py) in place on x (B,C,>=T), rows from x._vfx_rows; ``rowkey`` device
+    int32 (B,3) = (segment, key lo, key hi) per row."""
+    _need_cuda(x, rowkey)
+    assert rowkey.dtype == torch.int32 and rowkey.is_contiguous() and rowkey.numel() == 3 * x.shape[0]
+    xd = tdesc(x)
+    check(_lib.lib().vfx_dropout_f32(C.byref(xd), x.shape[0], x.shape[1], T, _ptr(rowkey), int(layer), int(bool(relu)),
+                                     _stream()), "vfx_dropout_f32")
