@@ -364,6 +364,22 @@ int vfx_post_rows_f32(const float* y, int64_t y_bstride, int Ly, const int32_t* 
                       int64_t out_bstride, const int32_t* n_rows, int n_max, int B, uint32_t* peak_ws,
                       vfx_stream_t stream);
 
+/* ---- rate conversion ---------------------------------------------------------------- */
+
+/* Band-limited polyphase rate conversion of rows (what librosa.load(sr=44100) does inside the reference,
+ * voicefixer/base.py:47-49; the same sum as the host resampler of include/vfx_audio.h, for B rows at once):
+ *   y[r][m] = sum_i bank[p][i] * x[r][lo + i],  pos = c + m*down, kmax = pos / up, p = pos mod up, lo = kmax - J + 1,
+ *   m < ny_r = ceil(n_rows[r] * up / down) (and < ny_max); x samples outside [0, n_rows[r]) count as zero.
+ * bank: device float32 [up][J], phase p's J taps reversed (bank[p][i] = g[p + (J-1-i)*up], g = the L-tap zero-phase
+ * low-pass scaled by up, zero past L; c = (L-1)/2): audio_io.polyphase_bank builds it.  x is [B][x_stride], y
+ * [B][y_stride] (y_stride >= ny_max), n_rows device int32[B] (sample counts of x's rows, each <= x_stride).
+ * row_index (device int32[n_index], may be NULL: then n_index == B and every row is converted) lists the rows ONE launch
+ * converts -- a mixed-rate batch costs one launch per rate pair; rows not listed, and columns >= ny_r of listed rows,
+ * are left untouched.  Positions are 64-bit (any row length).  Returns VFX_EINVAL on bad arguments. */
+int vfx_resample_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, const int32_t* row_index,
+                          int n_index, const float* bank, int J, int up, int down, int c, float* y, int64_t y_stride,
+                          int64_t ny_max, vfx_stream_t stream);
+
 /* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
 
 /* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into

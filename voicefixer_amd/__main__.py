@@ -19,6 +19,9 @@ Differences, all deliberate:
   * ``--selfcheck [IN.wav]`` (extension): runs the input through the path with the default (Winograd), the direct and the
     opt-in bf16x3 arithmetic and compares them stage by stage (voicefixer_amd/selfcheck.py) -- the one-command check for
     users with real checkpoints;
+  * ``--output-sample-rate HZ`` (extension): outputs are converted on the device and written at that rate (default
+    44100, nothing converted); ``--resample-on-device`` (extension): inputs at other rates are decoded at their own rate
+    and converted on the MI355X instead of in the host's decode workers (folder mode: forwarded to every ``--gpus`` rank);
   * output formats are WAV and FLAC (``audio_io.FORMATS``) instead of whatever libsndfile offers;
   * folder mode isolates faults per FILE: an unreadable / truncated / too short input or a row the device refuses costs that
     file only -- it is listed on stderr with its reason, every other file is written, the exit status is 2 (all ranks of a
@@ -68,12 +71,18 @@ def mode_outfile(outfile, mode, append_mode):
     return os.path.join(os.path.dirname(outfile), "{}-mode{}{}".format(base, mode, ext))
 
 
-def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None):
+def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
+              resample_on_device=False):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
     start = time.time()
-    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed)
+    kw = {}
+    if output_sample_rate is not None:
+        kw["output_sample_rate"] = output_sample_rate
+    if resample_on_device:
+        kw["resample_on_device"] = True
+    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, **kw)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 
@@ -107,7 +116,19 @@ def build_parser():
                              "outputs are written under a temporary name and renamed, so an existing output is a complete one)")
     parser.add_argument("--io-threads", type=int, default=0,
                         help="(extension) folder mode: decode / encode workers per rank (default: host cores / (2 * ranks), 2..8)")
+    parser.add_argument("--output-sample-rate", type=_rate, default=None, metavar="HZ",
+                        help="(extension) write the outputs at this sample rate (converted on the device; default 44100)")
+    parser.add_argument("--resample-on-device", default=False, action="store_true",
+                        help="(extension) convert inputs at other rates than 44.1 kHz on the device instead of in the host's "
+                             "decode workers")
     return parser
+
+
+def _rate(text):
+    v = int(text, 0)
+    if v <= 0:
+        raise argparse.ArgumentTypeError("a sample rate must be a positive number of samples per second")
+    return v
 
 
 def _seed(text):
@@ -213,7 +234,8 @@ def main(argv=None):
             print("--mode all: writing modes 0, 1 and 2 (seed %d)" % args.seed)
     if process_file:
         for m in modes:
-            writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed)
+            writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
+                      output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -227,7 +249,8 @@ def main(argv=None):
                 voicefixer.restore_folder(args.infolder, args.outfolder, mode=m, batch_size=args.batch_size,
                                           name_suffix="-mode%d" % m if append else "", stats=st,
                                           skip_existing=args.skip_existing, io_threads=args.io_threads or None,
-                                          seed=args.seed)
+                                          seed=args.seed, output_sample_rate=args.output_sample_rate,
+                                          resample_on_device=args.resample_on_device)
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

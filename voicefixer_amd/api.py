@@ -102,6 +102,69 @@ def plan_stream_chunks(n, chunk, overlap, min_tail=1024):
     return [tuple(c) for c in plan]
 
 
+def _check_rate(rate, what="sample_rate"):
+    if isinstance(rate, bool) or int(rate) != rate or int(rate) <= 0:
+        raise ValueError("%s must be a positive integer number of samples per second (got %r)" % (what, rate))
+    return int(rate)
+
+
+def _output_rate(output_sample_rate):
+    """None (the default: 44.1 kHz, nothing converted) or a positive rate."""
+    return 44100 if output_sample_rate is None else _check_rate(output_sample_rate, "output_sample_rate")
+
+
+def _row_rates(sample_rate, n):
+    """One input rate per row from an int or a list."""
+    if isinstance(sample_rate, (list, tuple, np.ndarray)):
+        if len(sample_rate) != n:
+            raise ValueError("sample_rate: %d rates for %d rows" % (len(sample_rate), n))
+        return [_check_rate(r) for r in sample_rate]
+    return [_check_rate(sample_rate)] * n
+
+
+def convert_rows(seg, lens, rates, rate_out=44100):
+    """Rate conversion of device rows on the device (ops.resample_rows): row r of ``seg`` (B, >= max lens) holds lens[r]
+    samples at rates[r]; returns (B, max ny) rows at ``rate_out`` and their lengths ny = ceil(lens * up / down)
+    (audio_io.converted_length).  ONE launch per distinct rate pair (its rows listed by index); rows already at
+    ``rate_out`` are copied.  Nothing is converted, and ``seg`` itself is returned, when every row is at ``rate_out``."""
+    from . import ops
+    lens, rates = [int(n) for n in lens], [int(r) for r in rates]
+    if all(r == rate_out for r in rates):
+        return seg, lens
+    if max(lens) > seg.shape[1] or seg.stride(-1) != 1:
+        raise ValueError("convert_rows: rows of %d samples in a buffer of width %d" % (max(lens), seg.shape[1]))
+    B, dev = seg.shape[0], seg.device
+    new = [audio_io.converted_length(n, r, rate_out) for n, r in zip(lens, rates)]
+    y = torch.empty((B, max(max(new), 1)), dtype=torch.float32, device=dev)
+    n_rows = torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
+    for sr in sorted(set(rates)):
+        rows = [r for r in range(B) if rates[r] == sr]
+        if sr == rate_out:
+            for r in rows:
+                y[r, :lens[r]] = seg[r, :lens[r]]
+            continue
+        up, down = audio_io.rate_ratio(sr, rate_out)
+        idx = None if len(rows) == B else torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True)
+        ops.resample_rows(seg, n_rows, y, up, down, row_index=idx)
+    return y, new
+
+
+def convert_output(full, lens, rate_out):
+    """Restored 44.1 kHz device rows -> ``rate_out`` on the device, then the reference's peak rule once more on every
+    converted row (base.py:131-133: a row whose peak exceeds 1 is divided by its peak -- band-limited conversion of a
+    peak-normalised row can overshoot, and audio_io.to_int16 would then skip its 2^15 scaling).  Returns (rows, lengths)."""
+    from . import ops
+    if rate_out == 44100:
+        return full, list(lens)
+    y, new = convert_rows(full if full.stride(-1) == 1 else full.contiguous(), lens, [44100] * len(lens), rate_out)
+    B, dev = y.shape[0], y.device
+    out = torch.empty_like(y)
+    ny_rows = torch.tensor(new, dtype=torch.int32).to(dev, non_blocking=True)
+    peak_ws = torch.empty((B,), dtype=torch.int32, device=dev)
+    ops.post_rows(y, y.shape[1], out, ny_rows, max(new), peak_ws, ly_rows=ny_rows)
+    return out, new
+
+
 class Vocoder(nn.Module):
     """44.1 kHz TFGAN-style universal vocoder (voicefixer/vocoder/base.py)."""
 
@@ -296,16 +359,27 @@ class VoiceFixer(nn.Module):
         raise ValueError("mode must be 0, 1 or 2")
 
     @torch.no_grad()
-    def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None):
+    def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
+                      output_sample_rate=None):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
+        ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
+        (ops.resample_rows, the filter of audio_io.resample_hq) before the path runs, to ceil(N * 44100 / sample_rate)
+        samples.  ``output_sample_rate`` (extension, default 44.1 kHz): the restored waveform is converted on the device
+        to that rate and the peak rule is applied once more to the converted waveform (``convert_output``).
         ``mode=2`` with ``seed`` (int in [0, 2**64)): the restorer in train mode -- batch statistics per segment, seeded
         dropout (dropout.py; segment s of the file draws the masks of (seed, s)); always fp32.  A segment of <= 64 frames
         (< 28224 samples: a short file, or the short tail of a long one) raises ValueError, as the reference does."""
         self._check_mode(mode, seed)
+        rate_in, rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
         pipe = self._get_pipe()
         wav = np.asarray(wav_10k, dtype=np.float32)
         n = wav.shape[0]
+        src = None           # the input converted to 44.1 kHz on the device (when it arrives at another rate)
+        if rate_in != 44100:
+            x = torch.from_numpy(np.ascontiguousarray(wav))[None].to(pipe.device)
+            y, (n,) = convert_rows(x, [n], [rate_in])
+            src = y[0, :n]
         # Segment boundaries exactly as the reference's while-loop (base.py:117-120,137): full 30 s
         # segments, then a shorter tail.  Segments are independent in mode 0 (no carried state), so all
         # full segments of a long file go through the path as ONE batch (the reference runs them one
@@ -323,13 +397,23 @@ class VoiceFixer(nn.Module):
             res = []
             for i in range(0, len(full), self.segment_batch):
                 grp = full[i:i + self.segment_batch]
-                seg = torch.from_numpy(np.stack([wav[a:b] for a, b in grp])).to(pipe.device)
+                if src is None:
+                    seg = torch.from_numpy(np.stack([wav[a:b] for a, b in grp])).to(pipe.device)
+                else:
+                    seg = torch.stack([src[a:b] for a, b in grp])
                 out = self._restore_segments(pipe, seg, SEG_LENGTH, mode, your_vocoder_func, seed, range(i, i + len(grp)))
                 res.extend(out[k:k + 1] for k in range(len(grp)))
             for a, b in tail:
-                seg = torch.from_numpy(np.ascontiguousarray(wav[a:b]))[None].to(pipe.device)
+                if src is None:
+                    seg = torch.from_numpy(np.ascontiguousarray(wav[a:b]))[None].to(pipe.device)
+                else:
+                    seg = src[a:b][None].contiguous()
                 res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)]))
-            return torch.cat(res, -1).cpu().numpy()  # (synchronises)
+            out = torch.cat(res, -1)
+            if rate_out != 44100:
+                y, (m,) = convert_output(out, [out.shape[-1]], rate_out)
+                out = y[:, :m]
+            return out.cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
 
@@ -357,20 +441,32 @@ class VoiceFixer(nn.Module):
             self._stream_pool.append(torch.cuda.Stream(device=pipe.device))
         return self._stream_pool[:max(1, int(streams))]
 
-    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None):
-        """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, the launch sequence, D2H of the result into
-        a pinned tensor, an event.  Nothing here waits for the device."""
+    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None):
+        """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates than
+        44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) D2H of the result into a pinned tensor, an
+        event.  Nothing here waits for the device."""
         from . import ops
-        tag, kind, host, lens = item
+        if len(item) not in (4, 5):
+            raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates)")
+        tag, kind, host, lens = item[:4]
         lens = list(lens)
+        rates = _row_rates(item[4], len(lens)) if len(item) == 5 and item[4] is not None else None
+        rate_out = _output_rate(output_sample_rate)
         if kind not in ("ragged", "samples") or len(lens) != host.shape[0] or max(lens) > host.shape[1]:
             raise ValueError("restore_batches: item must be (tag, 'ragged' | 'samples', host (B, >= max(lens)), lens (B))")
+        if rates is not None and all(r == 44100 for r in rates):
+            rates = None
+        lens_native = lens
+        if rates is not None:
+            lens = [audio_io.converted_length(n, r, 44100) for n, r in zip(lens, rates)]
         if kind == "ragged" and your_vocoder_func is not None:
             raise ValueError("restore_batches: a plugin vocoder takes 'samples' batches (equal lengths); plan_batches(ragged=False) cuts them")
         if kind == "samples" and min(lens) != max(lens):
             raise ValueError("restore_batches: a 'samples' batch holds rows of ONE length")
         with torch.cuda.stream(stream):
             seg = host.to(pipe.device, non_blocking=True)
+            if rates is not None:       # rows staged at their own rates: converted to 44.1 kHz here, one launch per rate pair
+                seg, lens = convert_rows(seg, lens_native, rates)
             if kind == "ragged":
                 if mode == 1:
                     if min(lens) < 1536:
@@ -406,6 +502,8 @@ class VoiceFixer(nn.Module):
                          for s0 in range(0, n, SEG_LENGTH)]
                 full = parts[0] if len(parts) == 1 else torch.cat(parts, -1)
                 lens_out = [full.shape[-1]] * len(lens)
+            if rate_out != 44100:
+                full, lens_out = convert_output(full, lens_out, rate_out)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
             out_host.copy_(full, non_blocking=True)
             ev = torch.cuda.Event()
@@ -413,7 +511,7 @@ class VoiceFixer(nn.Module):
         return [item, out_host, lens_out, ev]
 
     @torch.no_grad()
-    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None):
+    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -424,6 +522,10 @@ class VoiceFixer(nn.Module):
         H2D, the ~600 launches and the D2H of a batch are queued while earlier batches compute, so the device never waits
         for the host and the caller (restore_folder: decode / encode workers) works on other batches meanwhile.
         ``mode=2`` needs ``seed`` (restore_inmem): a row's result equals restoring that file alone with the same seed.
+        An item may carry a 5th field, ``rates``: the sample rate of every row (``lens`` then counts samples at those
+        rates); rows at other rates than 44.1 kHz are converted on the device before the path runs (``convert_rows``),
+        and ``kind`` / the planning refer to the converted lengths.  ``output_sample_rate``: results are converted on the
+        device (``convert_output``) before they cross to the host, ``lens_out`` counts samples at that rate.
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
@@ -459,7 +561,8 @@ class VoiceFixer(nn.Module):
                     pipe.vocoder.read_f16_flag()
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
-                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed)
+                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed,
+                                                            output_sample_rate)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
@@ -467,7 +570,8 @@ class VoiceFixer(nn.Module):
                 return rec[0][0], rec[1], rec[2]
 
             for item in batches:
-                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed))
+                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed,
+                                                  output_sample_rate))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -487,7 +591,8 @@ class VoiceFixer(nn.Module):
                 pipe.vocoder.read_f16_flag()
 
     @torch.no_grad()
-    def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None):
+    def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
+                      sample_rate=44100, output_sample_rate=None):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -500,11 +605,18 @@ class VoiceFixer(nn.Module):
         on ``streams`` HIP streams, pinned staging in both directions, the host one batch per stream ahead).
         ``mode=1``: every file (every 30 s segment of it) first goes through the device-side high-frequency cut
         (base.py:121-122, ``vfx_hf_cut_f32``) exactly as ``restore_inmem(mode=1)`` does it.  ``mode=2`` needs ``seed``:
-        every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it."""
+        every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it.
+        ``sample_rate`` (extension): the rate of the inputs, one int or a list with one rate per wav; rows are staged at
+        their own rates and converted on the device (one launch per distinct rate pair and batch), the batches are
+        planned by the converted lengths.  ``output_sample_rate``: as ``restore_inmem``."""
         self._check_mode(mode, seed)
-        order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
+        rates = _row_rates(sample_rate, len(wavs))
+        _output_rate(output_sample_rate)
+        native = all(r == 44100 for r in rates)
+        n44 = [len(w) if r == 44100 else audio_io.converted_length(len(w), r, 44100) for w, r in zip(wavs, rates)]
+        order = sorted(range(len(wavs)), key=lambda i: n44[i])
         outs = [None] * len(wavs)
-        plan = plan_batches([len(wavs[k]) for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None)
+        plan = plan_batches([n44[k] for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None)
 
         def staged():
             for kind, grp in plan:
@@ -517,9 +629,10 @@ class VoiceFixer(nn.Module):
                 for r, k in enumerate(idx):
                     hv[r, :lens[r]] = wavs[k]
                     hv[r, lens[r]:] = 0.0
-                yield idx, kind, host, lens
+                yield (idx, kind, host, lens) if native else (idx, kind, host, lens, [rates[k] for k in idx])
 
-        for idx, out_host, lens_out in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed):
+        kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
+        for idx, out_host, lens_out in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
             ov = out_host.numpy()
             for r, k in enumerate(idx):
                 outs[k] = ov[r:r + 1, :lens_out[r]].copy()   # (the pinned block goes back to torch's host cache)
@@ -527,7 +640,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_stream(self, wav, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=8, mode=0,
-                       your_vocoder_func=None, on_chunk=None):
+                       your_vocoder_func=None, on_chunk=None, sample_rate=44100, output_sample_rate=None):
         """Long-form restoration with overlap-add (BASELINE config 5; NOT in the reference, whose 30 s segments
         are hard-cut -- ``restore_inmem`` keeps that behaviour): chunks of ``chunk_seconds`` every
         ``chunk_seconds - overlap_seconds``, each restored independently (equal-length chunks are batched),
@@ -537,11 +650,23 @@ class VoiceFixer(nn.Module):
         aligned at the chunk's start, so the chunk length is rounded down to a multiple of 512 (every full chunk keeps
         its length) and only the last chunk loses its sub-512 tail -- the output is that much shorter, as the
         reference's mode-1 output is.  Modes 0 and 1 only: ``mode=2`` raises NotImplementedError (its per-segment
-        statistics have no overlap-add form).  Returns float32 numpy (1, N')."""
+        statistics have no overlap-add form).  Returns float32 numpy (1, N').
+        ``sample_rate`` (extension): the rate of ``wav``; another rate than 44.1 kHz is converted once, up front, on the
+        device, and the chunks are cut from the converted waveform.  ``output_sample_rate`` other than 44.1 kHz raises
+        NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries."""
         self._check_mode(mode)
+        rate_in = _check_rate(sample_rate)
+        if _output_rate(output_sample_rate) != 44100:
+            raise NotImplementedError("restore_stream: output_sample_rate is not built -- converting the on_chunk stretches "
+                                      "would need the resampler's filter state at every chunk boundary; use restore_inmem")
         pipe = self._get_pipe()
         wav = np.asarray(wav, dtype=np.float32)
         n = wav.shape[0]
+        src = None           # the input converted to 44.1 kHz on the device (when it arrives at another rate)
+        if rate_in != 44100:
+            x = torch.from_numpy(np.ascontiguousarray(wav))[None].to(pipe.device)
+            y, (n,) = convert_rows(x, [n], [rate_in])
+            src = y[0, :n]
         chunk, ov = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
         if mode == 1:
             chunk -= chunk % 512
@@ -554,7 +679,10 @@ class VoiceFixer(nn.Module):
         while i < len(plan):
             length = plan[i][1]
             grp = [c for c in plan[i:i + batch_size] if c[1] == length]
-            seg = torch.from_numpy(np.stack([wav[a:a + length] for a, _ in grp])).to(pipe.device)
+            if src is None:
+                seg = torch.from_numpy(np.stack([wav[a:a + length] for a, _ in grp])).to(pipe.device)
+            else:
+                seg = torch.stack([src[a:a + length] for a, _ in grp])
             res = pipe.run_checked(lambda: self._restore_segments(pipe, seg, length, mode, your_vocoder_func).cpu().numpy())
             got = res.shape[1]          # == length in mode 0; 512 * (length // 512) in mode 1
             for (a, _), y in zip(grp, res):
@@ -578,7 +706,7 @@ class VoiceFixer(nn.Module):
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
-    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None):
+    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
@@ -586,6 +714,8 @@ class VoiceFixer(nn.Module):
         voicefixer/__main__.py:187-212, keeps every file it finished before a bad one)."""
         from collections import deque
         kw = {"seed": seed} if mode == 2 else {}
+        if output_sample_rate is not None:
+            kw["output_sample_rate"] = output_sample_rate
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -620,9 +750,13 @@ class VoiceFixer(nn.Module):
                 if not bad:
                     raise
                 first = "%s: %s" % (type(exc).__name__, exc)
-                for tag, kind, host, lens in bad:
+                for it in bad:
+                    tag, kind, host, lens = it[:4]
+                    rates = it[4] if len(it) == 5 else None
                     for r in range(len(tag)):
                         one = (tag[r:r + 1], kind, host[r:r + 1, :max(int(lens[r]), 1)], [lens[r]])
+                        if rates is not None:
+                            one += ([rates[r]],)
                         try:
                             for t1, o1, l1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
                                 yield t1, o1, l1
@@ -633,7 +767,7 @@ class VoiceFixer(nn.Module):
 
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
-                       skip_existing=False, seed=None):
+                       skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -662,7 +796,12 @@ class VoiceFixer(nn.Module):
         FLAC (the workers decode / resample / encode in libvfx_audio.so, several thousand x real time).
         ``io_threads``: decode / encode workers of this rank (default: the host's cores / (2 * world), 2..8).
         ``stats`` (optional dict) receives this rank's counters: files, audio seconds, wall seconds, summed worker
-        seconds of decode and encode, seconds the device stage waited for decoded input, ``failed``, ``skipped``.
+        seconds of decode and encode (decode includes the host resampling; ``resample_worker_s`` is that part alone),
+        seconds the device stage waited for decoded input, ``failed``, ``skipped``.
+        ``resample_on_device`` (extension, off by default): the workers only decode and down-mix; staging rows hold the
+        files' own rates and the device converts every rate group of a batch to 44.1 kHz (``restore_batches``' rates
+        field) -- a file whose reduced rate ratio has max(up, down) > audio_io.DEVICE_MAX_RATIO is still resampled on the
+        host.  ``output_sample_rate``: outputs are converted on the device (``convert_output``) and written at that rate.
         Returns the list of file names THIS rank wrote."""
         import threading
         import time
@@ -670,6 +809,7 @@ class VoiceFixer(nn.Module):
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
+        rate_out = _output_rate(output_sample_rate)
         rank, world = vdist.rank_world(rank, world)
         if io_threads is None:
             io_threads = vdist.default_io_threads(world)
@@ -683,46 +823,73 @@ class VoiceFixer(nn.Module):
             flac.native()      # load the C codec once, before the workers race for it
         t_start = time.perf_counter()
         lock = threading.Lock()
-        cnt = {"decode_s": 0.0, "encode_s": 0.0, "stall_s": 0.0}
+        cnt = {"decode_s": 0.0, "encode_s": 0.0, "stall_s": 0.0, "resample_s": 0.0}
         failed = []            # (index, reason): files this rank gave up on
         real_len = {}          # index -> samples the decoder returned
         truncated = []         # (index, header length, decoded length): restored at the decoded length
+        stage = {}             # resample_on_device: index -> (rate of its staging row, planned samples at that rate)
+
+        def on_device(sr):
+            return sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) <= audio_io.DEVICE_MAX_RATIO
 
         def scan(i):
             """Planning length of file i from its header; None + reason when the header is unreadable.  A header that
             promises less than a restorable file (0 in a streamed / interrupted recording) is not believed: the file
             is decoded once to see what is really there."""
             try:
-                n, promised = audio_io.wav_length(paths[i], 44100, with_promise=True)
+                if resample_on_device:
+                    sr, n_nat, p_nat = audio_io.wav_info(paths[i])
+                    n, promised = audio_io.converted_length(n_nat, sr, 44100), audio_io.converted_length(p_nat, sr, 44100)
+                else:
+                    n, promised = audio_io.wav_length(paths[i], 44100, with_promise=True)
                 if promised != n:         # (a header that promises more than the file holds: planned at what is there)
                     with lock:
                         truncated.append((i, promised, n))
                 if n < min_len:
-                    n = len(audio_io.load_wav(paths[i], 44100))
+                    if resample_on_device:
+                        n_nat = len(audio_io.load_wav_native(paths[i])[0])
+                        n = audio_io.converted_length(n_nat, sr, 44100)
+                    else:
+                        n = len(audio_io.load_wav(paths[i], 44100))
+                if resample_on_device:
+                    stage[i] = (sr, n_nat) if on_device(sr) else (44100, n)
                 return n, None
             except Exception as e:    # noqa: BLE001 -- any unreadable file is this file's problem only
                 return None, "%s: %s" % (type(e).__name__, e)
 
         def decode_into(i, row, n):
-            """Worker: file i -> staging row (width n = the header's promise).  Returns the number of samples really
-            there (<= n: a longer decode is cut at the staging width), or raises -- the caller drops the row."""
+            """Worker: file i -> staging row (width n = the header's promise, at the row's rate).  Returns the number of
+            samples really there (<= n: a longer decode is cut at the staging width), or raises -- the caller drops the row.
+            (audio_io.load_wav's steps, with the host resampling timed on its own; with resample_on_device the row stays
+            at the file's rate unless the device does not take its ratio.)"""
             t0 = time.perf_counter()
-            x = audio_io.load_wav(paths[i], 44100)
+            x, sr = audio_io.load_wav_native(paths[i])
+            rs = 0.0
+            if sr != 44100 and not (resample_on_device and stage[i][0] == sr):
+                t1 = time.perf_counter()
+                x = audio_io.resample_hq(x, sr, 44100)
+                rs = time.perf_counter() - t1
+            x = np.ascontiguousarray(x, dtype=np.float32)
             m = min(len(x), n)
             row[:m] = x[:m]
             row[m:] = 0.0
             with lock:
                 cnt["decode_s"] += time.perf_counter() - t0
+                cnt["resample_s"] += rs
                 if len(x) != n and not any(t[0] == i for t in truncated):
-                    truncated.append((i, n, len(x)))
+                    sr_row = row_rate(i)
+                    truncated.append((i, audio_io.converted_length(n, sr_row, 44100), audio_io.converted_length(len(x), sr_row, 44100)))
             return m
+
+        def row_rate(i):
+            return stage[i][0] if resample_on_device else 44100
 
         def encode_from(row, i):
             t0 = time.perf_counter()
             final = os.path.join(outfolder, names[i])
             part = os.path.join(outfolder, ".part-%d-%s" % (os.getpid(), names[i]))   # (same extension: save_wave picks the container from it)
             try:
-                audio_io.save_wave(row, part, 44100)
+                audio_io.save_wave(row, part, rate_out)
                 os.replace(part, final)
             except BaseException:
                 if os.path.exists(part):
@@ -761,7 +928,7 @@ class VoiceFixer(nn.Module):
             def submit_decode(b):
                 kind, grp = plan[b]
                 idx = [mine[g] for g in grp]
-                lens = [lengths[i] for i in idx]
+                lens = [stage[i][1] if resample_on_device else lengths[i] for i in idx]     # (staging: at each row's rate)
                 try:
                     host = torch.empty((len(idx), max(lens)), dtype=torch.float32, pin_memory=self._pin_memory())
                 except Exception as e:    # noqa: BLE001 -- a staging block that cannot be had (host memory, pinning) costs THIS batch
@@ -780,16 +947,18 @@ class VoiceFixer(nn.Module):
                     if host is None:          # (its staging block could not be allocated: the files are already in `failed`)
                         continue
                     t0 = time.perf_counter()
-                    keep, real = [], []
+                    keep, real, real44 = [], [], []
                     for r, f in enumerate(futs):
                         try:
                             m = f.result()
-                            if m < min_len:
+                            m44 = audio_io.converted_length(m, row_rate(idx[r]), 44100)
+                            if m44 < min_len:
                                 raise RuntimeError("too short to restore: the header promised %d samples, the decoder "
-                                                   "returned %d (mode %d needs >= %d)" % (lens[r], m, mode, min_len))
+                                                   "returned %d (mode %d needs >= %d)" % (lengths[idx[r]], m44, mode, min_len))
                             keep.append(r)
                             real.append(m)
-                            real_len[idx[r]] = m
+                            real44.append(m44)
+                            real_len[idx[r]] = m44
                         except Exception as e:    # noqa: BLE001 -- a decode error costs this file only
                             failed.append((idx[r], "%s: %s" % (type(e).__name__, e)))
                     cnt["stall_s"] += time.perf_counter() - t0
@@ -800,12 +969,14 @@ class VoiceFixer(nn.Module):
                         if self._pin_memory():
                             host = host.pin_memory()
                         idx = [idx[r] for r in keep]
-                    if kind == "samples" and min(real) != max(real):
+                    rates = [row_rate(i) for i in idx]
+                    tail = (rates,) if resample_on_device else ()
+                    if kind == "samples" and min(real44) != max(real44):
                         # equal-length bucket (several 30 s segments, plugin vocoder) with a truncated member: one batch per row
                         for r in range(len(idx)):
-                            yield idx[r:r + 1], kind, host[r:r + 1, :real[r]], real[r:r + 1]
+                            yield (idx[r:r + 1], kind, host[r:r + 1, :real[r]], real[r:r + 1]) + tuple(t[r:r + 1] for t in tail)
                         continue
-                    yield idx, kind, host, real
+                    yield (idx, kind, host, real) + tail
 
             writes = deque()           # per batch: the futures of its rows (their views keep the batch's pinned result alive)
             dev_failed = []
@@ -822,8 +993,11 @@ class VoiceFixer(nn.Module):
 
             source_error = None
             try:
+                kw = {"seed": seed} if mode == 2 else {}
+                if output_sample_rate is not None:
+                    kw["output_sample_rate"] = output_sample_rate
                 for idx, out_host, lens_out in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func, streams, mode,
-                                                                               **({"seed": seed} if mode == 2 else {})):
+                                                                               **kw):
                     ov = out_host.numpy()
                     writes.append([(i, pool.submit(encode_from, ov[r:r + 1, :lens_out[r]], i)) for r, i in enumerate(idx)])
                     drain(ahead + 2)       # bounded backlog: pinned results do not pile up behind a slow disk
@@ -840,7 +1014,8 @@ class VoiceFixer(nn.Module):
         if stats is not None:
             stats.update(rank=rank, world=world, files=len(written), folder_files=len(files), batches=len(plan),
                          audio_s=sum(real_len[i] for i in done) / 44100.0, wall_s=time.perf_counter() - t_start,
-                         decode_worker_s=cnt["decode_s"], encode_worker_s=cnt["encode_s"],
+                         decode_worker_s=cnt["decode_s"], encode_worker_s=cnt["encode_s"], resample_worker_s=cnt["resample_s"],
+                         resample_on_device=bool(resample_on_device), output_sample_rate=rate_out,
                          device_waited_for_decode_s=cnt["stall_s"], io_threads=io_threads,
                          failed=sorted((files[i], why) for i, why in failed), skipped=sorted(skipped),
                          truncated=sorted((files[i], n, m) for i, n, m in truncated if i in real_len or i in mine))
@@ -850,7 +1025,21 @@ class VoiceFixer(nn.Module):
     def _pin_memory():
         return torch.cuda.is_available()
 
-    def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None):
-        wav_10k = self._load_wav(input, sample_rate=44100)
-        out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed)
-        audio_io.save_wave(out_np_wav, fname=output, sample_rate=44100)
+    def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
+                resample_on_device=False):
+        """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
+        rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
+        resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device)."""
+        rate_out = _output_rate(output_sample_rate)
+        if resample_on_device:
+            x, sr = audio_io.load_wav_native(input)
+            if sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) > audio_io.DEVICE_MAX_RATIO:
+                x, sr = audio_io.resample_hq(x, sr, 44100), 44100
+            out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
+                                            your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
+                                            output_sample_rate=output_sample_rate)
+        else:
+            wav_10k = self._load_wav(input, sample_rate=44100)
+            out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed,
+                                            output_sample_rate=output_sample_rate)
+        audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out)

@@ -77,9 +77,9 @@ def _riff_info(path):
                 f.seek(size + (size & 1), 1)
 
 
-def wav_length(path, sample_rate=SR, with_promise=False):
-    """Number of samples ``load_wav(path, sample_rate)`` will return, from the file header (and the file size) alone;
-    ``with_promise``: (that number, the number the header PROMISES) -- they differ for a truncated recording."""
+def wav_info(path):
+    """(sample rate, samples, samples the header PROMISES) of a WAV / FLAC file at its own rate, from the header (and the
+    file size) alone."""
     promised = None
     if str(path).lower().endswith(".flac"):
         from . import flac
@@ -91,28 +91,43 @@ def wav_length(path, sample_rate=SR, with_promise=False):
             n = flac.read(path)[1].shape[0]     # count what is really there
     else:
         sr, n, promised = _riff_info(path)
-    promised = n if promised is None else promised
+    return int(sr), n, (n if promised is None else promised)
+
+
+def wav_length(path, sample_rate=SR, with_promise=False):
+    """Number of samples ``load_wav(path, sample_rate)`` will return, from the file header (and the file size) alone;
+    ``with_promise``: (that number, the number the header PROMISES) -- they differ for a truncated recording."""
+    sr, n, promised = wav_info(path)
     if sr != sample_rate:
-        from math import gcd
-        g = gcd(int(sr), int(sample_rate))
-        up, down = sample_rate // g, sr // g
-        n, promised = -(-n * up // down), -(-promised * up // down)  # resample_poly: ceil(n * up / down)
+        n, promised = converted_length(n, sr, sample_rate), converted_length(promised, sr, sample_rate)  # ceil(n * up / down)
     return (n, promised) if with_promise else n
 
 
 _HQ_FILTERS = {}
 
+# largest max(up, down) the device resampler takes (api: larger reduced ratios -- no standard rate pair comes close -- are
+# converted by resample_hq on the host, file by file)
+DEVICE_MAX_RATIO = 1024
 
-def resample_hq(x, sr_in, sr_out, use_native=None):
-    """Band-limited rate conversion along the last axis, ceil(n * sr_out / sr_in) samples (librosa.load(sr=...) ->
-    soxr_hq).  One Kaiser-windowed sinc at the common rate up * sr_in: pass band edge 0.913 and stop band edge 1.0 of
-    the lower of the two Nyquist frequencies, 125 dB (beta = 0.1102 (A - 8.7), length from Kaiser's estimate), applied
-    as a polyphase filter: one dot product per output sample in libvfx_audio.so (vfx_resample_poly_f32: float32, several
-    times scipy's speed and without the interpreter lock, so the folder driver's workers scale), or scipy's upfirdn in
-    float64 when that library is not built / ``use_native=False`` (the two agree to float32 rounding)."""
+
+def rate_ratio(sr_in, sr_out):
+    """(up, down): the reduced ratio sr_out / sr_in of a conversion."""
     from math import gcd
     g = gcd(int(sr_in), int(sr_out))
-    up, down = int(sr_out) // g, int(sr_in) // g
+    return int(sr_out) // g, int(sr_in) // g
+
+
+def converted_length(n, sr_in, sr_out):
+    """Samples a conversion of n samples returns: ceil(n * up / down) (resample_poly's length)."""
+    up, down = rate_ratio(sr_in, sr_out)
+    return -(-int(n) * up // down)
+
+
+def hq_filter(up, down):
+    """The Kaiser-windowed sinc behind ``resample_hq`` at the common rate up * fs_in: (h float64 with unit DC gain,
+    g = float32(h * up)).  Pass band edge 0.913 and stop band edge 1.0 of the lower of the two Nyquist frequencies,
+    125 dB (beta = 0.1102 (A - 8.7), length from Kaiser's estimate, odd: zero phase).  Cached per (up, down); the host
+    resampler and the device bank (polyphase_bank) are built from this one design."""
     h = _HQ_FILTERS.get((up, down))
     if h is None:
         from scipy.signal import firwin
@@ -122,6 +137,36 @@ def resample_hq(x, sr_in, sr_out, use_native=None):
         h = firwin(taps, 0.5 * (f_pass + f_stop), window=("kaiser", 0.1102 * (att - 8.7)))       # (unit DC gain; the gain `up` is applied below)
         h = (h, np.ascontiguousarray(h * up, dtype=np.float32))
         _HQ_FILTERS[(up, down)] = h
+    return h
+
+
+def polyphase_bank(g, up):
+    """The per-phase tap layout of the polyphase sum (csrc_host/vfx_resample.c, vfx_resample_rows_f32): bank [up, J],
+    bank[p][i] = g[p + (J - 1 - i) * up] (phase p's taps reversed, zero past the filter's end), J = ceil(L / up) taps per
+    phase, c = (L - 1) / 2 the filter's centre.  Returns (bank in g's dtype, J, c)."""
+    g = np.asarray(g)
+    L = g.shape[0]
+    J = -(-L // up)
+    gp = np.zeros(up * J, dtype=g.dtype)
+    gp[:L] = g
+    bank = np.ascontiguousarray(gp.reshape(J, up).T[:, ::-1])      # [p][j] = g[p + j*up], then j -> J - 1 - i
+    return bank, J, (L - 1) // 2
+
+
+def hq_bank(up, down):
+    """(bank float32 [up, J], J, c): the per-phase layout of ``hq_filter(up, down)``'s float32 taps -- exactly what the host
+    resampler builds from the same taps inside vfx_resample_poly_f32; ops.resample_rows uploads it once per device."""
+    return polyphase_bank(hq_filter(up, down)[1], up)
+
+
+def resample_hq(x, sr_in, sr_out, use_native=None):
+    """Band-limited rate conversion along the last axis, ceil(n * sr_out / sr_in) samples (librosa.load(sr=...) ->
+    soxr_hq).  The filter of ``hq_filter`` applied as a polyphase filter: one dot product per output sample in
+    libvfx_audio.so (vfx_resample_poly_f32: float32, several times scipy's speed and without the interpreter lock, so the
+    folder driver's workers scale), or scipy's upfirdn in float64 when that library is not built / ``use_native=False``
+    (the two agree to float32 rounding).  The device form of the same sum is ops.resample_rows."""
+    up, down = rate_ratio(sr_in, sr_out)
+    h = hq_filter(up, down)
     from . import flac
     lib = flac.native() if use_native in (None, True) else None
     x = np.asarray(x)
@@ -142,8 +187,8 @@ def resample_hq(x, sr_in, sr_out, use_native=None):
     return resample_poly(np.asarray(x, dtype=np.float64), up, down, axis=-1, window=h[0]).astype(np.float32)
 
 
-def load_wav(path, sample_rate=SR, mono=True):
-    """Decode + (if needed) resample + downmix, float32 in [-1, 1] (librosa.load semantics)."""
+def load_wav_native(path, mono=True):
+    """Decode + downmix at the file's own rate: (float32 samples in [-1, 1], sample rate)."""
     low = str(path).lower()
     if low.endswith(".flac"):
         from . import flac
@@ -165,6 +210,12 @@ def load_wav(path, sample_rate=SR, mono=True):
         raise RuntimeError("input format not supported offline (WAV and FLAC are): %s" % path)
     if x.ndim == 2:
         x = x.mean(axis=1) if mono else x.T
+    return x, int(sr)
+
+
+def load_wav(path, sample_rate=SR, mono=True):
+    """Decode + (if needed) resample + downmix, float32 in [-1, 1] (librosa.load semantics)."""
+    x, sr = load_wav_native(path, mono)
     if sr != sample_rate:
         x = resample_hq(x, sr, sample_rate)
     return np.ascontiguousarray(x, dtype=np.float32)

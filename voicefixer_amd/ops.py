@@ -465,3 +465,37 @@ def dropout(x, T, rowkey, layer, relu=False):
     xd = tdesc(x)
     check(_lib.lib().vfx_dropout_f32(C.byref(xd), x.shape[0], x.shape[1], T, _ptr(rowkey), int(layer), int(bool(relu)),
                                      _stream()), "vfx_dropout_f32")
+
+
+_RESAMPLE_BANKS = {}
+
+
+def resample_bank(device, up, down):
+    """(bank, J, c) of the (up, down) conversion on ``device``: audio_io.hq_bank uploaded once per device and cached."""
+    key = (str(torch.device(device)), up, down)
+    hit = _RESAMPLE_BANKS.get(key)
+    if hit is None:
+        from . import audio_io
+        bank, J, c = audio_io.hq_bank(up, down)
+        hit = (torch.from_numpy(bank).to(device), J, c)
+        _RESAMPLE_BANKS[key] = hit
+    return hit
+
+
+def resample_rows(x, n_rows, y, up, down, ny_max=None, row_index=None):
+    """Polyphase rate conversion on the device (vfx_resample_rows_f32): x (B, >= max n) -> y (B, >= ny_max); row r holds
+    n_rows[r] samples (device int32 (B,)) and receives ceil(n_rows[r] * up / down) of them (at most ny_max, default y's
+    width).  row_index (device int32 or None): only the listed rows are converted, the others are left untouched."""
+    _need_cuda(x, n_rows, y, row_index)
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.dim() == 2 and y.dim() == 2
+    assert x.stride(1) == 1 and y.stride(1) == 1 and x.shape[0] == y.shape[0] == n_rows.numel()
+    assert n_rows.dtype == torch.int32 and (row_index is None or row_index.dtype == torch.int32)
+    ny_max = y.shape[1] if ny_max is None else int(ny_max)
+    if ny_max > y.shape[1]:
+        raise _lib.VfxError("resample_rows: ny_max %d exceeds the output width %d" % (ny_max, y.shape[1]))
+    bank, J, c = resample_bank(x.device, int(up), int(down))
+    n_index = x.shape[0] if row_index is None else row_index.numel()
+    check(_lib.lib().vfx_resample_rows_f32(_ptr(x), x.stride(0) if x.shape[0] > 1 else x.shape[1], _ptr(n_rows),
+                                           x.shape[0], _ptr(row_index), n_index, _ptr(bank), J, int(up), int(down), c,
+                                           _ptr(y), y.stride(0) if y.shape[0] > 1 else y.shape[1], ny_max, _stream()),
+          "vfx_resample_rows_f32")
