@@ -380,6 +380,29 @@ int vfx_resample_rows_f32(const float* x, int64_t x_stride, const int32_t* n_row
                           int n_index, const float* bank, int J, int up, int down, int c, float* y, int64_t y_stride,
                           int64_t ny_max, vfx_stream_t stream);
 
+/* ---- loudness normalisation (ITU-R BS.1770-4, one channel) --------------------------------------------------------- */
+
+/* Bytes of the workspace vfx_loudness_rows_f32 needs for B rows of at most n_max samples (0 on bad arguments). */
+size_t vfx_loudness_workspace_bytes(int B, int64_t n_max, int hop, int S);
+
+/* Integrated loudness L (LUFS) of B rows and, with a target, the normalising gain applied to them:
+ *   K-weighting (shelf then high-pass biquad, coef = host float64[10]: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2, run
+ *   in fp32), quarters of hop samples, 400 ms blocks of 4 quarters, absolute gate -70 LUFS, relative gate -10 LU;
+ *   L = -inf when no block passes (silence, rows under 4 quarters).  g = min(10^((target - L)/20), 10^(ceiling_db/20) / P),
+ *   P = max|x| of the row (a sample-peak ceiling); g = 1 when L = -inf; out = (float)g * x.
+ * x is [B][x_stride] (x_stride >= n_max when B > 1), n_rows device int32[B] (each clamped to [0, n_max]).  The state of the
+ * filter is carried across chunks of S samples (a multiple of 32, 32 <= S <= min(hop, 8192)) by an affine scan: mpow is
+ * device float64[16][4][4], the powers M^(2^i) of the one-chunk state transition M = A^S; lookback (1..255) is the number
+ * of preceding 256-chunk spans whose carry is summed (terms further back are negligible).  target NaN: measure only, out
+ * may be NULL and nothing is applied; otherwise out ([B][out_stride], may be x itself) receives the first n_rows[r]
+ * samples of every row and nothing past them.  result: device float64[B][3] = {L, g, P}.  ws: device workspace of
+ * >= vfx_loudness_workspace_bytes bytes, 16-byte aligned.  At most 4 launches, no host synchronisation; VFX_EINVAL on bad
+ * arguments (nothing launched). */
+int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                          const double* coef, const double* mpow, int S, int hop, int lookback, double target,
+                          double ceiling_db, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes,
+                          vfx_stream_t stream);
+
 /* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
 
 /* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into

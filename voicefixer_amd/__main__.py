@@ -22,6 +22,8 @@ Differences, all deliberate:
   * ``--output-sample-rate HZ`` (extension): outputs are converted on the device and written at that rate (default
     44100, nothing converted); ``--resample-on-device`` (extension): inputs at other rates are decoded at their own rate
     and converted on the MI355X instead of in the host's decode workers (folder mode: forwarded to every ``--gpus`` rank);
+  * ``--loudness LUFS`` (extension): every output is normalised on the device to that integrated loudness (ITU-R BS.1770-4),
+    limited by the sample-peak ceiling ``--peak-ceiling DBFS`` (default -1); file and folder mode, every ``--mode``;
   * output formats are WAV and FLAC (``audio_io.FORMATS``) instead of whatever libsndfile offers;
   * folder mode isolates faults per FILE: an unreadable / truncated / too short input or a row the device refuses costs that
     file only -- it is listed on stderr with its reason, every other file is written, the exit status is 2 (all ranks of a
@@ -72,7 +74,7 @@ def mode_outfile(outfile, mode, append_mode):
 
 
 def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
-              resample_on_device=False):
+              resample_on_device=False, loudness=None, peak_ceiling=-1.0):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
@@ -82,6 +84,8 @@ def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=Fals
         kw["output_sample_rate"] = output_sample_rate
     if resample_on_device:
         kw["resample_on_device"] = True
+    if loudness is not None:
+        kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
     voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, **kw)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
@@ -121,6 +125,11 @@ def build_parser():
     parser.add_argument("--resample-on-device", default=False, action="store_true",
                         help="(extension) convert inputs at other rates than 44.1 kHz on the device instead of in the host's "
                              "decode workers")
+    parser.add_argument("--loudness", type=_lufs, default=None, metavar="LUFS",
+                        help="(extension) normalise every output on the device to this integrated loudness (ITU-R BS.1770-4), "
+                             "in [-70, 0) LUFS, e.g. -23 (EBU R128) or -16 (podcasts)")
+    parser.add_argument("--peak-ceiling", type=_dbfs, default=-1.0, metavar="DBFS",
+                        help="(extension) sample-peak ceiling of --loudness, in [-20, 0] dBFS (default -1)")
     return parser
 
 
@@ -129,6 +138,22 @@ def _rate(text):
     if v <= 0:
         raise argparse.ArgumentTypeError("a sample rate must be a positive number of samples per second")
     return v
+
+
+def _lufs(text):
+    from . import loudness
+    try:
+        return loudness.check_target(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _dbfs(text):
+    from . import loudness
+    try:
+        return loudness.check_ceiling(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _seed(text):
@@ -235,7 +260,8 @@ def main(argv=None):
     if process_file:
         for m in modes:
             writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
-                      output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device)
+                      output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device,
+                      loudness=args.loudness, peak_ceiling=args.peak_ceiling)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -250,7 +276,8 @@ def main(argv=None):
                                           name_suffix="-mode%d" % m if append else "", stats=st,
                                           skip_existing=args.skip_existing, io_threads=args.io_threads or None,
                                           seed=args.seed, output_sample_rate=args.output_sample_rate,
-                                          resample_on_device=args.resample_on_device)
+                                          resample_on_device=args.resample_on_device, loudness=args.loudness,
+                                          peak_ceiling=args.peak_ceiling)
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

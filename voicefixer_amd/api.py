@@ -165,6 +165,47 @@ def convert_output(full, lens, rate_out):
     return out, new
 
 
+def apply_loudness(full, lens, rate, target, peak_ceiling=-1.0):
+    """Loudness normalisation of device rows (ops.loudness_rows, BS.1770-4 integrated loudness): row r of ``full`` holds
+    lens[r] samples at ``rate``; each is scaled by float32(g), g = min(10^((target - L)/20), 10^(peak_ceiling/20) / peak)
+    (a SAMPLE-peak ceiling; g = 1 when L = -inf: silence or under 400 ms).  Returns (rows, device float64 (B, 3) of
+    {L before, g, peak}); ``target`` None returns (full, None) and launches nothing."""
+    from . import loudness, ops
+    target, peak_ceiling = loudness.check_target(target), loudness.check_ceiling(peak_ceiling)
+    if target is None:
+        return full, None
+    x = full if full.stride(-1) == 1 else full.contiguous()
+    n_rows = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(x.device, non_blocking=True)
+    out = torch.empty_like(x)
+    res = ops.loudness_rows(x, n_rows, rate, target, peak_ceiling, out=out)
+    return out, res
+
+
+def _check_loudness(loudness_target, peak_ceiling):
+    from . import loudness
+    return loudness.check_target(loudness_target), loudness.check_ceiling(peak_ceiling)
+
+
+def measure_loudness(wav, sample_rate=44100):
+    """Integrated loudness (ITU-R BS.1770-4, one channel) in LUFS of a float32 array (N,) -- or of every array of a list,
+    in one device call -- measured on the device.  -inf: nothing above the gates (silence, or under 400 ms)."""
+    from . import loudness, ops
+    loudness.plan(sample_rate)
+    single = not isinstance(wav, (list, tuple))
+    wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in ([wav] if single else wav)]
+    if not wavs:
+        return []
+    dev = _device()
+    lens = [len(w) for w in wavs]
+    host = np.zeros((len(wavs), max(max(lens), 1)), np.float32)
+    for r, w in enumerate(wavs):
+        host[r, :len(w)] = w
+    x = torch.from_numpy(host).to(dev)
+    res = ops.loudness_rows(x, torch.tensor(lens, dtype=torch.int32).to(dev), sample_rate).cpu().numpy()
+    out = [float(v) for v in res[:, 0]]
+    return out[0] if single else out
+
+
 class Vocoder(nn.Module):
     """44.1 kHz TFGAN-style universal vocoder (voicefixer/vocoder/base.py)."""
 
@@ -360,7 +401,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
-                      output_sample_rate=None):
+                      output_sample_rate=None, loudness=None, peak_ceiling=-1.0):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
         ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
@@ -369,9 +410,13 @@ class VoiceFixer(nn.Module):
         to that rate and the peak rule is applied once more to the converted waveform (``convert_output``).
         ``mode=2`` with ``seed`` (int in [0, 2**64)): the restorer in train mode -- batch statistics per segment, seeded
         dropout (dropout.py; segment s of the file draws the masks of (seed, s)); always fp32.  A segment of <= 64 frames
-        (< 28224 samples: a short file, or the short tail of a long one) raises ValueError, as the reference does."""
+        (< 28224 samples: a short file, or the short tail of a long one) raises ValueError, as the reference does.
+        ``loudness`` (extension, LUFS in [-70, 0)): the whole output, after the peak rule and any output rate conversion, is
+        normalised on the device to that integrated loudness (ITU-R BS.1770-4), limited by the SAMPLE-peak ceiling
+        ``peak_ceiling`` (dBFS in [-20, 0]): one fp32 gain for the file (``apply_loudness``).  None (default): unchanged."""
         self._check_mode(mode, seed)
         rate_in, rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
+        loud = _check_loudness(loudness, peak_ceiling)
         pipe = self._get_pipe()
         wav = np.asarray(wav_10k, dtype=np.float32)
         n = wav.shape[0]
@@ -413,6 +458,8 @@ class VoiceFixer(nn.Module):
             if rate_out != 44100:
                 y, (m,) = convert_output(out, [out.shape[-1]], rate_out)
                 out = y[:, :m]
+            if loud[0] is not None:
+                out, _ = apply_loudness(out, [out.shape[-1]], rate_out, *loud)
             return out.cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
@@ -441,10 +488,11 @@ class VoiceFixer(nn.Module):
             self._stream_pool.append(torch.cuda.Stream(device=pipe.device))
         return self._stream_pool[:max(1, int(streams))]
 
-    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None):
+    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None, loudness=None,
+                     peak_ceiling=-1.0):
         """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates than
-        44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) D2H of the result into a pinned tensor, an
-        event.  Nothing here waits for the device."""
+        44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) (loudness normalisation,) D2H of the result
+        -- and of the per-row loudness results -- into pinned tensors, an event.  Nothing here waits for the device."""
         from . import ops
         if len(item) not in (4, 5):
             raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates)")
@@ -504,14 +552,20 @@ class VoiceFixer(nn.Module):
                 lens_out = [full.shape[-1]] * len(lens)
             if rate_out != 44100:
                 full, lens_out = convert_output(full, lens_out, rate_out)
+            loud_host = None
+            if loudness is not None:
+                full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling)
+                loud_host = torch.empty(tuple(res.shape), dtype=torch.float64, pin_memory=True)
+                loud_host.copy_(res, non_blocking=True)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
             out_host.copy_(full, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-        return [item, out_host, lens_out, ev]
+        return [item, out_host, lens_out, ev, loud_host]
 
     @torch.no_grad()
-    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None):
+    def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
+                        loudness=None, peak_ceiling=-1.0):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -526,11 +580,15 @@ class VoiceFixer(nn.Module):
         rates); rows at other rates than 44.1 kHz are converted on the device before the path runs (``convert_rows``),
         and ``kind`` / the planning refer to the converted lengths.  ``output_sample_rate``: results are converted on the
         device (``convert_output``) before they cross to the host, ``lens_out`` counts samples at that rate.
+        ``loudness`` / ``peak_ceiling``: every row is normalised on the device (restore_inmem) before it crosses, and the
+        generator yields ``(tag, out_host, lens_out, loud_host)``, ``loud_host`` a pinned float64 (B, 3) of {LUFS before,
+        gain, sample peak} per row, copied with the batch.
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
+        _check_loudness(loudness, peak_ceiling)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -562,16 +620,16 @@ class VoiceFixer(nn.Module):
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
                             inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed,
-                                                            output_sample_rate)
+                                                            output_sample_rate, loudness, peak_ceiling)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
                 inflight.popleft()
-                return rec[0][0], rec[1], rec[2]
+                return (rec[0][0], rec[1], rec[2]) + ((rec[4],) if loudness is not None else ())
 
             for item in batches:
                 inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed,
-                                                  output_sample_rate))
+                                                  output_sample_rate, loudness, peak_ceiling))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -592,7 +650,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
-                      sample_rate=44100, output_sample_rate=None):
+                      sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -608,8 +666,10 @@ class VoiceFixer(nn.Module):
         every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it.
         ``sample_rate`` (extension): the rate of the inputs, one int or a list with one rate per wav; rows are staged at
         their own rates and converted on the device (one launch per distinct rate pair and batch), the batches are
-        planned by the converted lengths.  ``output_sample_rate``: as ``restore_inmem``."""
+        planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``: as ``restore_inmem`` (each
+        file is measured on its own row, whatever else its batch holds)."""
         self._check_mode(mode, seed)
+        _check_loudness(loudness, peak_ceiling)
         rates = _row_rates(sample_rate, len(wavs))
         _output_rate(output_sample_rate)
         native = all(r == 44100 for r in rates)
@@ -632,7 +692,9 @@ class VoiceFixer(nn.Module):
                 yield (idx, kind, host, lens) if native else (idx, kind, host, lens, [rates[k] for k in idx])
 
         kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
-        for idx, out_host, lens_out in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
+        if loudness is not None:
+            kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+        for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
             ov = out_host.numpy()
             for r, k in enumerate(idx):
                 outs[k] = ov[r:r + 1, :lens_out[r]].copy()   # (the pinned block goes back to torch's host cache)
@@ -640,7 +702,8 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_stream(self, wav, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=8, mode=0,
-                       your_vocoder_func=None, on_chunk=None, sample_rate=44100, output_sample_rate=None):
+                       your_vocoder_func=None, on_chunk=None, sample_rate=44100, output_sample_rate=None, loudness=None,
+                       peak_ceiling=-1.0):
         """Long-form restoration with overlap-add (BASELINE config 5; NOT in the reference, whose 30 s segments
         are hard-cut -- ``restore_inmem`` keeps that behaviour): chunks of ``chunk_seconds`` every
         ``chunk_seconds - overlap_seconds``, each restored independently (equal-length chunks are batched),
@@ -653,9 +716,13 @@ class VoiceFixer(nn.Module):
         statistics have no overlap-add form).  Returns float32 numpy (1, N').
         ``sample_rate`` (extension): the rate of ``wav``; another rate than 44.1 kHz is converted once, up front, on the
         device, and the chunks are cut from the converted waveform.  ``output_sample_rate`` other than 44.1 kHz raises
-        NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries."""
+        NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries; so
+        does ``loudness``: the stretches leave before a whole-file measurement exists."""
         self._check_mode(mode)
         rate_in = _check_rate(sample_rate)
+        if _check_loudness(loudness, peak_ceiling)[0] is not None:
+            raise NotImplementedError("restore_stream: loudness normalisation is not built -- the on_chunk stretches leave before "
+                                      "the whole file has been measured; use restore_inmem or restore_folder")
         if _output_rate(output_sample_rate) != 44100:
             raise NotImplementedError("restore_stream: output_sample_rate is not built -- converting the on_chunk stretches "
                                       "would need the resampler's filter state at every chunk boundary; use restore_inmem")
@@ -706,7 +773,8 @@ class VoiceFixer(nn.Module):
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
-    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None):
+    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None,
+                                  loudness=None, peak_ceiling=-1.0):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
@@ -716,6 +784,8 @@ class VoiceFixer(nn.Module):
         kw = {"seed": seed} if mode == 2 else {}
         if output_sample_rate is not None:
             kw["output_sample_rate"] = output_sample_rate
+        if loudness is not None:
+            kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -734,9 +804,9 @@ class VoiceFixer(nn.Module):
 
         while True:
             try:
-                for tag, out_host, lens_out in self.restore_batches(feed(), your_vocoder_func, streams, mode, **kw):
+                for rec in self.restore_batches(feed(), your_vocoder_func, streams, mode, **kw):
                     pending.popleft()
-                    yield tag, out_host, lens_out
+                    yield rec
                 if src_exc:
                     raise BatchSourceError("the batch source failed after %s: %s" % (type(src_exc[0]).__name__, src_exc[0])) from src_exc[0]
                 return
@@ -758,8 +828,8 @@ class VoiceFixer(nn.Module):
                         if rates is not None:
                             one += ([rates[r]],)
                         try:
-                            for t1, o1, l1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
-                                yield t1, o1, l1
+                            for rec1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
+                                yield rec1
                         except (KeyboardInterrupt, GeneratorExit):
                             raise
                         except Exception as e1:    # noqa: BLE001
@@ -767,7 +837,8 @@ class VoiceFixer(nn.Module):
 
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
-                       skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False):
+                       skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False, loudness=None,
+                       peak_ceiling=-1.0):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -802,6 +873,8 @@ class VoiceFixer(nn.Module):
         files' own rates and the device converts every rate group of a batch to 44.1 kHz (``restore_batches``' rates
         field) -- a file whose reduced rate ratio has max(up, down) > audio_io.DEVICE_MAX_RATIO is still resampled on the
         host.  ``output_sample_rate``: outputs are converted on the device (``convert_output``) and written at that rate.
+        ``loudness`` / ``peak_ceiling``: every output is normalised on the device (restore_inmem) before it is written;
+        ``stats["loudness"]`` lists ``(output name, LUFS before, gain in dB)`` of the files written.
         Returns the list of file names THIS rank wrote."""
         import threading
         import time
@@ -810,6 +883,7 @@ class VoiceFixer(nn.Module):
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
         rate_out = _output_rate(output_sample_rate)
+        _check_loudness(loudness, peak_ceiling)
         rank, world = vdist.rank_world(rank, world)
         if io_threads is None:
             io_threads = vdist.default_io_threads(world)
@@ -899,6 +973,7 @@ class VoiceFixer(nn.Module):
                 cnt["encode_s"] += time.perf_counter() - t0
 
         written, skipped, done = [], [], []
+        loud_rows = {}         # index -> (LUFS before, gain in dB)
         with ThreadPoolExecutor(max_workers=io_threads) as pool:
             scanned = list(pool.map(scan, range(len(files))))
             # every rank must deal from the SAME list: inside an initialised process group of this world size the scans are
@@ -996,9 +1071,15 @@ class VoiceFixer(nn.Module):
                 kw = {"seed": seed} if mode == 2 else {}
                 if output_sample_rate is not None:
                     kw["output_sample_rate"] = output_sample_rate
-                for idx, out_host, lens_out in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func, streams, mode,
-                                                                               **kw):
+                if loudness is not None:
+                    kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+                for idx, out_host, lens_out, *extra in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func,
+                                                                                       streams, mode, **kw):
                     ov = out_host.numpy()
+                    if extra:
+                        lv = extra[0].numpy()
+                        for r, i in enumerate(idx):
+                            loud_rows[i] = (float(lv[r, 0]), 20.0 * float(np.log10(lv[r, 1])))
                     writes.append([(i, pool.submit(encode_from, ov[r:r + 1, :lens_out[r]], i)) for r, i in enumerate(idx)])
                     drain(ahead + 2)       # bounded backlog: pinned results do not pile up behind a slow disk
             except BatchSourceError as e:  # the source died: every batch it had handed over has been finished and is written below
@@ -1018,7 +1099,8 @@ class VoiceFixer(nn.Module):
                          resample_on_device=bool(resample_on_device), output_sample_rate=rate_out,
                          device_waited_for_decode_s=cnt["stall_s"], io_threads=io_threads,
                          failed=sorted((files[i], why) for i, why in failed), skipped=sorted(skipped),
-                         truncated=sorted((files[i], n, m) for i, n, m in truncated if i in real_len or i in mine))
+                         truncated=sorted((files[i], n, m) for i, n, m in truncated if i in real_len or i in mine),
+                         loudness=sorted((names[i],) + loud_rows[i] for i in done if i in loud_rows))
         return sorted(written)
 
     @staticmethod
@@ -1026,20 +1108,22 @@ class VoiceFixer(nn.Module):
         return torch.cuda.is_available()
 
     def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
-                resample_on_device=False):
+                resample_on_device=False, loudness=None, peak_ceiling=-1.0):
         """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
         rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
-        resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device)."""
+        resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device);
+        ``loudness`` / ``peak_ceiling``: as ``restore_inmem``."""
         rate_out = _output_rate(output_sample_rate)
+        _check_loudness(loudness, peak_ceiling)
         if resample_on_device:
             x, sr = audio_io.load_wav_native(input)
             if sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) > audio_io.DEVICE_MAX_RATIO:
                 x, sr = audio_io.resample_hq(x, sr, 44100), 44100
             out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
                                             your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
-                                            output_sample_rate=output_sample_rate)
+                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling)
         else:
             wav_10k = self._load_wav(input, sample_rate=44100)
             out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed,
-                                            output_sample_rate=output_sample_rate)
+                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling)
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out)

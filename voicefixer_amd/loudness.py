@@ -1,0 +1,136 @@
+"""Loudness normalisation of restored audio (ITU-R BS.1770-4 integrated loudness, one channel): the host half.
+
+The measurement and the gain run on the device (``vfx_loudness_rows_f32``, csrc/vfx_loudness.hip; ``ops.loudness_rows``);
+this module designs what the kernel is given, in float64, once per rate:
+
+  * the K-weighting biquads from their analog parameters (the shelf and the high-pass of BS.1770; at 48 kHz the formulas
+    reproduce the tables of the recommendation),
+  * ``hop`` = 100 ms of samples (a quarter of the 400 ms gating block) and the chunk length S of the filter scan,
+  * the powers M^(2^i) of the one-chunk state transition M = A^S (A: one sample of both biquads with zero input, built from
+    the fp32-rounded coefficients the kernel runs), and how many 256-chunk spans back the carried state still matters,
+
+and checks the user's parameters.  DESIGN.md 3.10 has the definition, the scan and the measured cost.
+"""
+import math
+
+import numpy as np
+
+SHELF_F0, SHELF_G_DB, SHELF_Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+SHELF_VB_EXP = 0.4996667741545416
+HP_F0, HP_Q = 38.13547087602444, 0.5003270373238773
+MIN_RATE, MAX_RATE = 4000, 768000
+SPAN = 256                    # chunks per workgroup of the kernel (LK_T)
+NPOW = 16                     # M^(2^i), i < NPOW (LK_NPOW)
+TARGET_RANGE = (-70.0, 0.0)   # LUFS, [lo, hi)
+CEILING_RANGE = (-20.0, 0.0)  # dBFS, [lo, hi]
+
+
+def _check_rate(fs):
+    if isinstance(fs, bool) or int(fs) != fs or not MIN_RATE <= int(fs) <= MAX_RATE:
+        raise ValueError("loudness: sample rate must be an integer in [%d, %d] (got %r)" % (MIN_RATE, MAX_RATE, fs))
+    return int(fs)
+
+
+def k_weighting(fs):
+    """(shelf_b, shelf_a, hp_b, hp_a) of the K-weighting at ``fs`` Hz, float64, a[0] = 1."""
+    fs = _check_rate(fs)
+    K = math.tan(math.pi * SHELF_F0 / fs)
+    Vh = 10.0 ** (SHELF_G_DB / 20.0)
+    Vb = Vh ** SHELF_VB_EXP
+    a0 = 1.0 + K / SHELF_Q + K * K
+    sb = np.array([(Vh + Vb * K / SHELF_Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / SHELF_Q + K * K) / a0])
+    sa = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / SHELF_Q + K * K) / a0])
+    K = math.tan(math.pi * HP_F0 / fs)
+    d = 1.0 + K / HP_Q + K * K
+    hb = np.array([1.0, -2.0, 1.0])
+    ha = np.array([1.0, 2.0 * (K * K - 1.0) / d, (1.0 - K / HP_Q + K * K) / d])
+    return sb, sa, hb, ha
+
+
+def hop_length(fs):
+    """Samples of one 100 ms quarter block: (fs + 5) // 10 (1103 at 11025 Hz)."""
+    return (_check_rate(fs) + 5) // 10
+
+
+def chunk_length(fs):
+    """Samples one lane filters: a multiple of 32 near fs / 200 (224 at 44.1 kHz: a 32 x 10 s batch is ~63 K lanes), never
+    more than a quarter block, so a chunk straddles at most one quarter boundary."""
+    return 32 * max(1, (_check_rate(fs) + 3200) // 6400)
+
+
+def coefficients(fs):
+    """The 10 float64 values the kernel takes: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2."""
+    sb, sa, hb, ha = k_weighting(fs)
+    return np.concatenate([sb, sa[1:], hb, ha[1:]])
+
+
+def transition(fs):
+    """A: the 4x4 zero-input state transition of one sample, state (shelf z1, z2, high-pass z1, z2) of the transposed
+    direct form II, with the coefficients rounded to fp32 as the kernel runs them."""
+    c = coefficients(fs).astype(np.float32).astype(np.float64)
+    b0s, b1s, b2s, a1s, a2s, b0h, b1h, b2h, a1h, a2h = c
+    A = np.zeros((4, 4))
+    for j in range(4):
+        s = np.zeros(4)
+        s[j] = 1.0
+        ys = s[0]                                      # zero input
+        t0, t1 = -a1s * ys + s[1], -a2s * ys
+        yh = b0h * ys + s[2]
+        t2, t3 = b1h * ys - a1h * yh + s[3], b2h * ys - a2h * yh
+        A[:, j] = (t0, t1, t2, t3)
+    return A
+
+
+_PLANS = {}
+
+
+def plan(fs):
+    """Everything the kernel needs at ``fs`` (cached): dict with coef (float64[10]), S, hop, mpow (float64[16, 4, 4]:
+    M^(2^i)) and lookback (spans whose carry is summed: the first p with max|Mspan^p| < 2^-80, Mspan = M^256)."""
+    fs = _check_rate(fs)
+    hit = _PLANS.get(fs)
+    if hit is not None:
+        return hit
+    S, hop = chunk_length(fs), hop_length(fs)
+    M = np.linalg.matrix_power(transition(fs), S)
+    pw = [M]
+    for _ in range(NPOW - 1):
+        pw.append(pw[-1] @ pw[-1])
+    mpow = np.ascontiguousarray(np.stack(pw))
+    span = pw[8]                                       # M^256
+    lookback, p = 1, span
+    while np.abs(p).max() >= 2.0 ** -80:
+        lookback += 1
+        p = p @ span
+        if lookback >= SPAN:
+            raise ValueError("loudness: the filter state does not decay at %d Hz" % fs)
+    hit = {"coef": coefficients(fs), "S": S, "hop": hop, "mpow": mpow, "lookback": lookback}
+    _PLANS[fs] = hit
+    return hit
+
+
+def _number(v, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a number (got %r)" % (what, v))
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError("%s must be finite (got %r)" % (what, v))
+    return v
+
+
+def check_target(target):
+    """None (no normalisation) or a loudness target in [-70, 0) LUFS."""
+    if target is None:
+        return None
+    v = _number(target, "loudness")
+    if not TARGET_RANGE[0] <= v < TARGET_RANGE[1]:
+        raise ValueError("loudness must be in [-70, 0) LUFS (got %r)" % target)
+    return v
+
+
+def check_ceiling(ceiling_db):
+    """A sample-peak ceiling in [-20, 0] dBFS."""
+    v = _number(ceiling_db, "peak_ceiling")
+    if not CEILING_RANGE[0] <= v <= CEILING_RANGE[1]:
+        raise ValueError("peak_ceiling must be in [-20, 0] dBFS (got %r)" % ceiling_db)
+    return v

@@ -499,3 +499,41 @@ def resample_rows(x, n_rows, y, up, down, ny_max=None, row_index=None):
                                            x.shape[0], _ptr(row_index), n_index, _ptr(bank), J, int(up), int(down), c,
                                            _ptr(y), y.stride(0) if y.shape[0] > 1 else y.shape[1], ny_max, _stream()),
           "vfx_resample_rows_f32")
+
+
+_LOUDNESS_MPOW = {}
+
+
+def loudness_rows(x, n_rows, rate, target=None, ceiling_db=-1.0, out=None):
+    """Integrated loudness (BS.1770-4, one channel) of the rows of x (B, >= max n) on the device (vfx_loudness_rows_f32):
+    row r holds n_rows[r] samples (device int32 (B,)) at ``rate`` Hz.  Returns a device float64 (B, 3) of {L in LUFS (-inf:
+    nothing above the gates), gain, sample peak}.  ``target`` (LUFS): rows are scaled by float32(gain) into ``out`` (default:
+    in place, into x) up to their own lengths; None measures only.  At most 4 launches, no synchronisation."""
+    from . import loudness
+    _need_cuda(x, n_rows, out)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == n_rows.numel()
+    assert n_rows.dtype == torch.int32
+    target = loudness.check_target(target)
+    ceiling_db = loudness.check_ceiling(ceiling_db)
+    p = loudness.plan(rate)
+    key = (str(x.device), int(rate))
+    mpow = _LOUDNESS_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(x.device)
+        _LOUDNESS_MPOW[key] = mpow
+    if target is not None and out is None:
+        out = x
+    if out is not None:
+        assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == x.shape[0]
+        assert out.shape[1] >= x.shape[1]
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_workspace_bytes(B, n_max, p["hop"], p["S"])
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    res = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
+    check(h.vfx_loudness_rows_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, coef, _ptr(mpow),
+                                  p["S"], p["hop"], p["lookback"], float("nan") if target is None else target, ceiling_db,
+                                  _ptr(out), (out.stride(0) if B > 1 else out.shape[1]) if out is not None else 0, _ptr(res),
+                                  _ptr(ws), nb, _stream()), "vfx_loudness_rows_f32")
+    return res
