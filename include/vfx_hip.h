@@ -139,6 +139,10 @@ uint64_t vfx_launch_count(void);
  *   code 80           convwg4_kernel<..>                          (Winograd F(4,3), 1-D), BL = output positions
  *   code 81           convwg4p_kernel<..>                         (the same tile on persistent workgroups: the two long launches of a
  *                     ResStack layer, tap / staging / weight pipeline running across tiles)
+ *   code 82           convwg4x_kernel<..>                         (the 128-channel convwg4_kernel tile with a 32 x 64 x 6 wave tile and a
+ *                     deferred epilogue: the wide ResStack launches of large batches)
+ *   code 83           convtw_kernel<..>                           (vfx_convtr1d_f32 as Winograd F(3,2) along the input axis,
+ *                     BM = output channels x BL = 3 * positions per phase)
  *   code 88           convwg4s_kernel<..>                         (Winograd F(4,3), 3x3 on a pitch map, kernel columns share one tile)
  *   code 32           convh_kernel                                (opt-in f16 arithmetic, vfx_conv1d_f16: direct sum on
  *                     v_mfma_f32_32x32x16_f16, BM = 128 output channels x BL = 128 positions) */

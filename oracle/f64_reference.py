@@ -1,11 +1,14 @@
-"""FLOAT64 REFERENCES OF THE SEQUENCE, FRONT-END AND PER-ROW KERNELS -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
+"""FLOAT64 REFERENCES OF THE SEQUENCE, FRONT-END, PER-ROW AND CONVOLUTION KERNELS -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
 Plain double-precision statements of what the recurrence (vfx_gru_bidir_f32 / vfx_gru_bidir2_f32), the analysis front-end
-(vfx_stft_mel_f32 / _rows_f32 / _oracle_f32) and the per-row bookkeeping kernels (vfx_mel_to_cond_rows_f32,
-vfx_unet_input_f32, vfx_post_rows_f32) compute, written from torch primitives (``torch.nn.GRU`` with
-packed sequences, ``torch.stft``) rather than through ``oracle.py``, so the two can check each other:
-tests/test_seq_reference_cpu.py pins these statements against the oracle on the CPU, tests/test_seq_kernels_gpu.py holds the
-kernels to them.  Ragged batches are given as a list of per-row lengths; every function returns float64 CPU tensors.
+(vfx_stft_mel_f32 / _rows_f32 / _oracle_f32), the per-row bookkeeping kernels (vfx_mel_to_cond_rows_f32,
+vfx_unet_input_f32, vfx_post_rows_f32) and the four convolution entry points that conv_taps_kernel serves (vfx_conv1d_f32,
+vfx_convtr1d_f32, vfx_conv2d_f32, vfx_convtr2d_3x3s2_f32, with their fused activations, bias, residual and per-row lengths)
+compute, written from torch primitives (``torch.nn.GRU`` with packed sequences, ``torch.stft``, ``torch.matmul``) rather than
+through ``oracle.py``, so the two can check each other: tests/test_seq_reference_cpu.py and tests/test_conv_reference_cpu.py
+pin these statements against the oracle and the torch operators on the CPU, tests/test_seq_kernels_gpu.py and
+tests/test_conv_taps_gpu.py hold the kernels to them.  Ragged batches are given as a list of per-row lengths; every function
+returns float64 CPU tensors.
 """
 import torch
 
@@ -146,3 +149,201 @@ def post_rows(y, ly_rows, n_rows):
         out.append(seg / pk if pk > 1.0 else seg)
     return out
 
+
+
+# --------------------------------------------------------------------------------------
+# first-generation convolution family (vfx_conv1d_f32, vfx_convtr1d_f32, vfx_conv2d_f32, vfx_convtr2d_3x3s2_f32)
+# --------------------------------------------------------------------------------------
+# Written from include/vfx_hip.h and the torch operators the entry points replace: every convolution is a sum over its
+# taps of one matrix product with a shifted slice of the (padded) input, so there is no algorithm to trust but the
+# index arithmetic on this page -- tests/test_conv_reference_cpu.py pins it against torch.nn.functional and the oracle's
+# modules.  Layouts are torch's own ((B, C, L) and dense (B, C, H, W) maps, torch weight layouts); to_pitch / from_pitch
+# move maps to and from the device's pitch layout.  Every function takes `lengths`: per-row valid extents (samples, or
+# map rows), each row then being computed as if it were alone in the batch; outputs past a row's own end are NaN.
+# `magnitude=True` returns sum |pre(x)| |w| + |bias| + |res| per output instead of the value: the scale that the
+# rounding error of the sum grows with.
+PRE_NONE, PRE_LRELU, PRE_AFFINE_LRELU = 0, 1, 2
+POST_NONE, POST_LRELU, POST_ELU, POST_TANH, POST_SIGMOID, POST_LRELU_SNAKE = 0, 1, 2, 3, 4, 5
+
+
+def to_pitch(x, pitch_log2, fill=0.0):
+    """Dense (B, C, H, W = P - 1) -> pitch map (B, C, H * P) with `fill` in the pad column."""
+    B, Cn, Hh, W = x.shape
+    P = 1 << pitch_log2
+    assert W == P - 1
+    out = torch.full((B, Cn, Hh, P), fill, dtype=x.dtype)
+    out[..., :W] = x
+    return out.reshape(B, Cn, Hh * P)
+
+
+def from_pitch(y, H, pitch_log2):
+    """Pitch map (B, C, >= H * P) -> (B, C, H, P), pad column included."""
+    P = 1 << pitch_log2
+    return y[:, :, :H * P].reshape(y.shape[0], y.shape[1], H, P)
+
+
+def conv_pre(x, pre=PRE_NONE, slope=0.0, scale=None, shift=None):
+    """The fused pre-activation of the input (VFX_PRE_*), float64; scale / shift are per input channel."""
+    x = x.to(torch.float64)
+    if pre == PRE_AFFINE_LRELU:
+        shp = [1, -1] + [1] * (x.dim() - 2)
+        x = x * scale.to(torch.float64).reshape(shp) + shift.to(torch.float64).reshape(shp)
+    if pre in (PRE_LRELU, PRE_AFFINE_LRELU):
+        x = torch.where(x > 0, x, x * float(slope))
+    return x
+
+
+def conv_post(v, post=POST_NONE, slope=0.0):
+    """The fused post-activation (VFX_POST_*), float64."""
+    if post in (POST_LRELU, POST_LRELU_SNAKE):
+        v = torch.where(v > 0, v, v * float(slope))
+        return v + torch.sin(v) if post == POST_LRELU_SNAKE else v
+    if post == POST_ELU:
+        return torch.where(v > 0, v, torch.expm1(v))
+    if post == POST_TANH:
+        return torch.tanh(v)
+    if post == POST_SIGMOID:
+        return 1.0 / (1.0 + torch.exp(-v))
+    assert post == POST_NONE
+    return v
+
+
+def post_lipschitz(post):
+    """Lipschitz constant of the post-activation (v + sin v has slope up to 2)."""
+    return 2.0 if post == POST_LRELU_SNAKE else 1.0
+
+
+def _finish(acc, bias, res, post, post_slope, magnitude):
+    """acc (B, Cout, ...) + bias + res -> post(...); or the magnitude |acc| + |bias| + |res| (acc then already is
+    sum |x~| |w|)."""
+    shp = [1, -1] + [1] * (acc.dim() - 2)
+    if magnitude:
+        if bias is not None:
+            acc = acc + bias.to(torch.float64).abs().reshape(shp)
+        return acc + res.to(torch.float64).abs() if res is not None else acc
+    if bias is not None:
+        acc = acc + bias.to(torch.float64).reshape(shp)
+    if res is not None:
+        acc = acc + res.to(torch.float64)
+    return conv_post(acc, post, post_slope)
+
+
+def _by_rows(fn, x, res, lengths, out_len):
+    """Ragged batches: run `fn(x_row, res_row)` on every row cut to its own extent (along dim 2) and paste the results
+    into a NaN-filled (B, Cout, out_len(max extent), ...) batch."""
+    outs = []
+    for b, n in enumerate(lengths):
+        xb = x[b:b + 1, :, :n]
+        outs.append(fn(xb, None if res is None else res[b:b + 1, :, :out_len(n)]))
+    full = torch.full((len(outs), outs[0].shape[1], out_len(x.shape[2])) + tuple(outs[0].shape[3:]), float("nan"),
+                      dtype=torch.float64)
+    for b, o in enumerate(outs):
+        full[b:b + 1, :, :o.shape[2]] = o
+    return full
+
+
+def conv1d(x, w, bias=None, res=None, dilation=1, reflect=False, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None,
+           post=POST_NONE, post_slope=0.0, lengths=None, magnitude=False):
+    """vfx_conv1d_f32: y[b,n,l] = post(bias[n] + res[b,n,l] + sum_{c,t} w[n,c,t] pre(x)[b,c,l + (t - (k-1)/2) dilation]),
+    the pre-activated input padded with zeros, or mirrored about its first and last sample (ReflectionPad1d).
+    x (B, Cin, L), w (Cout, Cin, k) with k odd -> (B, Cout, L) float64."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: conv1d(xb, w, bias, rb, dilation, reflect, pre, pre_slope, scale, shift, post,
+                                              post_slope, None, magnitude), x, res, lengths, lambda n: n)
+    k = w.shape[2]
+    assert k % 2 == 1
+    L, p = x.shape[2], (k - 1) // 2 * dilation
+    xa = conv_pre(x, pre, pre_slope, scale, shift)
+    w64 = w.to(torch.float64)
+    if magnitude:
+        xa, w64 = xa.abs(), w64.abs()
+    if reflect:
+        assert p < L
+        idx = torch.arange(-p, L + p).abs()
+        idx = torch.where(idx > L - 1, 2 * (L - 1) - idx, idx)
+        xp = xa[:, :, idx]
+    else:
+        xp = torch.zeros((x.shape[0], x.shape[1], L + 2 * p), dtype=torch.float64)
+        xp[:, :, p:p + L] = xa
+    acc = torch.zeros((x.shape[0], w.shape[0], L), dtype=torch.float64)
+    for t in range(k):
+        acc += torch.matmul(w64[:, :, t], xp[:, :, t * dilation:t * dilation + L])
+    return _finish(acc, bias, res, post, post_slope, magnitude)
+
+
+def convtr1d(x, w, bias=None, stride=2, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE,
+             post_slope=0.0, lengths=None, magnitude=False):
+    """vfx_convtr1d_f32 = ConvTranspose1d(Cin, Cout, kernel 2s, stride s, padding s // 2 + s % 2, output_padding s % 2):
+    input sample i adds w[c,n,t] x[b,c,i] to position i s + t - padding; positions outside [0, s Lin) are dropped.
+    x (B, Cin, Lin), w (Cin, Cout, 2s) -> (B, Cout, s Lin) float64."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: convtr1d(xb, w, bias, stride, pre, pre_slope, scale, shift, post, post_slope,
+                                                None, magnitude), x, None, lengths, lambda n: n * stride)
+    s = stride
+    assert w.shape[2] == 2 * s
+    Lin, pad = x.shape[2], s // 2 + s % 2
+    xa = conv_pre(x, pre, pre_slope, scale, shift)
+    w64 = w.to(torch.float64)
+    if magnitude:
+        xa, w64 = xa.abs(), w64.abs()
+    full = torch.zeros((x.shape[0], w.shape[1], (Lin + 1) * s), dtype=torch.float64)   # positions i s + t, t < 2s
+    for t in range(2 * s):
+        full[:, :, t:t + Lin * s:s] += torch.matmul(w64[:, :, t].t(), xa)
+    return _finish(full[:, :, pad:pad + s * Lin].clone(), bias, None, post, post_slope, magnitude)
+
+
+def conv2d(x, w, bias=None, res=None, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE,
+           post_slope=0.0, lengths=None, magnitude=False):
+    """vfx_conv2d_f32 on dense maps: Conv2d(k x k, k = 1 or 3, stride 1, padding k // 2) of the pre-activated input,
+    zero padding on all four sides (on the device the pad column of the pitch map IS the left / right padding, and
+    the output's pad column is written as zero: see to_pitch).  x (B, Cin, H, W), w (Cout, Cin, k, k) -> (B, Cout, H, W)
+    float64.  `lengths`: map rows per batch item."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: conv2d(xb, w, bias, rb, pre, pre_slope, scale, shift, post, post_slope, None,
+                                              magnitude), x, res, lengths, lambda n: n)
+    k = w.shape[2]
+    assert k in (1, 3) and w.shape[3] == k
+    B, _, Hh, W = x.shape
+    p = k // 2
+    xa = conv_pre(x, pre, pre_slope, scale, shift)
+    w64 = w.to(torch.float64)
+    if magnitude:
+        xa, w64 = xa.abs(), w64.abs()
+    xp = torch.zeros((B, x.shape[1], Hh + 2 * p, W + 2 * p), dtype=torch.float64)
+    xp[:, :, p:p + Hh, p:p + W] = xa
+    acc = torch.zeros((B, w.shape[0], Hh, W), dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            acc += torch.einsum("nc,bchw->bnhw", w64[:, :, ky, kx], xp[:, :, ky:ky + Hh, kx:kx + W])
+    return _finish(acc, bias, res, post, post_slope, magnitude)
+
+
+def convtr2d_3x3s2(x, w, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE, post_slope=0.0,
+                   lengths=None, magnitude=False):
+    """vfx_convtr2d_3x3s2_f32 = ConvTranspose2d(3 x 3, stride 2, padding 0) followed by DecoderBlockRes' cut of the last
+    output row: input (i, j) adds w[c,n,ky,kx] x[b,c,i,j] to (2 i + ky, 2 j + kx); (h, w) -> (2 h, 2 w + 1).
+    x (B, Cin, h, w), w (Cin, Cout, 3, 3) -> (B, Cout, 2 h, 2 w + 1) float64.  `lengths`: input map rows per item."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: convtr2d_3x3s2(xb, w, pre, pre_slope, scale, shift, post, post_slope, None,
+                                                      magnitude), x, None, lengths, lambda n: 2 * n)
+    B, _, h, wd = x.shape
+    xa = conv_pre(x, pre, pre_slope, scale, shift)
+    w64 = w.to(torch.float64)
+    if magnitude:
+        xa, w64 = xa.abs(), w64.abs()
+    full = torch.zeros((B, w.shape[1], 2 * h + 1, 2 * wd + 1), dtype=torch.float64)
+    for ky in range(3):
+        for kx in range(3):
+            full[:, :, ky:ky + 2 * h:2, kx:kx + 2 * wd:2] += torch.einsum("cn,bchw->bnhw", w64[:, :, ky, kx], xa)
+    return _finish(full[:, :, :2 * h].clone(), None, None, post, post_slope, magnitude)
+
+
+def conv_error(got, ref, mag, lipschitz=1.0):
+    """The figure the convolution tests bound: |got - ref| / (lipschitz * magnitude + |ref|) per output, over the
+    outputs where ref is not NaN (rows of a ragged batch end early).  Returns (max, sum of squares, count)."""
+    ok = ~torch.isnan(ref)
+    e = (got.to(torch.float64) - ref).abs() / (lipschitz * mag + ref.abs()).clamp(min=1e-300)
+    e = torch.where(ok, e, torch.zeros_like(e))      # a NaN in `got` at a valid output stays NaN and fails the bound
+    bad = torch.isnan(got.to(torch.float64)) & ok
+    mx = float("inf") if bool(bad.any()) else float(e.max())
+    return mx, float((e * e).sum()), int(ok.sum())

@@ -120,7 +120,8 @@ struct ConvArgs {
     float* ws;
     int bl_step;            // tile step along q (= BL, or BL - span for exact-width halo tiles)
     int nxv;                // activation staging slots per thread this launch needs (host copy of the kernel's nxv)
-    int res_init;           // 1: plain output map (out = q) -> the residual is loaded into the accumulators up front
+    int two_level;          // conv_taps_kernel: 1 = long K (>= 256 channels of 7 / 9 taps): partial sums of 64 channels (see the kernel)
+    int res_init;           // 1: plain output map (out = q) -> convw_kernel / conv_x3_kernel load the residual into the accumulators up front
     // ---- bf16x3 instance (conv_x3_kernel) only
     const void* w3;         // weights as bf16 hi/lo planes: [slab][Cin/16][plane][k-half][Cout][8]
     const ConvTables* tab3; // tap tables in POSITIONS (no 4-alignment: the x3 staging moves single floats)
@@ -355,14 +356,28 @@ __device__ __forceinline__ void acc_init_residual(f32x16 (&acc)[RM][RL], const f
     }
 }
 
-// ---- epilogue of one tile (bias is already in the accumulators)
-template <int BM, int BL, int WGM, int WGL>
+// ---- epilogue of one tile.  SUM_FIRST = false: the accumulators started at the bias (and, with res_init, at the residual).
+// SUM_FIRST = true (conv_taps_kernel): they hold the bare sum of products, and bias and residual are added here, in the
+// order torch adds them.  An accumulator that starts at bias + residual rounds every one of the K partial sums at the
+// magnitude of bias + residual: where those dominate the sum (small weight-norm gains) the result carried ~sqrt(K) fp32
+// roundings of the residual's size, 10-30 x the error of the sum added last (profiles/conv_taps_parity.txt).
+template <int BM, int BL, int WGM, int WGL, bool SUM_FIRST = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[BM / WGM / 32][BL / WGL / 32], int q0,
                                               int m0, int b, int wm, int wl, int lo, int hi, int ooff, int qend) {
     constexpr int WMT = BM / WGM, WLT = BL / WGL, RM = WMT / 32, RL = WLT / 32;
     float* __restrict__ yb = a.y + (long long)b * a.y_bs;
-    const float* __restrict__ rb = (a.res && !a.res_init) ? a.res + (long long)b * a.r_bs : nullptr;
+    const float* __restrict__ rb = (a.res && (SUM_FIRST || !a.res_init)) ? a.res + (long long)b * a.r_bs : nullptr;
     const int nbase = m0 + wm * WMT + 4 * hi;
+    // the bias of this lane's 16 rows per 32-row block (the staging registers are dead by now)
+    float4 bq[RM][4];
+    if (SUM_FIRST && a.post_act <= VFX_POST_LRELU) {
+#pragma unroll
+        for (int i = 0; i < RM; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                bq[i][g] = a.bias ? *reinterpret_cast<const float4*>(a.bias + nbase + i * 32 + 8 * g)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     if (a.post_act <= VFX_POST_LRELU) {
         // hot case (no / leaky-ReLU activation): unrolled, 32-bit offsets from the per-batch base, one
         // 32x32 accumulator tile at a time (sched barriers keep the register footprint of the in-loop
@@ -385,6 +400,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
                     for (int g = 0; g < 4; ++g) {
                         float v0 = acc[i][j][4 * g + 0], v1 = acc[i][j][4 * g + 1];
                         float v2 = acc[i][j][4 * g + 2], v3 = acc[i][j][4 * g + 3];
+                        if constexpr (SUM_FIRST) { v0 += bq[i][g].x; v1 += bq[i][g].y; v2 += bq[i][g].z; v3 += bq[i][g].w; }
                         if (rb) {
                             v0 += rb[ro + (8 * g + 0) * rcs];
                             v1 += rb[ro + (8 * g + 1) * rcs];
@@ -419,6 +435,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
                     const int n = nbase + i * 32 + (r & 3) + 8 * (r >> 2);
                     if (ok) {
                         float v = acc[i][j][r];
+                        if constexpr (SUM_FIRST) {
+                            if (a.bias) v += a.bias[n];
+                        }
                         if (rb) v += rb[(long long)n * a.r_cs + (long long)out * a.r_ls];
                         v = vfx_post(v, a.post_act, a.post_slope);
                         if (zero) v = 0.f;
@@ -559,11 +578,22 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
         st.w_off[j] = ((pt->tap_w[t] * a.CinPad + kc) * a.Cout + m0 + 4 * v) * (FAST ? 4 : 1);
     }
 
+    // the accumulators start at zero: bias and residual are added to the finished sum (conv_epilogue<.., SUM_FIRST>;
+    // split-K: splitk_reduce_kernel), so that the K partial sums are rounded at their own magnitude
     f32x16 acc[RM][RL];
-    acc_init_bias<RM, RL>(acc, SPLITK ? nullptr : a.bias, m0 + wm * WMT + 4 * hi);
-    if (!SPLITK && a.res && a.res_init)
-        acc_init_residual<RM, RL>(acc, a.res + (long long)b * a.r_bs, (int)a.r_cs, (int)a.r_ls, m0 + wm * WMT + 4 * hi,
-                                  q0 + wl * WLT + lo, qend);
+    acc_init_bias<RM, RL>(acc, nullptr, m0 + wm * WMT + 4 * hi);
+    // Two-level sum where K is long: the 4-channel K-chunk (7 or 9 taps per channel: K = 9 Cin of the deep UNet levels) on
+    // the small wave tiles (one or two 32x32 accumulators per wave: the 64x64, 128x64, 32x128 and 32x256 tiles those
+    // launches choose), not cut by split-K.  Every 64 input channels the accumulators are added into a second set and
+    // cleared, so a K = 9 * 768 sum is twelve partial sums of 576 products instead of one chain of 6912 -- a strictly
+    // sequential fp32 chain of that length was 5 x the RMS error of a blocked sum (profiles/conv_taps_parity.txt).
+    // The larger wave tiles have no registers for a second set; 8-channel chunks (K <= 3 Cin) and split-K partials are
+    // short chains already, and the second set cost a batch-1 step 4 % when every small-tile instance carried it; the
+    // host asks for it from 256 input channels on (ConvArgs::two_level).
+    constexpr bool TWO_LEVEL = RM * RL <= 2 && KC == 4 && !SPLITK;
+    constexpr int FLUSH = 64 / KC;   // K-chunks per partial sum (a power of two)
+    f32x16 acc2[TWO_LEVEL ? RM : 1][TWO_LEVEL ? RL : 1];
+    if constexpr (TWO_LEVEL) acc_init_bias<RM, RL>(acc2, nullptr, 0);
 
     const int ooff = __builtin_amdgcn_readfirstlane(pt->ooff);
     const int a_col = wm * WMT + lo;  // column into the weight tile row
@@ -672,12 +702,30 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
 #endif
         ++ch1;
         ++ch2;
+        if constexpr (TWO_LEVEL) {
+            if (a.two_level && ((s + 1) & (FLUSH - 1)) == 0 && s + 1 < S) {
+#pragma unroll
+                for (int i = 0; i < RM; ++i)
+#pragma unroll
+                    for (int j = 0; j < RL; ++j) {
+                        acc2[i][j] += acc[i][j];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                    }
+            }
+        }
+    }
+    if constexpr (TWO_LEVEL) {
+#pragma unroll
+        for (int i = 0; i < RM; ++i)
+#pragma unroll
+            for (int j = 0; j < RL; ++j) acc[i][j] += acc2[i][j];
     }
 #if VFX_ABL & 8
     const unsigned long long t_loop = __builtin_amdgcn_s_memtime();
 #endif
     if constexpr (SPLITK) conv_epilogue_partial<BM, BL, WGM, WGL>(a, acc, q0, m0, b, ks, wm, wl, lo, hi, qend);
-    else conv_epilogue<BM, BL, WGM, WGL>(a, acc, q0, m0, b, wm, wl, lo, hi, ooff, qend);
+    else conv_epilogue<BM, BL, WGM, WGL, true>(a, acc, q0, m0, b, wm, wl, lo, hi, ooff, qend);
 #if VFX_ABL & 8
     if (tid == 0 && FAST) {
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -1559,6 +1607,7 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     }
     a.tab = device_tables(tb);
     if (!a.tab) return VFX_EINVAL;
+    a.two_level = KC == 4 && Cin >= 256;
     g_last_tile = tc.BM * 100000 + tc.BL * 100 + KC;
     // split-K: a launch with few workgroups and a long K (the deep UNet levels at small batch: 48 workgroups x 864
     // serial K-chunks) is cut along K so that the whole chip works on it; plain output maps only
