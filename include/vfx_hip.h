@@ -407,6 +407,51 @@ int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int32_t* n_row
                           double ceiling_db, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes,
                           vfx_stream_t stream);
 
+/* ---- true peak and loudness report (ITU-R BS.1770-4 Annex 2, EBU R 128 / Tech 3341 / Tech 3342) --------------------------- */
+
+/* True peak TP of a row of n samples: the row is oversampled R times by the polyphase sum of vfx_resample_rows_f32 at
+ * down = 1 and the largest magnitude is kept,
+ *   y[m] = sum_i bank[p][i] * x[lo + i],  pos = c + m, kmax = pos / R, p = pos mod R, lo = kmax - J + 1,  m in [0, R*n),
+ *   samples outside [0, n) count as zero;   TP = max(P, max_m |y[m]|),  P = max|x| (so TP >= P);   R = 1 or n = 0: TP = P.
+ * bank: device float32 [R][J] in the layout of vfx_resample_rows_f32 (audio_io.polyphase_bank of the R-times
+ * interpolator, c = (L-1)/2 its centre); 1 <= J <= 2048, R in {1, 2, 4}, 0 <= c < R*J.  y is never stored: one fused
+ * kernel reduces |y| to one float per (row, tile of 1024 inputs), every output summed in one fixed order -- a row reads the
+ * same bits alone and inside any batch; positions are 64-bit.
+ *
+ * Bytes vfx_loudness_tp_rows_f32 needs BEHIND the vfx_loudness_workspace_bytes(B, n_max, hop, S) bytes of the loudness
+ * measurement, for B rows of at most n_max samples: B * (n_max/1024 + 2) floats, rounded (0 on bad arguments). */
+size_t vfx_true_peak_workspace_bytes(int B, int64_t n_max, int R, int J);
+
+/* vfx_loudness_rows_f32 with a TRUE-peak ceiling: the same arguments, measurement and bits of L and P, plus bank, J, R, c
+ * (above);  g = min(10^((target - L)/20), 10^(ceiling_db/20) / TP) (1 when L = -inf), ceiling_db read as dBTP;
+ * result: device float64[B][4] = {L, g, P, TP}.  target NaN: measure only.  ws: >= vfx_loudness_workspace_bytes(B, n_max,
+ * hop, S) + vfx_true_peak_workspace_bytes(B, n_max, R, J) bytes, 16-byte aligned.  Exactly one launch more than
+ * vfx_loudness_rows_f32 with the same arguments when R > 1 and n_max > 0 (the oversampling kernel; its partials are
+ * folded by the gate kernel), none more when R = 1; no host synchronisation.  Nothing is read past a row's length and
+ * nothing written outside ws, result and the rows of out.  VFX_EINVAL on bad arguments (nothing launched): those of
+ * vfx_loudness_rows_f32, a NULL bank, J or c out of range, R not in {1, 2, 4}, ws too small. */
+int vfx_loudness_tp_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                             const double* coef, const double* mpow, int S, int hop, int lookback, double target,
+                             double ceiling_db, const float* bank, int J, int R, int c, float* out, int64_t out_stride,
+                             double* result, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
+/* Bytes of the WHOLE workspace of vfx_loudness_report_rows_f32 (0 on bad arguments). */
+size_t vfx_loudness_report_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J);
+
+/* Loudness report of B rows (measure only): report is device float64[B][6] = {L, LRA, Mmax, Smax, P, TP}.
+ *   L, P, TP: as vfx_loudness_tp_rows_f32 (the same bits).
+ *   Mmax: the largest momentary loudness -0.691 + 10 log10 z_j over ALL 400 ms blocks (ungated); -inf without a block.
+ *   Short-term blocks: 30 consecutive quarters from every quarter j in [0, nq - 30], e_j = their energy / (30 hop);
+ *   Smax: the largest -0.691 + 10 log10 e_j; -inf without a block.
+ *   LRA (EBU Tech 3342): of the short-term values above -70 LUFS, those above the loudness of their mean energy - 20 LU,
+ *   sorted ascending (n values s[]): s[((n-1)*95 + 50) / 100] - s[((n-1) + 5) / 10] (integer division); 0 when n = 0.
+ * One launch more than vfx_loudness_tp_rows_f32 measuring only: one workgroup per row selects the two order statistics
+ * by counting over the float64 bit patterns (64 passes each, any row length), fixed-order reductions throughout.
+ * VFX_EINVAL on bad arguments (nothing launched). */
+int vfx_loudness_report_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                 const double* coef, const double* mpow, int S, int hop, int lookback, const float* bank,
+                                 int J, int R, int c, double* report, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
 /* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
 
 /* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into

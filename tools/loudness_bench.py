@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """What loudness normalisation costs on the device: device-event time of vfx_loudness_rows_f32 (measure +
 apply, 4 launches) for one 32 x 10 s batch at 44.1 kHz and for one 30-minute row; one JSON line per case.
+``--true-peak`` times, for the same two shapes and in one process, alternating: the sample-peak
+measurement (3 launches), the true-peak measurement (the same + the fused oversample-and-reduce kernel), and what the
+true peak cost before that kernel existed -- ops.resample_rows at up = R, down = 1 into an R-times-wider scratch, then
+abs().amax per row.  Median of ``--reps`` per pass, ``--passes`` passes: the spread of a leg's medians is the yardstick
+for the difference between two legs.  The shader clock is sampled over the timed window (bench.ClockSampler).
 
     python tools/loudness_bench.py [--reps 20]
+    python tools/loudness_bench.py --true-peak [--reps 10] [--passes 3]
     rocprofv3 --kernel-trace --stats -- python tools/loudness_bench.py     # per-kernel table
 """
 import argparse
@@ -36,10 +42,79 @@ def run(B, seconds, reps, fs=44100):
                       "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}), flush=True)
 
 
+def run_true_peak(B, seconds, reps, passes, fs=44100):
+    import time
+    import torch
+    import bench
+    from voicefixer_amd import loudness, ops
+    dev = torch.device("cuda", 0)
+    n = int(seconds * fs)
+    R = loudness.oversampling(fs)
+    g = torch.Generator().manual_seed(3)
+    x = (0.1 * torch.randn((B, n), generator=g)).to(dev)
+    n_rows = torch.full((B,), n, dtype=torch.int32, device=dev)
+    wide = torch.empty((B, R * n), device=dev)                      # the composition's scratch: R times the input
+
+    def composed():
+        ops.resample_rows(x, n_rows, wide, R, 1)
+        return wide.abs().amax(dim=1)
+
+    legs = {"sample_peak_measure": lambda: ops.loudness_rows(x, n_rows, fs),
+            "true_peak_measure": lambda: ops.loudness_rows(x, n_rows, fs, true_peak=True),
+            "resample_rows_then_amax": composed}
+    for fn in legs.values():                                        # warm-up: bank / plan uploads, code objects
+        fn()
+    a = ops.loudness_rows(x, n_rows, fs, true_peak=True)[:, 3].float()
+    b = torch.maximum(composed(), x.abs().amax(dim=1))
+    agree = float(((a - b).abs() / b).max())                        # the two ways measure the same peak
+    torch.cuda.synchronize()
+    med = {k: [] for k in legs}
+    sampler = bench.ClockSampler(torch.cuda.current_device(), period=0.02)
+    with sampler:
+        t0 = time.perf_counter()
+        for _ in range(passes):
+            ev = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():                          # alternating: the legs see the same machine
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    ev[k].append((e0, e1))
+            torch.cuda.synchronize()
+            for k in legs:
+                ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev[k])
+                med[k].append(round(ms[len(ms) // 2], 4))
+        t1 = time.perf_counter()
+    clocks = sampler.summary(t0, t1)
+    mid = {k: sorted(v)[len(v) // 2] for k, v in med.items()}
+    macs = B * n * R * ops.true_peak_bank(dev, R)[1]
+    fused = mid["true_peak_measure"] - mid["sample_peak_measure"]
+    print(json.dumps({"case": "true_peak", "rows": B, "seconds": seconds, "rate": fs, "R": R, "samples": B * n, "reps": reps,
+                      "medians_ms": med, "median_ms": mid,
+                      "spread_ms": {k: round(max(v) - min(v), 4) for k, v in med.items()},
+                      "fused_kernel_ms": round(fused, 4), "fused_kernel_tmacs": round(macs / fused / 1e9, 3) if fused > 0 else None,
+                      "composition_tmacs": round(macs / mid["resample_rows_then_amax"] / 1e9, 3),
+                      "scratch_bytes_composition": wide.numel() * 4,
+                      "scratch_bytes_fused": int(_true_peak_bytes(B, n, R, dev)), "max_rel_disagreement": agree,
+                      "sclk_mhz": clocks.get("sclk_mhz"), "clock_source": clocks.get("source")}), flush=True)
+
+
+def _true_peak_bytes(B, n, R, dev):
+    from voicefixer_amd import _lib, ops
+    return _lib.lib().vfx_true_peak_workspace_bytes(B, n, R, ops.true_peak_bank(dev, R)[1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--true-peak", action="store_true", help="time the true-peak legs instead (DESIGN.md 3.11)")
+    ap.add_argument("--passes", type=int, default=3, help="--true-peak: passes of --reps alternating repetitions")
     args = ap.parse_args(argv)
+    if args.true_peak:
+        run_true_peak(32, 10.0, args.reps, args.passes)
+        run_true_peak(1, 1800.0, args.reps, args.passes)
+        return
     run(32, 10.0, args.reps)
     run(1, 1800.0, args.reps)
 

@@ -24,6 +24,8 @@ Differences, all deliberate:
     and converted on the MI355X instead of in the host's decode workers (folder mode: forwarded to every ``--gpus`` rank);
   * ``--loudness LUFS`` (extension): every output is normalised on the device to that integrated loudness (ITU-R BS.1770-4),
     limited by the sample-peak ceiling ``--peak-ceiling DBFS`` (default -1); file and folder mode, every ``--mode``;
+    ``--true-peak`` with it: the ceiling is read as dBTP and the TRUE peak, measured between the samples, limits the gain
+    (alone it is an argument error; forwarded to every ``--gpus`` rank with the rest of the command line);
   * output formats are WAV and FLAC (``audio_io.FORMATS``) instead of whatever libsndfile offers;
   * folder mode isolates faults per FILE: an unreadable / truncated / too short input or a row the device refuses costs that
     file only -- it is listed on stderr with its reason, every other file is written, the exit status is 2 (all ranks of a
@@ -74,7 +76,7 @@ def mode_outfile(outfile, mode, append_mode):
 
 
 def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
-              resample_on_device=False, loudness=None, peak_ceiling=-1.0):
+              resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
@@ -86,12 +88,24 @@ def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=Fals
         kw["resample_on_device"] = True
     if loudness is not None:
         kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+        if true_peak:
+            kw["true_peak"] = True
     voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, **kw)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 
+class _Parser(argparse.ArgumentParser):
+    """Flags that only mean something together are checked where the values are: an argument error, not a late exception."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.true_peak and ns.loudness is None:
+            self.error("--true-peak needs --loudness: it turns the ceiling of the loudness normalisation into a true-peak one")
+        return ns
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(prog="voicefixer_amd", description="VoiceFixer - restores degraded speech (MI355X path)")
+    parser = _Parser(prog="voicefixer_amd", description="VoiceFixer - restores degraded speech (MI355X path)")
     parser.add_argument("-i", "--infile", type=str, default="", help="An input file to be processed by VoiceFixer.")
     parser.add_argument("-o", "--outfile", type=str, default="outfile.wav", help="An output file to store the result.")
     parser.add_argument("-ifdr", "--infolder", type=str, default="",
@@ -130,6 +144,9 @@ def build_parser():
                              "in [-70, 0) LUFS, e.g. -23 (EBU R128) or -16 (podcasts)")
     parser.add_argument("--peak-ceiling", type=_dbfs, default=-1.0, metavar="DBFS",
                         help="(extension) sample-peak ceiling of --loudness, in [-20, 0] dBFS (default -1)")
+    parser.add_argument("--true-peak", default=False, action="store_true",
+                        help="(extension) with --loudness: read --peak-ceiling as dBTP and limit the gain by the TRUE peak, measured "
+                             "on the device between the samples (EBU R 128's ceiling)")
     return parser
 
 
@@ -261,7 +278,7 @@ def main(argv=None):
         for m in modes:
             writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
                       output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device,
-                      loudness=args.loudness, peak_ceiling=args.peak_ceiling)
+                      loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -277,7 +294,7 @@ def main(argv=None):
                                           skip_existing=args.skip_existing, io_threads=args.io_threads or None,
                                           seed=args.seed, output_sample_rate=args.output_sample_rate,
                                           resample_on_device=args.resample_on_device, loudness=args.loudness,
-                                          peak_ceiling=args.peak_ceiling)
+                                          peak_ceiling=args.peak_ceiling, **({"true_peak": True} if args.true_peak else {}))
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

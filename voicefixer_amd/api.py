@@ -165,25 +165,76 @@ def convert_output(full, lens, rate_out):
     return out, new
 
 
-def apply_loudness(full, lens, rate, target, peak_ceiling=-1.0):
+def apply_loudness(full, lens, rate, target, peak_ceiling=-1.0, true_peak=False):
     """Loudness normalisation of device rows (ops.loudness_rows, BS.1770-4 integrated loudness): row r of ``full`` holds
     lens[r] samples at ``rate``; each is scaled by float32(g), g = min(10^((target - L)/20), 10^(peak_ceiling/20) / peak)
     (a SAMPLE-peak ceiling; g = 1 when L = -inf: silence or under 400 ms).  Returns (rows, device float64 (B, 3) of
-    {L before, g, peak}); ``target`` None returns (full, None) and launches nothing."""
+    {L before, g, peak}); ``target`` None returns (full, None) and launches nothing.
+    ``true_peak=True``: ``peak_ceiling`` is read as dBTP -- the gain is limited by the TRUE peak (loudness.py) -- and the
+    result is (B, 4) of {L before, g, sample peak, true peak}."""
     from . import loudness, ops
     target, peak_ceiling = loudness.check_target(target), loudness.check_ceiling(peak_ceiling)
+    true_peak = loudness.check_true_peak(true_peak)
     if target is None:
         return full, None
     x = full if full.stride(-1) == 1 else full.contiguous()
     n_rows = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(x.device, non_blocking=True)
     out = torch.empty_like(x)
-    res = ops.loudness_rows(x, n_rows, rate, target, peak_ceiling, out=out)
+    if true_peak:
+        res = ops.loudness_rows(x, n_rows, rate, target, peak_ceiling, out=out, true_peak=True)
+    else:
+        res = ops.loudness_rows(x, n_rows, rate, target, peak_ceiling, out=out)
     return out, res
 
 
-def _check_loudness(loudness_target, peak_ceiling):
+def _check_loudness(loudness_target, peak_ceiling, true_peak=False):
     from . import loudness
+    loudness.check_true_peak(true_peak)
     return loudness.check_target(loudness_target), loudness.check_ceiling(peak_ceiling)
+
+
+def _stage_rows(wav):
+    """One array or a list of them -> (single, padded device rows (B, >= 1), device int32 lengths, lengths)."""
+    single = not isinstance(wav, (list, tuple))
+    wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in ([wav] if single else wav)]
+    if not wavs:
+        return single, None, None, []
+    dev = _device()
+    lens = [len(w) for w in wavs]
+    host = np.zeros((len(wavs), max(max(lens), 1)), np.float32)
+    for r, w in enumerate(wavs):
+        host[r, :len(w)] = w
+    return single, torch.from_numpy(host).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev), lens
+
+
+def measure_true_peak(wav, sample_rate=44100):
+    """True peak in dBTP (after ITU-R BS.1770-4 Annex 2; loudness.py has the definition) of a float32 array (N,) -- or of
+    every array of a list, in one device call -- measured on the device.  -inf: an all-zero or empty array."""
+    from . import loudness, ops
+    loudness.plan(sample_rate)
+    single, x, n_rows, lens = _stage_rows(wav)
+    if not lens:
+        return []
+    res = ops.loudness_rows(x, n_rows, sample_rate, true_peak=True).cpu().numpy()
+    out = [loudness.to_db(v) for v in res[:, 3]]
+    return out[0] if single else out
+
+
+def loudness_report(wav, sample_rate=44100):
+    """EBU R 128 figures of a float32 array (N,) -- or of every array of a list, in one device call -- all computed on the
+    device (ops.loudness_report_rows; loudness.py has the definitions): a dict (a list of dicts) with ``integrated``
+    (LUFS), ``loudness_range`` (LU), ``max_momentary`` and ``max_short_term`` (LUFS), ``sample_peak`` (dBFS) and
+    ``true_peak`` (dBTP).  -inf: nothing to measure (silence, too short a row); the range is then 0.0."""
+    from . import loudness, ops
+    loudness.plan(sample_rate)
+    single, x, n_rows, lens = _stage_rows(wav)
+    if not lens:
+        return []
+    res = ops.loudness_report_rows(x, n_rows, sample_rate).cpu().numpy()
+    out = [{"integrated": float(v[0]), "loudness_range": float(v[1]), "max_momentary": float(v[2]),
+            "max_short_term": float(v[3]), "sample_peak": loudness.to_db(v[4]), "true_peak": loudness.to_db(v[5])}
+           for v in res]
+    return out[0] if single else out
 
 
 def measure_loudness(wav, sample_rate=44100):
@@ -401,7 +452,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
-                      output_sample_rate=None, loudness=None, peak_ceiling=-1.0):
+                      output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
         ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
@@ -413,10 +464,12 @@ class VoiceFixer(nn.Module):
         (< 28224 samples: a short file, or the short tail of a long one) raises ValueError, as the reference does.
         ``loudness`` (extension, LUFS in [-70, 0)): the whole output, after the peak rule and any output rate conversion, is
         normalised on the device to that integrated loudness (ITU-R BS.1770-4), limited by the SAMPLE-peak ceiling
-        ``peak_ceiling`` (dBFS in [-20, 0]): one fp32 gain for the file (``apply_loudness``).  None (default): unchanged."""
+        ``peak_ceiling`` (dBFS in [-20, 0]): one fp32 gain for the file (``apply_loudness``).  None (default): unchanged.
+        ``true_peak=True`` (extension): ``peak_ceiling`` is read as dBTP, the gain is limited by the file's TRUE peak at the
+        output rate (measured on the device between the samples: loudness.py, EBU R 128's ceiling)."""
         self._check_mode(mode, seed)
         rate_in, rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
-        loud = _check_loudness(loudness, peak_ceiling)
+        loud = _check_loudness(loudness, peak_ceiling, true_peak)
         pipe = self._get_pipe()
         wav = np.asarray(wav_10k, dtype=np.float32)
         n = wav.shape[0]
@@ -459,7 +512,7 @@ class VoiceFixer(nn.Module):
                 y, (m,) = convert_output(out, [out.shape[-1]], rate_out)
                 out = y[:, :m]
             if loud[0] is not None:
-                out, _ = apply_loudness(out, [out.shape[-1]], rate_out, *loud)
+                out, _ = apply_loudness(out, [out.shape[-1]], rate_out, *loud, true_peak=true_peak)
             return out.cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
@@ -489,7 +542,7 @@ class VoiceFixer(nn.Module):
         return self._stream_pool[:max(1, int(streams))]
 
     def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None, loudness=None,
-                     peak_ceiling=-1.0):
+                     peak_ceiling=-1.0, true_peak=False):
         """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates than
         44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) (loudness normalisation,) D2H of the result
         -- and of the per-row loudness results -- into pinned tensors, an event.  Nothing here waits for the device."""
@@ -554,7 +607,7 @@ class VoiceFixer(nn.Module):
                 full, lens_out = convert_output(full, lens_out, rate_out)
             loud_host = None
             if loudness is not None:
-                full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling)
+                full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling, true_peak)
                 loud_host = torch.empty(tuple(res.shape), dtype=torch.float64, pin_memory=True)
                 loud_host.copy_(res, non_blocking=True)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
@@ -565,7 +618,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
-                        loudness=None, peak_ceiling=-1.0):
+                        loudness=None, peak_ceiling=-1.0, true_peak=False):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -582,13 +635,14 @@ class VoiceFixer(nn.Module):
         device (``convert_output``) before they cross to the host, ``lens_out`` counts samples at that rate.
         ``loudness`` / ``peak_ceiling``: every row is normalised on the device (restore_inmem) before it crosses, and the
         generator yields ``(tag, out_host, lens_out, loud_host)``, ``loud_host`` a pinned float64 (B, 3) of {LUFS before,
-        gain, sample peak} per row, copied with the batch.
+        gain, sample peak} per row, copied with the batch.  ``true_peak=True``: the ceiling is a true-peak one (restore_inmem)
+        and ``loud_host`` is (B, 4): {LUFS before, gain, sample peak, true peak}.
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
-        _check_loudness(loudness, peak_ceiling)
+        _check_loudness(loudness, peak_ceiling, true_peak)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -620,7 +674,7 @@ class VoiceFixer(nn.Module):
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
                             inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed,
-                                                            output_sample_rate, loudness, peak_ceiling)
+                                                            output_sample_rate, loudness, peak_ceiling, true_peak)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
@@ -629,7 +683,7 @@ class VoiceFixer(nn.Module):
 
             for item in batches:
                 inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed,
-                                                  output_sample_rate, loudness, peak_ceiling))
+                                                  output_sample_rate, loudness, peak_ceiling, true_peak))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -650,7 +704,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
-                      sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0):
+                      sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -666,10 +720,10 @@ class VoiceFixer(nn.Module):
         every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it.
         ``sample_rate`` (extension): the rate of the inputs, one int or a list with one rate per wav; rows are staged at
         their own rates and converted on the device (one launch per distinct rate pair and batch), the batches are
-        planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``: as ``restore_inmem`` (each
-        file is measured on its own row, whatever else its batch holds)."""
+        planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``, ``true_peak``: as
+        ``restore_inmem`` (each file is measured on its own row, whatever else its batch holds)."""
         self._check_mode(mode, seed)
-        _check_loudness(loudness, peak_ceiling)
+        _check_loudness(loudness, peak_ceiling, true_peak)
         rates = _row_rates(sample_rate, len(wavs))
         _output_rate(output_sample_rate)
         native = all(r == 44100 for r in rates)
@@ -694,6 +748,8 @@ class VoiceFixer(nn.Module):
         kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
         if loudness is not None:
             kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+            if true_peak:
+                kw["true_peak"] = True
         for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
             ov = out_host.numpy()
             for r, k in enumerate(idx):
@@ -703,7 +759,7 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_stream(self, wav, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=8, mode=0,
                        your_vocoder_func=None, on_chunk=None, sample_rate=44100, output_sample_rate=None, loudness=None,
-                       peak_ceiling=-1.0):
+                       peak_ceiling=-1.0, true_peak=False):
         """Long-form restoration with overlap-add (BASELINE config 5; NOT in the reference, whose 30 s segments
         are hard-cut -- ``restore_inmem`` keeps that behaviour): chunks of ``chunk_seconds`` every
         ``chunk_seconds - overlap_seconds``, each restored independently (equal-length chunks are batched),
@@ -717,10 +773,10 @@ class VoiceFixer(nn.Module):
         ``sample_rate`` (extension): the rate of ``wav``; another rate than 44.1 kHz is converted once, up front, on the
         device, and the chunks are cut from the converted waveform.  ``output_sample_rate`` other than 44.1 kHz raises
         NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries; so
-        does ``loudness``: the stretches leave before a whole-file measurement exists."""
+        does ``loudness``, and ``true_peak=True`` with it: the stretches leave before a whole-file measurement exists."""
         self._check_mode(mode)
         rate_in = _check_rate(sample_rate)
-        if _check_loudness(loudness, peak_ceiling)[0] is not None:
+        if _check_loudness(loudness, peak_ceiling, true_peak)[0] is not None or true_peak:
             raise NotImplementedError("restore_stream: loudness normalisation is not built -- the on_chunk stretches leave before "
                                       "the whole file has been measured; use restore_inmem or restore_folder")
         if _output_rate(output_sample_rate) != 44100:
@@ -774,7 +830,7 @@ class VoiceFixer(nn.Module):
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
     def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None,
-                                  loudness=None, peak_ceiling=-1.0):
+                                  loudness=None, peak_ceiling=-1.0, true_peak=False):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
@@ -786,6 +842,8 @@ class VoiceFixer(nn.Module):
             kw["output_sample_rate"] = output_sample_rate
         if loudness is not None:
             kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+            if true_peak:
+                kw["true_peak"] = True
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -838,7 +896,7 @@ class VoiceFixer(nn.Module):
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
                        skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False, loudness=None,
-                       peak_ceiling=-1.0):
+                       peak_ceiling=-1.0, true_peak=False):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -874,7 +932,9 @@ class VoiceFixer(nn.Module):
         field) -- a file whose reduced rate ratio has max(up, down) > audio_io.DEVICE_MAX_RATIO is still resampled on the
         host.  ``output_sample_rate``: outputs are converted on the device (``convert_output``) and written at that rate.
         ``loudness`` / ``peak_ceiling``: every output is normalised on the device (restore_inmem) before it is written;
-        ``stats["loudness"]`` lists ``(output name, LUFS before, gain in dB)`` of the files written.
+        ``stats["loudness"]`` lists ``(output name, LUFS before, gain in dB)`` of the files written.  ``true_peak=True``:
+        the ceiling is a true-peak one (restore_inmem) and ``stats["true_peak"]`` lists ``(output name, dBTP before, dBTP
+        after)``.
         Returns the list of file names THIS rank wrote."""
         import threading
         import time
@@ -883,7 +943,7 @@ class VoiceFixer(nn.Module):
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
         rate_out = _output_rate(output_sample_rate)
-        _check_loudness(loudness, peak_ceiling)
+        _check_loudness(loudness, peak_ceiling, true_peak)
         rank, world = vdist.rank_world(rank, world)
         if io_threads is None:
             io_threads = vdist.default_io_threads(world)
@@ -974,6 +1034,7 @@ class VoiceFixer(nn.Module):
 
         written, skipped, done = [], [], []
         loud_rows = {}         # index -> (LUFS before, gain in dB)
+        tp_rows = {}           # index -> (dBTP before, dBTP after)
         with ThreadPoolExecutor(max_workers=io_threads) as pool:
             scanned = list(pool.map(scan, range(len(files))))
             # every rank must deal from the SAME list: inside an initialised process group of this world size the scans are
@@ -1073,6 +1134,8 @@ class VoiceFixer(nn.Module):
                     kw["output_sample_rate"] = output_sample_rate
                 if loudness is not None:
                     kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
+                    if true_peak:
+                        kw["true_peak"] = True
                 for idx, out_host, lens_out, *extra in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func,
                                                                                        streams, mode, **kw):
                     ov = out_host.numpy()
@@ -1080,6 +1143,9 @@ class VoiceFixer(nn.Module):
                         lv = extra[0].numpy()
                         for r, i in enumerate(idx):
                             loud_rows[i] = (float(lv[r, 0]), 20.0 * float(np.log10(lv[r, 1])))
+                            if lv.shape[1] == 4:
+                                before = 20.0 * float(np.log10(lv[r, 3])) if lv[r, 3] > 0 else -float("inf")
+                                tp_rows[i] = (before, before + loud_rows[i][1])
                     writes.append([(i, pool.submit(encode_from, ov[r:r + 1, :lens_out[r]], i)) for r, i in enumerate(idx)])
                     drain(ahead + 2)       # bounded backlog: pinned results do not pile up behind a slow disk
             except BatchSourceError as e:  # the source died: every batch it had handed over has been finished and is written below
@@ -1101,6 +1167,8 @@ class VoiceFixer(nn.Module):
                          failed=sorted((files[i], why) for i, why in failed), skipped=sorted(skipped),
                          truncated=sorted((files[i], n, m) for i, n, m in truncated if i in real_len or i in mine),
                          loudness=sorted((names[i],) + loud_rows[i] for i in done if i in loud_rows))
+            if true_peak and loudness is not None:
+                stats["true_peak"] = sorted((names[i],) + tp_rows[i] for i in done if i in tp_rows)
         return sorted(written)
 
     @staticmethod
@@ -1108,22 +1176,25 @@ class VoiceFixer(nn.Module):
         return torch.cuda.is_available()
 
     def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
-                resample_on_device=False, loudness=None, peak_ceiling=-1.0):
+                resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False):
         """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
         rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
         resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device);
-        ``loudness`` / ``peak_ceiling``: as ``restore_inmem``."""
+        ``loudness`` / ``peak_ceiling`` / ``true_peak``: as ``restore_inmem``."""
         rate_out = _output_rate(output_sample_rate)
-        _check_loudness(loudness, peak_ceiling)
+        _check_loudness(loudness, peak_ceiling, true_peak)
+        kw = {"true_peak": True} if true_peak else {}
         if resample_on_device:
             x, sr = audio_io.load_wav_native(input)
             if sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) > audio_io.DEVICE_MAX_RATIO:
                 x, sr = audio_io.resample_hq(x, sr, 44100), 44100
             out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
                                             your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
-                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling)
+                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
+                                            **kw)
         else:
             wav_10k = self._load_wav(input, sample_rate=44100)
             out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed,
-                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling)
+                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
+                                            **kw)
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out)

@@ -1,5 +1,5 @@
 // vfx_loudness.hip -- integrated loudness (ITU-R BS.1770-4, one channel) of B rows and the gain that normalises it
-// (vfx_loudness_rows_f32).  Definition, chunk scan and measured cost: DESIGN.md 3.10.
+// (vfx_loudness_rows_f32), its true peak and its EBU R 128 report.  Definition, chunk scan and measured cost: DESIGN.md 3.10, 3.11.
 //
 //   K-weighting: two cascaded biquads (shelf, then high-pass), transposed direct form II, fp32.  Quarter q = sum of the
 //   squared K-weighted samples [q*hop, (q+1)*hop) (fp64); block j = quarters j..j+3, z_j = sum / (4 hop),
@@ -25,6 +25,11 @@
 //      (fixed-order LDS reductions: bit-reproducible), L, the row peak, the gain -> result[r] = {L, g, peak}.
 //   4. lk_apply_kernel: out = float(g) * x over each row's own length (float4 where aligned); not launched to measure only.
 // Nothing is written past a row's length; at most 4 launches per call, none of them waits for the host.
+//
+// vfx_loudness_tp_rows_f32 (a TRUE-peak ceiling) adds lk_truepeak_kernel before the gate -- the row
+// oversampled R times and reduced to max |y| per tile without being stored -- and the gate kernel's RS = 4 form folds those
+// partials: result[r] = {L, g, P, TP}, g limited by TP.  vfx_loudness_report_rows_f32 adds lk_report_kernel behind the gate:
+// maximum momentary / short-term loudness and the loudness range from the same quarter sums.
 #include <cmath>
 #include "vfx_common.h"
 
@@ -261,9 +266,119 @@ __device__ __forceinline__ void lk_reduce(double& s, long long& cnt, double* rs,
     __syncthreads();
 }
 
+// ---- true peak ------------------------------------------------------------------------------------------
+// The polyphase sum of vfx_resample_rows_f32 at down = 1, reduced to max |y| without ever writing y:
+//     y[m] = sum_i bank[p][i] * x[K - J + 1 + i],   t = c + m,  K = t / R,  p = t mod R,   m in [0, R n)
+// A workgroup owns TP_TILE consecutive K (all R phases of each), lane l the TP_KPL of them from K0 + TP_KPL*l.  The tile of x
+// with its halo (x[K0 - Jp + 1 .. K0 + TP_TILE), zero outside [0, n)) and the bank, front-padded with zero taps to Jp (a
+// multiple of 8) per phase, are staged in LDS once; the tiles start at Kal + b*TP_TILE with Kal + 1 a multiple of 4, so
+// every staged float4 is an aligned one in x.  A lane slides a 12-sample register window over its taps, 8 at a time:
+// three 16-byte LDS reads of x (one kept from the step before) and 2 R broadcast reads of the bank feed 32 R FMAs.  Every
+// output is two chains (taps 8b..8b+3 / 8b+4..8b+7, ascending) added once -- the same order whatever B, tile or row.
+#define TP_T 256
+#define TP_KPL 4
+#define TP_TILE (TP_T * TP_KPL)
+#define TP_JMAX 2048
+
+struct lk_tp {
+    const float* part;            // [B][ntiles]  max |y| of every tile
+    long long ntiles, Kal;
+    int c, R;
+};
+
+static inline long long tp_kal(int c, int R) { return (((long long)(c / R) + 1) & ~3LL) - 1; }
+static inline long long tp_ntiles(long long n_max) { return (n_max + 4) / TP_TILE + 1; }     // K takes <= n + 4 values from Kal
+static inline int tp_jp(int J) { return (J + 7) / 8 * 8; }
+
+// tiles that hold outputs of a row of n samples
+__device__ __forceinline__ long long tp_tiles(long long n, int R, int c, long long Kal) {
+    return n > 0 ? (((long long)c + (long long)R * n - 1) / R - Kal) / TP_TILE + 1 : 0;
+}
+
+template <int R, bool VEC>
+__global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restrict__ x, long long x_stride,
+                                                           const int* __restrict__ n_rows, long long n_max,
+                                                           const float* __restrict__ bank, int J, int Jp, float* part,
+                                                           lk_tp t) {
+    extern __shared__ float4 tp_lds[];
+    float* xs = reinterpret_cast<float*>(tp_lds);         // [TP_TILE + Jp]
+    float* bk = xs + TP_TILE + Jp;                        // [R][Jp]
+    const int r = blockIdx.y, l = threadIdx.x;
+    long long n = n_rows[r];
+    n = n < 0 ? 0 : (n > n_max ? n_max : n);
+    if ((long long)blockIdx.x >= tp_tiles(n, R, t.c, t.Kal)) return;         // (uniform over the workgroup)
+    const long long t_end = (long long)t.c + (long long)R * n;
+    const long long K0 = t.Kal + (long long)blockIdx.x * TP_TILE;
+    const float* xr = x + (long long)r * x_stride;
+    for (int i = l; i < R * Jp; i += TP_T) {
+        const int p = i / Jp, ii = i - p * Jp - (Jp - J);
+        bk[i] = ii >= 0 ? bank[p * J + ii] : 0.f;
+    }
+    const long long g0 = K0 - Jp + 1;                     // (a multiple of 4)
+    for (int f = l; f < (TP_TILE + Jp) / 4; f += TP_T) {
+        const long long idx = g0 + 4 * f;
+        float4 u;
+        if (VEC && idx >= 0 && idx + 3 < n) {
+            u = *reinterpret_cast<const float4*>(xr + idx);
+        } else {
+            u.x = idx >= 0 && idx < n ? xr[idx] : 0.f;
+            u.y = idx + 1 >= 0 && idx + 1 < n ? xr[idx + 1] : 0.f;
+            u.z = idx + 2 >= 0 && idx + 2 < n ? xr[idx + 2] : 0.f;
+            u.w = idx + 3 >= 0 && idx + 3 < n ? xr[idx + 3] : 0.f;
+        }
+        tp_lds[f] = u;
+    }
+    __syncthreads();
+    const float4* xs4 = tp_lds;
+    const float4* bk4 = reinterpret_cast<const float4*>(bk);
+    const int nb = Jp / 4;
+    float aa[R][TP_KPL], ab[R][TP_KPL];
+#pragma unroll
+    for (int p = 0; p < R; ++p)
+#pragma unroll
+        for (int k = 0; k < TP_KPL; ++k) { aa[p][k] = 0.f; ab[p][k] = 0.f; }
+    float4 a = xs4[l];
+    for (int ib = 0; ib < nb; ib += 2) {
+        const float4 b = xs4[l + ib + 1], d = xs4[l + ib + 2];
+        const float w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int p = 0; p < R; ++p) {
+            const float4 u = bk4[p * nb + ib], v = bk4[p * nb + ib + 1];
+            const float tu[4] = {u.x, u.y, u.z, u.w}, tv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int k = 0; k < TP_KPL; ++k) {
+                    aa[p][k] = fmaf(tu[e], w[k + e], aa[p][k]);
+                    ab[p][k] = fmaf(tv[e], w[4 + k + e], ab[p][k]);
+                }
+        }
+        a = d;
+    }
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < TP_KPL; ++k)
+#pragma unroll
+        for (int p = 0; p < R; ++p) {
+            const long long tt = (K0 + TP_KPL * l + k) * R + p;
+            if (tt >= t.c && tt < t_end) m = fmaxf(m, fabsf(aa[p][k] + ab[p][k]));
+        }
+    __syncthreads();
+    xs[l] = m;
+    __syncthreads();
+    for (int h = TP_T / 2; h > 0; h >>= 1) {
+        if (l < h) xs[l] = fmaxf(xs[l], xs[l + h]);
+        __syncthreads();
+    }
+    if (l == 0) part[(long long)r * t.ntiles + blockIdx.x] = xs[0];
+}
+
+// RS = 3: result[r] = {L, g, P}, the gain limited by the sample peak P.  RS = 4: result[r] = {L, g, P, TP}, TP = max(P, the
+// row's true-peak partials of lk_truepeak_kernel), the gain limited by TP.
+template <int RS>
 __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n_rows, long long n_max, int S, int hop,
                                                        double target, double ceiling_db, double* __restrict__ result,
-                                                       lk_ws w) {
+                                                       lk_ws w, lk_tp t) {
     __shared__ double rs[LK_T];
     __shared__ long long rc[LK_T];
     __shared__ float rp[LK_T];
@@ -280,6 +395,22 @@ __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n
         __syncthreads();
     }
     const double peak = rp[0];
+    double tpk = peak;
+    if (RS == 4) {
+        float m = 0.f;
+        const long long nt = t.R > 1 ? tp_tiles(n, t.R, t.c, t.Kal) : 0;
+        const float* __restrict__ pr = t.part + (long long)r * t.ntiles;
+#pragma unroll 8
+        for (long long j = c; j < nt; j += LK_T) m = fmaxf(m, pr[j]);     // (8 loads in flight: one workgroup, ~300 per lane for 30 min)
+        __syncthreads();
+        rp[c] = m;
+        __syncthreads();
+        for (int h = LK_T / 2; h > 0; h >>= 1) {
+            if (c < h) rp[c] = fmaxf(rp[c], rp[c + h]);
+            __syncthreads();
+        }
+        tpk = fmax(peak, (double)rp[0]);
+    }
     const long long nq = n / hop;
     const long long nblk = nq > 3 ? nq - 3 : 0;
     const double2* parts = w.parts + (long long)r * w.nchunks;
@@ -311,16 +442,129 @@ __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n
         double g = 1.0;
         if (isfinite(L) && !isnan(target)) {
             g = pow(10.0, (target - L) / 20.0);
-            const double lim = pow(10.0, ceiling_db / 20.0) / peak;
+            const double lim = pow(10.0, ceiling_db / 20.0) / (RS == 4 ? tpk : peak);
             if (lim < g) g = lim;
         }
-        result[3 * r] = L;
-        result[3 * r + 1] = g;
-        result[3 * r + 2] = peak;
+        result[RS * r] = L;
+        result[RS * r + 1] = g;
+        result[RS * r + 2] = peak;
+        if (RS == 4) result[RS * r + 3] = tpk;
     }
 }
 
-template <bool VEC>
+// ---- loudness report (EBU Tech 3341 / 3342) -----------------------------------------------------------------
+#define LK_ST 30                  // quarters of one 3 s short-term block
+
+// number of keys below `cand` (every lane gets it)
+__device__ __forceinline__ long long lk_count_below(const unsigned long long* __restrict__ key, long long nst,
+                                                    unsigned long long cand, long long* rc) {
+    const int c = threadIdx.x;
+    long long cnt = 0;
+    for (long long j = c; j < nst; j += LK_T) cnt += key[j] < cand;
+    rc[c] = cnt;
+    __syncthreads();
+    for (int h = LK_T / 2; h > 0; h >>= 1) {
+        if (c < h) rc[c] += rc[c + h];
+        __syncthreads();
+    }
+    cnt = rc[0];
+    __syncthreads();
+    return cnt;
+}
+
+// the k-th smallest key (k from 0), bit by bit from the top: exact, and the same whatever the order of the keys
+__device__ __forceinline__ unsigned long long lk_select(const unsigned long long* __restrict__ key, long long nst, long long k,
+                                                        long long* rc) {
+    unsigned long long pre = 0;
+    for (int b = 63; b >= 0; --b) {
+        const unsigned long long cand = pre | (1ULL << b);
+        if (lk_count_below(key, nst, cand, rc) <= k) pre = cand;
+    }
+    return pre;
+}
+
+// One workgroup per row, after lk_gate_kernel<4>: report[r] = {L, LRA, max momentary, max short-term, P, TP}.
+// qs [B][nqmax]: the row's quarter sums; st [B][nqmax]: its short-term energies, then their bit patterns as sort keys
+// (positive doubles order as their bits do; a block below a gate gets the key ~0 and is never counted).
+__global__ __launch_bounds__(LK_T) void lk_report_kernel(const int* __restrict__ n_rows, long long n_max, int S, int hop,
+                                                         const double* __restrict__ res4, double* __restrict__ report,
+                                                         double* __restrict__ qs, double* __restrict__ st,
+                                                         long long nqmax, lk_ws w) {
+    __shared__ double rs[LK_T];
+    __shared__ long long rc[LK_T];
+    const int r = blockIdx.x, c = threadIdx.x;
+    long long n = n_rows[r];
+    n = n < 0 ? 0 : (n > n_max ? n_max : n);
+    const long long nq = n / hop;
+    const long long nblk = nq > 3 ? nq - 3 : 0;
+    const long long nst = nq >= LK_ST ? nq - LK_ST + 1 : 0;
+    const double2* parts = w.parts + (long long)r * w.nchunks;
+    const double* z = w.z + (long long)r * w.nblk;
+    double* q = qs + (long long)r * nqmax;
+    double* e = st + (long long)r * nqmax;
+    unsigned long long* key = reinterpret_cast<unsigned long long*>(e);
+    double zm = -1.0;                                     // (max is exact: any order gives the same bits)
+    for (long long j = c; j < nblk; j += LK_T) zm = fmax(zm, z[j]);
+    for (long long j = c; j < nq; j += LK_T) q[j] = lk_quarter(parts, j, hop, S);
+    __syncthreads();                                      // (q is read across lanes below)
+    const double inv = 1.0 / ((double)LK_ST * hop);
+    double em = -1.0, s1 = 0.0;
+    long long c1 = 0;
+    for (long long j = c; j < nst; j += LK_T) {
+        double a = 0.0;
+        for (int i = 0; i < LK_ST; ++i) a += q[j + i];    // (fixed order)
+        a *= inv;
+        e[j] = a;
+        em = fmax(em, a);
+        if (-0.691 + 10.0 * log10(a) > -70.0) { s1 += a; ++c1; }
+    }
+    rs[c] = zm;
+    __syncthreads();
+    for (int h = LK_T / 2; h > 0; h >>= 1) {
+        if (c < h) rs[c] = fmax(rs[c], rs[c + h]);
+        __syncthreads();
+    }
+    zm = rs[0];
+    __syncthreads();
+    rs[c] = em;
+    __syncthreads();
+    for (int h = LK_T / 2; h > 0; h >>= 1) {
+        if (c < h) rs[c] = fmax(rs[c], rs[c + h]);
+        __syncthreads();
+    }
+    em = rs[0];
+    __syncthreads();
+    lk_reduce(s1, c1, rs, rc);
+    double lra = 0.0;
+    if (c1 > 0) {
+        const double gr = -0.691 + 10.0 * log10(s1 / (double)c1) - 20.0;
+        long long c2 = 0;
+        double zero = 0.0;
+        for (long long j = c; j < nst; j += LK_T) {      // (each lane rewrites only the entries it wrote itself)
+            const double a = e[j];
+            const double lj = -0.691 + 10.0 * log10(a);
+            const bool keep = lj > -70.0 && lj > gr;
+            key[j] = keep ? (unsigned long long)__double_as_longlong(a) : ~0ULL;
+            c2 += keep;
+        }
+        lk_reduce(zero, c2, rs, rc);                      // (also orders the key writes before the counting reads)
+        if (c2 > 0) {
+            const double lo = __longlong_as_double((long long)lk_select(key, nst, (c2 - 1 + 5) / 10, rc));
+            const double hi = __longlong_as_double((long long)lk_select(key, nst, ((c2 - 1) * 95 + 50) / 100, rc));
+            lra = (-0.691 + 10.0 * log10(hi)) - (-0.691 + 10.0 * log10(lo));
+        }
+    }
+    if (c == 0) {
+        report[6 * r] = res4[4 * r];
+        report[6 * r + 1] = lra;
+        report[6 * r + 2] = zm >= 0.0 ? -0.691 + 10.0 * log10(zm) : -INFINITY;
+        report[6 * r + 3] = em >= 0.0 ? -0.691 + 10.0 * log10(em) : -INFINITY;
+        report[6 * r + 4] = res4[4 * r + 2];
+        report[6 * r + 5] = res4[4 * r + 3];
+    }
+}
+
+template <bool VEC, int RS>
 __global__ __launch_bounds__(LK_T) void lk_apply_kernel(const float* x, long long x_stride,   // (out may alias x)
                                                         const int* __restrict__ n_rows, long long n_max,
                                                         const double* __restrict__ result, float* out,
@@ -328,7 +572,7 @@ __global__ __launch_bounds__(LK_T) void lk_apply_kernel(const float* x, long lon
     const int r = blockIdx.y;
     long long n = n_rows[r];
     n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    const float g = (float)result[3 * r + 1];
+    const float g = (float)result[RS * r + 1];
     const float* xr = x + (long long)r * x_stride;
     float* yr = out + (long long)r * out_stride;
     const long long step = (long long)gridDim.x * LK_T;
@@ -353,10 +597,42 @@ extern "C" size_t vfx_loudness_workspace_bytes(int B, int64_t n_max, int hop, in
     return total;
 }
 
-extern "C" int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
-                                     const double* coef, const double* mpow, int S, int hop, int lookback, double target,
-                                     double ceiling_db, float* out, int64_t out_stride, double* result, void* ws,
-                                     size_t ws_bytes, vfx_stream_t stream) {
+// Extra workspace behind lk_layout's: the true-peak partials, then (report only) the {L, g, P, TP} rows, the quarter sums and
+// the short-term energies.
+struct lk_ext {
+    float* part;
+    double* res4;
+    double* qs;
+    double* st;
+    long long ntiles, nqmax;
+};
+
+static void lk_ext_layout(int B, long long n_max, int hop, bool report, size_t* total, lk_ext* e, char* base) {
+    const long long ntiles = tp_ntiles(n_max);
+    const long long nqmax = hop > 0 && n_max / hop > 0 ? n_max / hop : 1;
+    size_t off = 0;
+    const size_t o_part = off; off += lk_round((size_t)B * ntiles * sizeof(float));
+    size_t o_res = 0, o_q = 0, o_st = 0;
+    if (report) {
+        o_res = off; off += lk_round((size_t)B * 4 * sizeof(double));
+        o_q = off;   off += lk_round((size_t)B * nqmax * sizeof(double));
+        o_st = off;  off += lk_round((size_t)B * nqmax * sizeof(double));
+    }
+    *total = off;
+    if (e) {
+        e->part = (float*)(base + o_part);
+        e->res4 = report ? (double*)(base + o_res) : nullptr;
+        e->qs = report ? (double*)(base + o_q) : nullptr;
+        e->st = report ? (double*)(base + o_st) : nullptr;
+        e->ntiles = ntiles;
+        e->nqmax = nqmax;
+    }
+}
+
+// mode 0: vfx_loudness_rows_f32 ({L, g, P});  1: with the true peak ({L, g, P, TP});  2: the report (measure only)
+static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max, const double* coef,
+                  const double* mpow, int S, int hop, int lookback, double target, double ceiling_db, const float* bank, int J,
+                  int R, int c, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream) {
     if (!x || !n_rows || !coef || !mpow || !result || !ws || B <= 0 || B > 65535 || n_max < 0 || n_max > INT32_MAX)
         return VFX_EINVAL;
     if (S < LK_P || S % LK_P != 0 || S > 8192 || hop < S || lookback < 1 || lookback > LK_T - 1) return VFX_EINVAL;
@@ -365,10 +641,14 @@ extern "C" int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int
     if (apply && (!out || out_stride < (B > 1 ? n_max : 0))) return VFX_EINVAL;
     for (int i = 0; i < 10; ++i)
         if (!std::isfinite(coef[i])) return VFX_EINVAL;
-    size_t need = 0;
+    if (mode != 0 && (!bank || J < 1 || J > TP_JMAX || (R != 1 && R != 2 && R != 4) || c < 0 || (long long)c >= (long long)R * J))
+        return VFX_EINVAL;
+    size_t need = 0, more = 0;
     lk_ws w;
+    lk_ext e = {nullptr, nullptr, nullptr, nullptr, 0, 0};
     lk_layout(B, n_max, hop, S, &need, &w, (char*)ws);
-    if (ws_bytes < need || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
+    if (mode != 0) lk_ext_layout(B, n_max, hop, mode == 2, &more, &e, (char*)ws + need);
+    if (ws_bytes < need + more || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
     const lk_coef k = {(float)coef[0], (float)coef[1], (float)coef[2], (float)coef[3], (float)coef[4],
                        (float)coef[5], (float)coef[6], (float)coef[7], (float)coef[8], (float)coef[9]};
     hipStream_t s = (hipStream_t)stream;
@@ -384,20 +664,83 @@ extern "C" int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int
     else hipLaunchKernelGGL(lk_filter_kernel<false>, gs, dim3(LK_T), 0, s, x, (long long)x_stride, (const int*)n_rows,
                             (long long)n_max, k, mpow, S, hop, lookback, w);
     VFX_LAUNCHED();
-    hipLaunchKernelGGL(lk_gate_kernel, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows, (long long)n_max, S, hop,
-                       target, ceiling_db, result, w);
+    lk_tp t = {e.part, e.ntiles, 0, c, R};
+    if (mode != 0 && R > 1 && n_max > 0) {
+        t.Kal = tp_kal(c, R);
+        const int Jp = tp_jp(J);
+        const size_t lds = (size_t)(TP_TILE + Jp + R * Jp) * sizeof(float);
+        const dim3 gt((unsigned)e.ntiles, (unsigned)B);
+#define TP_LAUNCH(RR, VV) hipLaunchKernelGGL((lk_truepeak_kernel<RR, VV>), gt, dim3(TP_T), lds, s, x, (long long)x_stride, \
+                                             (const int*)n_rows, (long long)n_max, bank, J, Jp, e.part, t)
+        if (R == 4) { if (vx) TP_LAUNCH(4, true); else TP_LAUNCH(4, false); }
+        else { if (vx) TP_LAUNCH(2, true); else TP_LAUNCH(2, false); }
+#undef TP_LAUNCH
+        VFX_LAUNCHED();
+    } else {
+        t.R = 1;                                          // (no partials: TP = P)
+    }
+    if (mode == 0) hipLaunchKernelGGL(lk_gate_kernel<3>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
+                                      (long long)n_max, S, hop, target, ceiling_db, result, w, t);
+    else hipLaunchKernelGGL(lk_gate_kernel<4>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows, (long long)n_max, S,
+                            hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t);
     VFX_LAUNCHED();
+    if (mode == 2) {
+        hipLaunchKernelGGL(lk_report_kernel, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows, (long long)n_max, S, hop,
+                           (const double*)e.res4, result, e.qs, e.st, e.nqmax, w);
+        VFX_LAUNCHED();
+    }
     if (apply) {
         long long nbx = (n_max / 4 + LK_T - 1) / LK_T;
         nbx = nbx < 1 ? 1 : (nbx > 2048 ? 2048 : nbx);
         const bool vo = vx && vfx_aligned16(out) && out_stride % 4 == 0;
-        if (vo) hipLaunchKernelGGL(lk_apply_kernel<true>, dim3((unsigned)nbx, (unsigned)B), dim3(LK_T), 0, s, x,
-                                   (long long)x_stride, (const int*)n_rows, (long long)n_max, (const double*)result, out,
-                                   (long long)out_stride);
-        else hipLaunchKernelGGL(lk_apply_kernel<false>, dim3((unsigned)nbx, (unsigned)B), dim3(LK_T), 0, s, x,
-                                (long long)x_stride, (const int*)n_rows, (long long)n_max, (const double*)result, out,
-                                (long long)out_stride);
+        const dim3 ga((unsigned)nbx, (unsigned)B);
+#define AP_LAUNCH(VV, RS) hipLaunchKernelGGL((lk_apply_kernel<VV, RS>), ga, dim3(LK_T), 0, s, x, (long long)x_stride, \
+                                             (const int*)n_rows, (long long)n_max, (const double*)result, out, \
+                                             (long long)out_stride)
+        if (mode == 0) { if (vo) AP_LAUNCH(true, 3); else AP_LAUNCH(false, 3); }
+        else { if (vo) AP_LAUNCH(true, 4); else AP_LAUNCH(false, 4); }
+#undef AP_LAUNCH
         VFX_LAUNCHED();
     }
     return vfx_last_error();
+}
+
+extern "C" int vfx_loudness_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                     const double* coef, const double* mpow, int S, int hop, int lookback, double target,
+                                     double ceiling_db, float* out, int64_t out_stride, double* result, void* ws,
+                                     size_t ws_bytes, vfx_stream_t stream) {
+    return lk_run(0, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, target, ceiling_db, nullptr, 0, 1, 0, out,
+                  out_stride, result, ws, ws_bytes, stream);
+}
+
+extern "C" size_t vfx_true_peak_workspace_bytes(int B, int64_t n_max, int R, int J) {
+    if (B <= 0 || n_max < 0 || n_max > INT32_MAX || J < 1 || J > TP_JMAX || (R != 1 && R != 2 && R != 4)) return 0;
+    size_t total = 0;
+    lk_ext_layout(B, n_max, 0, false, &total, nullptr, nullptr);
+    return total;
+}
+
+extern "C" int vfx_loudness_tp_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                        const double* coef, const double* mpow, int S, int hop, int lookback, double target,
+                                        double ceiling_db, const float* bank, int J, int R, int c, float* out,
+                                        int64_t out_stride, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream) {
+    return lk_run(1, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, target, ceiling_db, bank, J, R, c, out,
+                  out_stride, result, ws, ws_bytes, stream);
+}
+
+extern "C" size_t vfx_loudness_report_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J) {
+    if (B <= 0 || n_max < 0 || n_max > INT32_MAX || hop <= 0 || S <= 0 || J < 1 || J > TP_JMAX || (R != 1 && R != 2 && R != 4))
+        return 0;
+    size_t total = 0, more = 0;
+    lk_layout(B, n_max, hop, S, &total, nullptr, nullptr);
+    lk_ext_layout(B, n_max, hop, true, &more, nullptr, nullptr);
+    return total + more;
+}
+
+extern "C" int vfx_loudness_report_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                            const double* coef, const double* mpow, int S, int hop, int lookback,
+                                            const float* bank, int J, int R, int c, double* report, void* ws, size_t ws_bytes,
+                                            vfx_stream_t stream) {
+    return lk_run(2, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, NAN, -1.0, bank, J, R, c, nullptr, 0, report,
+                  ws, ws_bytes, stream);
 }

@@ -10,6 +10,24 @@ this module designs what the kernel is given, in float64, once per rate:
     the fp32-rounded coefficients the kernel runs), and how many 256-chunk spans back the carried state still matters,
 
 and checks the user's parameters.  DESIGN.md 3.10 has the definition, the scan and the measured cost.
+
+True peak (``true_peak=True``; ours, after ITU-R BS.1770-4 Annex 2).  A row of n samples at fs is
+oversampled R(fs) times -- 4 below 96 kHz, 2 from 96 kHz to below 192 kHz, 1 from 192 kHz -- by the project's one
+Kaiser design, ``audio_io.hq_filter(R, 1)``: its float32 taps g in the ``audio_io.polyphase_bank`` layout (751 taps, J = 188
+per phase at R = 4),
+
+    y[m] = sum_i bank[p][i] * x[lo + i],   m in [0, R n),   pos = c + m, p = pos mod R, lo = pos // R - J + 1,
+
+the sum ``vfx_resample_rows_f32`` evaluates with down = 1, samples outside [0, n) taken as zero; TP = max(P, max |y[m]|)
+with P the sample peak, so a true-peak ceiling is never looser than the sample-peak one; R = 1 or n = 0: TP = P and
+nothing is oversampled.  dBTP = 20 log10 TP (-inf for 0).  The device never stores y (``vfx_loudness_tp_rows_f32``).
+
+Loudness report (``vfx_loudness_report_rows_f32``; EBU Tech 3341 / 3342): on the quarters of ``hop`` samples of the
+integrated measurement, the maximum momentary loudness is the largest -0.691 + 10 log10 z_j over ALL 400 ms blocks
+(ungated), the short-term blocks are 30 consecutive quarters from every quarter j in [0, nq - 30], the maximum short-term
+loudness the largest of theirs, and the loudness range LRA is taken over the short-term values above -70 LUFS and above
+the loudness of their mean energy - 20 LU: sorted ascending (n values s), LRA = s[((n-1) 95 + 50) // 100] -
+s[((n-1) + 5) // 10]; 0.0 when no block survives, -inf for a maximum without a block.
 """
 import math
 
@@ -23,6 +41,25 @@ SPAN = 256                    # chunks per workgroup of the kernel (LK_T)
 NPOW = 16                     # M^(2^i), i < NPOW (LK_NPOW)
 TARGET_RANGE = (-70.0, 0.0)   # LUFS, [lo, hi)
 CEILING_RANGE = (-20.0, 0.0)  # dBFS, [lo, hi]
+
+
+def oversampling(fs):
+    """R(fs) of the true-peak measurement: 4 below 96 kHz, 2 below 192 kHz, else 1."""
+    fs = _check_rate(fs)
+    return 4 if fs < 96000 else (2 if fs < 192000 else 1)
+
+
+def check_true_peak(flag):
+    """``true_peak`` is a bool."""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError("true_peak must be True or False (got %r)" % (flag,))
+    return bool(flag)
+
+
+def to_db(v):
+    """20 log10 v; -inf for 0."""
+    v = float(v)
+    return 20.0 * math.log10(v) if v > 0.0 else -math.inf
 
 
 def _check_rate(fs):

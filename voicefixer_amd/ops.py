@@ -504,12 +504,37 @@ def resample_rows(x, n_rows, y, up, down, ny_max=None, row_index=None):
 _LOUDNESS_MPOW = {}
 
 
-def loudness_rows(x, n_rows, rate, target=None, ceiling_db=-1.0, out=None):
+def true_peak_bank(device, R):
+    """(bank, J, c) of the R-times interpolator of the true-peak measurement on ``device``: audio_io.hq_bank(R, 1) uploaded
+    once per device and cached (the cache of resample_bank: there is one filter design)."""
+    if R not in (2, 4):
+        raise _lib.VfxError("true_peak_bank: R must be 2 or 4 (got %r)" % (R,))
+    return resample_bank(device, int(R), 1)
+
+
+def _loudness_plan(x, rate):
+    from . import loudness
+    p = loudness.plan(rate)
+    key = (str(x.device), int(rate))
+    mpow = _LOUDNESS_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(x.device)
+        _LOUDNESS_MPOW[key] = mpow
+    R = loudness.oversampling(rate)
+    bank, J, c = true_peak_bank(x.device, R) if R > 1 else (mpow, 1, 0)      # (R = 1: never read, must not be null)
+    return p, mpow, (C.c_double * 10)(*[float(v) for v in p["coef"]]), (bank, J, R, c)
+
+
+def loudness_rows(x, n_rows, rate, target=None, ceiling_db=-1.0, out=None, true_peak=False):
     """Integrated loudness (BS.1770-4, one channel) of the rows of x (B, >= max n) on the device (vfx_loudness_rows_f32):
     row r holds n_rows[r] samples (device int32 (B,)) at ``rate`` Hz.  Returns a device float64 (B, 3) of {L in LUFS (-inf:
     nothing above the gates), gain, sample peak}.  ``target`` (LUFS): rows are scaled by float32(gain) into ``out`` (default:
-    in place, into x) up to their own lengths; None measures only.  At most 4 launches, no synchronisation."""
+    in place, into x) up to their own lengths; None measures only.  At most 4 launches, no synchronisation.
+    ``true_peak=True`` (vfx_loudness_tp_rows_f32): the ceiling is a TRUE-peak one (dBTP; loudness.py), the result is
+    (B, 4) = {L, gain, sample peak, true peak}, one launch more (none more at rates from 192 kHz)."""
     from . import loudness
+    if loudness.check_true_peak(true_peak):
+        return _loudness_tp_rows(x, n_rows, rate, target, ceiling_db, out)
     _need_cuda(x, n_rows, out)
     assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == n_rows.numel()
     assert n_rows.dtype == torch.int32
@@ -537,3 +562,48 @@ def loudness_rows(x, n_rows, rate, target=None, ceiling_db=-1.0, out=None):
                                   _ptr(out), (out.stride(0) if B > 1 else out.shape[1]) if out is not None else 0, _ptr(res),
                                   _ptr(ws), nb, _stream()), "vfx_loudness_rows_f32")
     return res
+
+
+def _loudness_tp_rows(x, n_rows, rate, target, ceiling_db, out):
+    from . import loudness
+    _need_cuda(x, n_rows, out)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == n_rows.numel()
+    assert n_rows.dtype == torch.int32
+    target = loudness.check_target(target)
+    ceiling_db = loudness.check_ceiling(ceiling_db)
+    p, mpow, coef, (bank, J, R, c) = _loudness_plan(x, rate)
+    if target is not None and out is None:
+        out = x
+    if out is not None:
+        assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == x.shape[0]
+        assert out.shape[1] >= x.shape[1]
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_workspace_bytes(B, n_max, p["hop"], p["S"]) + h.vfx_true_peak_workspace_bytes(B, n_max, R, J)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    res = torch.empty((B, 4), dtype=torch.float64, device=x.device)
+    check(h.vfx_loudness_tp_rows_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, coef, _ptr(mpow),
+                                     p["S"], p["hop"], p["lookback"], float("nan") if target is None else target,
+                                     ceiling_db, _ptr(bank), J, R, c, _ptr(out),
+                                     (out.stride(0) if B > 1 else out.shape[1]) if out is not None else 0, _ptr(res),
+                                     _ptr(ws), nb, _stream()), "vfx_loudness_tp_rows_f32")
+    return res
+
+
+def loudness_report_rows(x, n_rows, rate):
+    """Loudness report of the rows of x (B, >= max n) on the device (vfx_loudness_report_rows_f32; definitions:
+    loudness.py): a device float64 (B, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term
+    loudness, sample peak, true peak} (peaks linear).  Measures only; one launch more than loudness_rows(true_peak=True)."""
+    _need_cuda(x, n_rows)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == n_rows.numel()
+    assert n_rows.dtype == torch.int32
+    p, mpow, coef, (bank, J, R, c) = _loudness_plan(x, rate)
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_report_workspace_bytes(B, n_max, p["hop"], p["S"], R, J)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    rep = torch.empty((B, 6), dtype=torch.float64, device=x.device)
+    check(h.vfx_loudness_report_rows_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, coef, _ptr(mpow),
+                                         p["S"], p["hop"], p["lookback"], _ptr(bank), J, R, c, _ptr(rep), _ptr(ws), nb,
+                                         _stream()), "vfx_loudness_report_rows_f32")
+    return rep
