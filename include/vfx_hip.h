@@ -384,6 +384,22 @@ int vfx_resample_rows_f32(const float* x, int64_t x_stride, const int32_t* n_row
                           int n_index, const float* bank, int J, int up, int down, int c, float* y, int64_t y_stride,
                           int64_t ny_max, vfx_stream_t stream);
 
+/* Outputs m in [m0, m1) of the polyphase sum of vfx_resample_rows_f32 for ONE row of n_total samples, of which the
+ * caller holds only the window xw[k] = x[g0 + k], 0 <= k < wlen.  y[m - m0] receives output m; nothing else is written.
+ * Samples outside [0, n_total) count as zero (n_total = INT64_MAX: the row's end is not yet known).  VFX_EINVAL, nothing
+ * launched, unless the window covers every sample of [0, n_total) that any of the outputs reads:
+ *   max(lo(m0), 0) >= g0   and   min(kmax(m1 - 1), n_total - 1) < g0 + wlen      (lo, kmax as in vfx_resample_rows_f32)
+ * m0 == m1: VFX_OK, nothing launched.  All positions 64-bit.  Output m carries the same 32 bits vfx_resample_rows_f32
+ * writes for output m of the whole row: the taps are clipped against [0, n_total), never against the window, so they
+ * meet the same partial sums in the same order.  One launch. */
+int vfx_resample_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_total, const float* bank, int J, int up,
+                          int down, int c, int64_t m0, int64_t m1, float* y, vfx_stream_t stream);
+
+/* out[k] = tail[k] * (1 - fade[k]) + head[k] * fade[k], 0 <= k < n: every operation rounded to fp32 on its own (no
+ * contraction into an fma), so the result is the bits of numpy's float32  a * (1.0 - f) + b * f.  out may alias tail or
+ * head.  n == 0: VFX_OK, nothing launched. */
+int vfx_xfade_f32(const float* tail, const float* head, const float* fade, int64_t n, float* out, vfx_stream_t stream);
+
 /* ---- loudness normalisation (ITU-R BS.1770-4, one channel) --------------------------------------------------------- */
 
 /* Bytes of the workspace vfx_loudness_rows_f32 needs for B rows of at most n_max samples (0 on bad arguments). */

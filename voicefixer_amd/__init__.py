@@ -4,6 +4,7 @@ Same public surface as ``voicefixer`` for this path::
 
     from voicefixer_amd import VoiceFixer, Vocoder
 """
-from .api import VoiceFixer, Vocoder, loudness_report, measure_loudness, measure_true_peak  # noqa: F401
+from .api import RestoreSession, StreamPlanner, VoiceFixer, Vocoder, loudness_report, measure_loudness, measure_true_peak  # noqa: F401
 
-__all__ = ["VoiceFixer", "Vocoder", "measure_loudness", "measure_true_peak", "loudness_report"]
+__all__ = ["VoiceFixer", "Vocoder", "measure_loudness", "measure_true_peak", "loudness_report", "RestoreSession",
+           "StreamPlanner"]

@@ -86,6 +86,8 @@ SIGNATURES = {
     "vfx_bn_apply_f32": (_I, [_T, _T, _I, _I, _I, _I, _I, _P, _P, _I, C.c_float, _P]),
     "vfx_dropout_f32": (_I, [_T, _I, _I, _I, _P, _I, _I, _P]),
     "vfx_resample_rows_f32": (_I, [_P, C.c_int64, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, C.c_int64, C.c_int64, _P]),
+    "vfx_resample_span_f32": (_I, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _P, _P]),
+    "vfx_xfade_f32": (_I, [_P, _P, _P, C.c_int64, _P, _P]),
     "vfx_loudness_workspace_bytes": (C.c_size_t, [_I, C.c_int64, _I, _I]),
     "vfx_loudness_rows_f32": (_I, [_P, C.c_int64, _P, _I, C.c_int64, _P, _P, _I, _I, _I, C.c_double, C.c_double, _P,
                                    C.c_int64, _P, _P, C.c_size_t, _P]),

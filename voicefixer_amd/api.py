@@ -102,6 +102,42 @@ def plan_stream_chunks(n, chunk, overlap, min_tail=1024):
     return [tuple(c) for c in plan]
 
 
+class StreamPlanner:
+    """``plan_stream_chunks`` for a waveform whose length is not known yet: ``feed(n_new)`` announces ``n_new`` more
+    samples and returns the chunks (start, length) that are settled now, ``finish()`` the rest.  Everything returned,
+    concatenated, is ``plan_stream_chunks(n, chunk, overlap, min_tail)`` of the final n, whatever the block sizes.
+    ``plan_stream_chunks`` merges a tail of <= overlap + min_tail samples into its predecessor, so the chunk at ``start``
+    is settled at length ``chunk`` only once MORE than start + chunk + min_tail samples are known: that is the latency of
+    a streaming session."""
+
+    def __init__(self, chunk, overlap, min_tail=1024):
+        if chunk <= overlap + 1024 or overlap < 0:
+            raise ValueError("chunk must exceed overlap + 1024 samples")
+        self.chunk, self.overlap, self.min_tail = int(chunk), int(overlap), int(min_tail)
+        self.known = 0       # samples announced so far
+        self.start = 0       # start of the first chunk not yet returned
+        self.finished = False
+
+    def feed(self, n_new):
+        if self.finished:
+            raise RuntimeError("StreamPlanner: feed after finish")
+        if n_new < 0:
+            raise ValueError("StreamPlanner: a negative number of samples")
+        self.known += int(n_new)
+        out = []
+        while self.known > self.start + self.chunk + self.min_tail:
+            out.append((self.start, self.chunk))
+            self.start += self.chunk - self.overlap
+        return out
+
+    def finish(self):
+        if self.finished:
+            raise RuntimeError("StreamPlanner: finish called twice")
+        self.finished = True
+        rest = plan_stream_chunks(self.known - self.start, self.chunk, self.overlap, self.min_tail)
+        return [(self.start + a, length) for a, length in rest]
+
+
 def _check_rate(rate, what="sample_rate"):
     if isinstance(rate, bool) or int(rate) != rate or int(rate) <= 0:
         raise ValueError("%s must be a positive integer number of samples per second (got %r)" % (what, rate))
@@ -825,6 +861,18 @@ class VoiceFixer(nn.Module):
             i += len(grp)
         return out[:, :n_out]
 
+    def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
+                    sample_rate=44100, output_sample_rate=None):
+        """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
+        ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
+        chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
+        returns for the concatenated blocks (converted to 44.1 kHz as a whole) with the same ``chunk_seconds``,
+        ``overlap_seconds``, ``batch_size`` and ``mode`` -- bit for bit at ``batch_size=1`` -- converted as a whole to the
+        output rate.  Modes 0 and 1; ``mode=2`` raises NotImplementedError.  The arguments are checked here, before the
+        device is touched."""
+        return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
+                              output_sample_rate)
+
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
@@ -1198,3 +1246,187 @@ class VoiceFixer(nn.Module):
                                             output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
                                             **kw)
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out)
+
+
+class _SpanConverter:
+    """Rate conversion of ONE row that arrives in pieces (ops.resample_span): ``feed`` takes the next samples (device
+    (k,)) and returns the outputs that read nothing beyond what has arrived (audio_io.ready_outputs), ``finish`` the rest
+    up to ceil(n * up / down) with the row's end known.  Every output has the bits of ops.resample_rows on the whole row.
+    Kept between calls: the samples future outputs still read (at most J + down / up + 1 of them) and their global offset."""
+
+    def __init__(self, rate_in, rate_out):
+        self.up, self.down = audio_io.rate_ratio(rate_in, rate_out)
+        _, self.J, self.c = audio_io.hq_bank(self.up, self.down)
+        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
+        self.g0 = 0
+        self.n_in = 0        # samples fed
+        self.m_done = 0      # outputs returned
+
+    def feed(self, x):
+        self.win = x if self.win is None else torch.cat([self.win, x])
+        self.n_in += x.numel()
+        return self._emit(audio_io.ready_outputs(self.n_in, self.up, self.down, self.c), None)
+
+    def finish(self, device):
+        if self.win is None:
+            return torch.empty((0,), dtype=torch.float32, device=device)
+        return self._emit(-(-self.n_in * self.up // self.down), self.n_in)
+
+    def _emit(self, m1, n_total):
+        from . import ops
+        m0, m1 = self.m_done, max(m1, self.m_done)
+        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
+        if m1 > m0:
+            ops.resample_span(self.win, self.g0, n_total, self.up, self.down, m0, m1, y)
+        self.m_done = m1
+        # drop what no later output reads: output m1 starts at lo(m1) (one sample always stays: a window is never empty)
+        keep = min(max(audio_io.span_window(m1, m1 + 1, self.up, self.down, self.J, self.c)[0], 0), self.n_in - 1)
+        if keep > self.g0:
+            self.win = self.win[keep - self.g0:].clone()
+            self.g0 = keep
+        return y
+
+
+class RestoreSession:
+    """``VoiceFixer.open_stream``: the overlap-add long-form mode as a push-style session on the device.
+
+        s = vf.open_stream(chunk_seconds=30.0, overlap_seconds=1.0, sample_rate=16000, output_sample_rate=48000)
+        y = s.push(block)        # float32 (k,) at sample_rate, any k >= 0 -> float32 numpy (1, j) at the output rate, j >= 0
+        y = s.finish()           # the rest; afterwards push / finish raise RuntimeError
+        s.position               # output samples delivered so far
+
+    Definition: with X the concatenation of all pushed blocks, X44 its whole-row conversion to 44.1 kHz (``convert_rows``),
+    Y44 = ``restore_stream(X44, chunk_seconds, overlap_seconds, batch_size, mode)`` and Z = Y44 converted as a whole row to
+    the output rate by ops.resample_rows (Z = Y44 at 44.1 kHz), the results of all ``push`` calls and of ``finish``
+    concatenate to Z.  NO second peak rule is applied to a converted output (``convert_output`` applies one to whole
+    files): a stretch leaves before the file's peak exists, so a converted stretch may overshoot 1.0 slightly.
+    Four stages, all on the device and on the current stream: the input converter (ops.resample_span on the samples that
+    future outputs still read; a copy at 44.1 kHz), the chunker (``StreamPlanner``; settled chunks of equal length go
+    through the path in groups of up to ``batch_size``), the stitcher (ops.xfade of the previous chunk's last ``overlap``
+    samples with the next chunk's head) and the output converter (the input converter again, fed with the final 44.1 kHz
+    stretches, which therefore never visit the host).  Held between calls: the 44.1 kHz samples from the next chunk's
+    start on, one overlap, two filter windows -- O(chunk + the largest block), whatever has been pushed.  A chunk is
+    settled once more than chunk + min_tail samples (1024; mode 1: 1535) beyond its start are known at 44.1 kHz: the
+    session's latency.  Loudness normalisation and a true-peak ceiling need the whole file and are not offered here.
+    A context manager; leaving it without ``finish`` discards what is pending."""
+
+    def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
+                 sample_rate=44100, output_sample_rate=None):
+        if mode == 2:
+            raise NotImplementedError("open_stream: mode=2 is not built -- its per-segment statistics have no overlap-add form")
+        VoiceFixer._check_mode(mode)
+        self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
+        for r in (self._rate_in, self._rate_out):
+            if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
+                raise ValueError("open_stream: the device resampler does not take the ratio of %d Hz to 44100 Hz" % r)
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError("batch_size must be a positive integer")
+        chunk, ov = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
+        if mode == 1:
+            chunk -= chunk % 512
+        self._planner = StreamPlanner(chunk, ov, 1535 if mode == 1 else 1024)     # (ValueError: chunk <= overlap + 1024)
+        self._vf, self._mode, self._voc, self._batch, self._ov = vf, mode, your_vocoder_func, int(batch_size), ov
+        self._conv_in = _SpanConverter(self._rate_in, 44100) if self._rate_in != 44100 else None
+        self._conv_out = _SpanConverter(44100, self._rate_out) if self._rate_out != 44100 else None
+        self._n_in = 0           # samples pushed
+        self._buf = None         # device (k,): 44.1 kHz samples [b0, b0 + k)
+        self._b0 = 0
+        self._tail = None        # device (ov,): the previous chunk's stitched last ``ov`` samples
+        self._fade = None        # device (ov,): restore_stream's fade-in ramp, uploaded once
+        self._closed = False
+        self.position = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        """Drop what is pending (nothing more is delivered); ``push`` and ``finish`` raise afterwards."""
+        self._closed = True
+        self._buf = self._tail = self._fade = self._conv_in = self._conv_out = None
+
+    @torch.no_grad()
+    def push(self, block):
+        """The next ``block`` (float32 (k,), k >= 0, at the session's input rate) -> the output that became final with it:
+        float32 numpy (1, j) at the output rate, j >= 0."""
+        if self._closed:
+            raise RuntimeError("RestoreSession: push after finish / close")
+        block = np.asarray(block, dtype=np.float32)
+        if block.ndim != 1:
+            raise ValueError("push: a block is a 1-D array of samples (got shape %r)" % (block.shape,))
+        if block.shape[0] == 0:
+            return np.zeros((1, 0), np.float32)
+        pipe = self._vf._get_pipe()
+        x = torch.from_numpy(np.ascontiguousarray(block)).to(pipe.device)
+        self._n_in += block.shape[0]
+        if self._conv_in is not None:
+            x = self._conv_in.feed(x)
+        self._buf = x if self._buf is None else torch.cat([self._buf, x])
+        return self._deliver(pipe, self._restore(pipe, self._planner.feed(x.numel()), False), False)
+
+    @torch.no_grad()
+    def finish(self):
+        """The rest of the output, float32 numpy (1, j); the session is closed afterwards.  ValueError, nothing launched,
+        when fewer 44.1 kHz samples than ``VoiceFixer.MIN_SAMPLES[mode]`` were pushed."""
+        if self._closed:
+            raise RuntimeError("RestoreSession: finish called twice (or after close)")
+        try:
+            n44 = audio_io.converted_length(self._n_in, self._rate_in, 44100)
+            if n44 < VoiceFixer.MIN_SAMPLES[self._mode]:
+                raise ValueError("RestoreSession: %d samples at 44.1 kHz were pushed, mode %d needs at least %d"
+                                 % (n44, self._mode, VoiceFixer.MIN_SAMPLES[self._mode]))
+            pipe = self._vf._get_pipe()
+            n_new = 0
+            if self._conv_in is not None:
+                x = self._conv_in.finish(pipe.device)
+                self._buf = torch.cat([self._buf, x])
+                n_new = x.numel()
+            plan = self._planner.feed(n_new) + self._planner.finish()
+            return self._deliver(pipe, self._restore(pipe, plan, True), True)
+        finally:
+            self.close()
+
+    def _restore(self, pipe, plan, at_end):
+        """The settled chunks ``plan`` through the path and the stitcher; returns their final 44.1 kHz stretches (device)."""
+        from . import ops
+        ov, out, i = self._ov, [], 0
+        while i < len(plan):
+            length = plan[i][1]
+            grp = [c for c in plan[i:i + self._batch] if c[1] == length]
+            seg = torch.stack([self._buf[a - self._b0:a - self._b0 + length] for a, _ in grp])
+            res = pipe.run_checked(lambda: VoiceFixer._restore_segments(pipe, seg, length, self._mode, self._voc))
+            got = res.shape[1]          # == length in mode 0; 512 * (length // 512) in mode 1
+            for k, (a, _) in enumerate(grp):
+                y = res[k]
+                if a > 0 and ov > 0:    # cross-fade with what the previous chunk left in the overlap, in place
+                    ops.xfade(self._tail, y[:ov], self._fade, y[:ov])
+                last = at_end and i + k == len(plan) - 1
+                if last:
+                    out.append(y)
+                else:
+                    out.append(y[:got - ov])
+                    if ov > 0:
+                        if self._fade is None:
+                            self._fade = torch.from_numpy(np.arange(ov, dtype=np.float32) / max(ov, 1)).to(pipe.device)
+                        self._tail = y[got - ov:].clone()
+            i += len(grp)
+        # the next chunk starts at the planner's start: nothing before it is read again
+        if not at_end and self._planner.start > self._b0:
+            self._buf = self._buf[self._planner.start - self._b0:].clone()
+            self._b0 = self._planner.start
+        return out
+
+    def _deliver(self, pipe, stretches, at_end):
+        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs."""
+        if self._conv_out is not None:
+            stretches = [self._conv_out.feed(y) for y in stretches if y.numel()]
+            if at_end:
+                stretches.append(self._conv_out.finish(pipe.device))
+        if not stretches:
+            return np.zeros((1, 0), np.float32)
+        y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches)).cpu().numpy()[None]
+        self.position += y.shape[1]
+        return y

@@ -159,6 +159,19 @@ def hq_bank(up, down):
     return polyphase_bank(hq_filter(up, down)[1], up)
 
 
+def ready_outputs(avail, up, down, c):
+    """Leading outputs of the polyphase sum (vfx_resample_rows_f32) that read nothing at or past sample ``avail``: those with
+    kmax(m) = (c + m * down) // up < avail.  A streaming converter may emit them before the row's end is known."""
+    t = int(avail) * up - 1 - c
+    return 0 if t < 0 else t // down + 1
+
+
+def span_window(m0, m1, up, down, J, c):
+    """(lo(m0), kmax(m1 - 1) + 1): the unclipped range of input samples that outputs [m0, m1), m1 > m0, of the polyphase sum
+    read (lo(m) = kmax(m) - J + 1; both grow with m)."""
+    return (c + int(m0) * down) // up - J + 1, (c + (int(m1) - 1) * down) // up + 1
+
+
 def resample_hq(x, sr_in, sr_out, use_native=None):
     """Band-limited rate conversion along the last axis, ceil(n * sr_out / sr_in) samples (librosa.load(sr=...) ->
     soxr_hq).  The filter of ``hq_filter`` applied as a polyphase filter: one dot product per output sample in

@@ -501,6 +501,36 @@ def resample_rows(x, n_rows, y, up, down, ny_max=None, row_index=None):
           "vfx_resample_rows_f32")
 
 
+INT64_MAX = 2 ** 63 - 1
+
+
+def resample_span(xw, g0, n_total, up, down, m0, m1, y):
+    """Outputs [m0, m1) of ONE row's rate conversion from a window of it (vfx_resample_span_f32): xw (wlen,) device holds
+    samples [g0, g0 + wlen) of a row of ``n_total`` samples (None: its end is not known yet), y (>= m1 - m0,) receives
+    output m at y[m - m0] -- the bits ops.resample_rows writes for output m of the whole row.  The window must cover what
+    the span reads (audio_io.span_window clipped to [0, n_total)), or VfxError.  The bank is resample_bank's."""
+    _need_cuda(xw, y)
+    assert xw.dtype == torch.float32 and y.dtype == torch.float32 and xw.dim() == 1 and y.dim() == 1
+    assert (xw.numel() == 0 or xw.stride(0) == 1) and (y.numel() == 0 or y.stride(0) == 1)
+    m0, m1 = int(m0), int(m1)
+    if m1 - m0 > y.numel():
+        raise _lib.VfxError("resample_span: %d outputs into a buffer of %d" % (m1 - m0, y.numel()))
+    bank, J, c = resample_bank(xw.device, int(up), int(down))
+    check(_lib.lib().vfx_resample_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total),
+                                           _ptr(bank), J, int(up), int(down), c, m0, m1, _ptr(y), _stream()),
+          "vfx_resample_span_f32")
+
+
+def xfade(tail, head, fade, out):
+    """out = tail * (1 - fade) + head * fade over the n = fade.numel() samples of an overlap (vfx_xfade_f32): the bits of the
+    float32 numpy expression of restore_stream.  out may be tail or head."""
+    _need_cuda(tail, head, fade, out)
+    n = fade.numel()
+    for t in (tail, head, fade, out):
+        assert t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n and (n == 0 or t.stride(0) == 1)
+    check(_lib.lib().vfx_xfade_f32(_ptr(tail), _ptr(head), _ptr(fade), n, _ptr(out), _stream()), "vfx_xfade_f32")
+
+
 _LOUDNESS_MPOW = {}
 
 
