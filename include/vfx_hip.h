@@ -400,7 +400,7 @@ int vfx_resample_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_t
  * head.  n == 0: VFX_OK, nothing launched. */
 int vfx_xfade_f32(const float* tail, const float* head, const float* fade, int64_t n, float* out, vfx_stream_t stream);
 
-/* ---- loudness normalisation (ITU-R BS.1770-4, one channel) --------------------------------------------------------- */
+/* ---- loudness normalisation (ITU-R BS.1770-4; one channel per row -- programmes of several channels: further below) - */
 
 /* Bytes of the workspace vfx_loudness_rows_f32 needs for B rows of at most n_max samples (0 on bad arguments). */
 size_t vfx_loudness_workspace_bytes(int B, int64_t n_max, int hop, int S);
@@ -467,6 +467,40 @@ size_t vfx_loudness_report_workspace_bytes(int B, int64_t n_max, int hop, int S,
 int vfx_loudness_report_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
                                  const double* coef, const double* mpow, int S, int hop, int lookback, const float* bank,
                                  int J, int R, int c, double* report, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
+/* ---- programmes of several channels (ITU-R BS.1770-4 with channel weights) -------------------------------- */
+
+/* The B rows form G programmes of adjacent rows: group_start is device int32[G + 1], ascending, group_start[0] = 0,
+ * group_start[G] = B; weight is device float64[B], the channel weight G_c >= 0 of every row.  The length of a programme is
+ * n_rows of its FIRST row; the caller guarantees that its other rows have the same and that group_start is as described (if
+ * the lengths differ, or group_start is not ascending from 0 to B -- overlapping programmes, rows in none -- the figures are
+ * unspecified, but nothing is read or written outside ws, result and the rows of out: the kernels clamp it into [0, B]).  With q_{c,i} the quarter sums of
+ * row c (vfx_loudness_rows_f32),
+ *   z_j = (sum_c G_c * (q_{c,j} + q_{c,j+1} + q_{c,j+2} + q_{c,j+3})) * 1/(4 hop),   rows in ascending order, fp64
+ * (one row of weight 1.0: the bits of the per-row z_j), gates and L as vfx_loudness_rows_f32 on these z_j;
+ * P = max_c P_c, TP = max_c TP_c (rows of weight 0 included);  g = min(10^((target - L)/20), 10^(ceiling_db/20) / TP),
+ * 1 when L = -inf;  out = (float)g * x for every row of the programme over that row's own n_rows -- ONE factor per programme.
+ * result: device float64[G][4] = {L, g, P, TP}.  The chunk, filter and true-peak kernels run per row as they do for
+ * vfx_loudness_tp_rows_f32; one workgroup per programme folds them in a fixed order, so a programme's result does not depend
+ * on what else the call holds.  Exactly the launches of vfx_loudness_tp_rows_f32 with the same arguments; no host
+ * synchronisation.  ws: >= vfx_loudness_groups_workspace_bytes bytes (the WHOLE workspace), 16-byte aligned.
+ * VFX_EINVAL on bad arguments (nothing launched): G < 1, G > B, NULL group_start or weight, and everything
+ * vfx_loudness_tp_rows_f32 rejects. */
+size_t vfx_loudness_groups_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J);
+int vfx_loudness_groups_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                            const int32_t* group_start, const double* weight, int G, const double* coef, const double* mpow,
+                            int S, int hop, int lookback, double target, double ceiling_db, const float* bank, int J, int R,
+                            int c, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes,
+                            vfx_stream_t stream);
+
+/* Loudness report of G programmes (measure only): report is device float64[G][6] = {L, LRA, Mmax, Smax, P, TP}, the recipe
+ * of vfx_loudness_report_rows_f32 on the programme quarter sums Q_i = sum_c G_c * q_{c,i} (ascending rows, fp64) and on the
+ * z_j above; L, P, TP: the bits of vfx_loudness_groups_f32.  Exactly the launches of vfx_loudness_report_rows_f32. */
+size_t vfx_loudness_report_groups_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J);
+int vfx_loudness_report_groups_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                   const int32_t* group_start, const double* weight, int G, const double* coef,
+                                   const double* mpow, int S, int hop, int lookback, const float* bank, int J, int R, int c,
+                                   double* report, void* ws, size_t ws_bytes, vfx_stream_t stream);
 
 /* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
 

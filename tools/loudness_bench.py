@@ -6,9 +6,13 @@ measurement (3 launches), the true-peak measurement (the same + the fused oversa
 true peak cost before that kernel existed -- ops.resample_rows at up = R, down = 1 into an R-times-wider scratch, then
 abs().amax per row.  Median of ``--reps`` per pass, ``--passes`` passes: the spread of a leg's medians is the yardstick
 for the difference between two legs.  The shader clock is sampled over the timed window (bench.ClockSampler).
+``--channels C`` (DESIGN.md 3.13) times, for 32 rows of 10 s cut into programmes of C channels (32 // C of them and one of
+the remainder: 16 stereo programmes at C = 2, 5 x 6 + 2 at C = 6), alternating in one process: ops.loudness_groups against
+ops.loudness_rows(true_peak=True) on the same rows, measuring only and measuring + applying.
 
     python tools/loudness_bench.py [--reps 20]
     python tools/loudness_bench.py --true-peak [--reps 10] [--passes 3]
+    python tools/loudness_bench.py --channels 2 [--reps 10] [--passes 3]
     rocprofv3 --kernel-trace --stats -- python tools/loudness_bench.py     # per-kernel table
 """
 import argparse
@@ -100,6 +104,56 @@ def run_true_peak(B, seconds, reps, passes, fs=44100):
                       "sclk_mhz": clocks.get("sclk_mhz"), "clock_source": clocks.get("source")}), flush=True)
 
 
+def run_channels(C, B, seconds, reps, passes, fs=44100):
+    import time
+    import torch
+    import bench
+    from voicefixer_amd import ops
+    dev = torch.device("cuda", 0)
+    n = int(seconds * fs)
+    groups = [C] * (B // C) + ([B % C] if B % C else [])
+    g = torch.Generator().manual_seed(3)
+    x = (0.1 * torch.randn((B, n), generator=g)).to(dev)
+    y = torch.empty_like(x)
+    n_rows = torch.full((B,), n, dtype=torch.int32, device=dev)
+    lens = [n] * B       # (the grouped legs take the lengths as a list: checked on the host, uploaded once with the group
+    #                       starts and weights by the warm-up call and cached -- no copy and no read-back inside the timed
+    #                       region, as in the per-row legs, so the difference between two legs is the kernels')
+    legs = {"rows_measure": lambda: ops.loudness_rows(x, n_rows, fs, true_peak=True),
+            "groups_measure": lambda: ops.loudness_groups(x, lens, groups, fs),
+            "rows_apply": lambda: ops.loudness_rows(x, n_rows, fs, target=-23.0, out=y, true_peak=True),
+            "groups_apply": lambda: ops.loudness_groups(x, lens, groups, fs, target=-23.0, out=y)}
+    for fn in legs.values():                                        # warm-up: bank / plan / group uploads, code objects
+        fn()
+    torch.cuda.synchronize()
+    med = {k: [] for k in legs}
+    sampler = bench.ClockSampler(torch.cuda.current_device(), period=0.02)
+    with sampler:
+        t0 = time.perf_counter()
+        for _ in range(passes):
+            ev = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():                          # alternating: the legs see the same machine
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    ev[k].append((e0, e1))
+            torch.cuda.synchronize()
+            for k in legs:
+                ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev[k])
+                med[k].append(round(ms[len(ms) // 2], 4))
+        t1 = time.perf_counter()
+    clocks = sampler.summary(t0, t1)
+    mid = {k: sorted(v)[len(v) // 2] for k, v in med.items()}
+    print(json.dumps({"case": "channels", "channels": C, "groups": groups, "rows": B, "seconds": seconds, "rate": fs,
+                      "reps": reps, "medians_ms": med, "median_ms": mid,
+                      "spread_ms": {k: round(max(v) - min(v), 4) for k, v in med.items()},
+                      "groups_minus_rows_measure_ms": round(mid["groups_measure"] - mid["rows_measure"], 4),
+                      "groups_minus_rows_apply_ms": round(mid["groups_apply"] - mid["rows_apply"], 4),
+                      "sclk_mhz": clocks.get("sclk_mhz"), "clock_source": clocks.get("source")}), flush=True)
+
+
 def _true_peak_bytes(B, n, R, dev):
     from voicefixer_amd import _lib, ops
     return _lib.lib().vfx_true_peak_workspace_bytes(B, n, R, ops.true_peak_bank(dev, R)[1])
@@ -109,8 +163,15 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--true-peak", action="store_true", help="time the true-peak legs instead (DESIGN.md 3.11)")
-    ap.add_argument("--passes", type=int, default=3, help="--true-peak: passes of --reps alternating repetitions")
+    ap.add_argument("--passes", type=int, default=3, help="--true-peak / --channels: passes of --reps alternating repetitions")
+    ap.add_argument("--channels", type=int, default=0, metavar="C",
+                    help="time programmes of C channels (1..8) against the per-row call instead (DESIGN.md 3.13)")
     args = ap.parse_args(argv)
+    if args.channels:
+        if not 1 <= args.channels <= 8:
+            ap.error("--channels takes 1..8")
+        run_channels(args.channels, 32, 10.0, args.reps, args.passes)
+        return
     if args.true_peak:
         run_true_peak(32, 10.0, args.reps, args.passes)
         run_true_peak(1, 1800.0, args.reps, args.passes)

@@ -26,6 +26,10 @@ Differences, all deliberate:
     limited by the sample-peak ceiling ``--peak-ceiling DBFS`` (default -1); file and folder mode, every ``--mode``;
     ``--true-peak`` with it: the ceiling is read as dBTP and the TRUE peak, measured between the samples, limits the gain
     (alone it is an argument error; forwarded to every ``--gpus`` rank with the rest of the command line);
+  * ``--channels {mix,first,all}`` (extension; file and folder mode, forwarded to every ``--gpus`` rank): what becomes of an
+    input with several channels -- ``mix`` (default): their average, as the reference's ``librosa.load``; ``first``: the first
+    channel; ``all``: every channel is restored and the output has the input's channel count; ``--loudness`` is then ONE
+    linked gain per file (BS.1770-4's weighted sum over the channels), which keeps their balance;
   * output formats are WAV and FLAC (``audio_io.FORMATS``) instead of whatever libsndfile offers;
   * folder mode isolates faults per FILE: an unreadable / truncated / too short input or a row the device refuses costs that
     file only -- it is listed on stderr with its reason, every other file is written, the exit status is 2 (all ranks of a
@@ -76,7 +80,7 @@ def mode_outfile(outfile, mode, append_mode):
 
 
 def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
-              resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False):
+              resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
@@ -90,6 +94,8 @@ def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=Fals
         kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
         if true_peak:
             kw["true_peak"] = True
+    if channels is not None:
+        kw["channels"] = channels
     voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, **kw)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
@@ -147,6 +153,10 @@ def build_parser():
     parser.add_argument("--true-peak", default=False, action="store_true",
                         help="(extension) with --loudness: read --peak-ceiling as dBTP and limit the gain by the TRUE peak, measured "
                              "on the device between the samples (EBU R 128's ceiling)")
+    parser.add_argument("--channels", choices=["mix", "first", "all"], default=None,
+                        help="(extension) inputs of several channels: mix (default): restore their average; first: restore the "
+                             "first channel; all: restore every channel and write the input's channel count (with --loudness: "
+                             "one linked gain per file)")
     return parser
 
 
@@ -278,7 +288,7 @@ def main(argv=None):
         for m in modes:
             writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
                       output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device,
-                      loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak)
+                      loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak, channels=args.channels)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -294,7 +304,8 @@ def main(argv=None):
                                           skip_existing=args.skip_existing, io_threads=args.io_threads or None,
                                           seed=args.seed, output_sample_rate=args.output_sample_rate,
                                           resample_on_device=args.resample_on_device, loudness=args.loudness,
-                                          peak_ceiling=args.peak_ceiling, **({"true_peak": True} if args.true_peak else {}))
+                                          peak_ceiling=args.peak_ceiling, **({"true_peak": True} if args.true_peak else {}),
+                                          **({"channels": args.channels} if args.channels is not None else {}))
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

@@ -56,24 +56,35 @@ def _load_restorer_state(path):
     return out, (voc or None)  # vf.ckpt may overwrite the vocoder weights
 
 
-def plan_batches(sorted_lengths, batch_size, ragged_ratio=0.5, ragged=True):
+def plan_batches(sorted_lengths, batch_size, ragged_ratio=0.5, ragged=True, rows=None):
     """Cut a list of ASCENDING sample counts into batches: ("ragged", [positions]) for runs of utterances of
     1025..SEG_LENGTH samples whose shortest member has >= ragged_ratio of the frames (1 + n // 441) of the longest
     (Pipeline.restore_rows), ("samples", [positions]) for runs of exactly equal length otherwise (files of several
-    segments, plugin vocoders, too-short files -- the last raise in the pipeline as the reference does)."""
+    segments, plugin vocoders, too-short files -- the last raise in the pipeline as the reference does).
+    ``rows`` (multichannel files): how many batch rows every item takes -- its channel count; a batch then holds at most
+    ``batch_size`` ROWS and never splits an item (ValueError when an item alone has more rows than ``batch_size``)."""
+    if rows is not None:
+        if len(rows) != len(sorted_lengths):
+            raise ValueError("plan_batches: %d row counts for %d items" % (len(rows), len(sorted_lengths)))
+        if rows and max(rows) > batch_size:
+            raise ValueError("batch_size (%d) is smaller than the largest channel count (%d): the channels of a file share "
+                             "one batch" % (batch_size, max(rows)))
     plan = []
     i, n_items = 0, len(sorted_lengths)
     while i < n_items:
         n0 = sorted_lengths[i]
         j = i + 1
+        used = 1 if rows is None else rows[i]
         if ragged and 1025 <= n0 <= SEG_LENGTH:
             t0 = 1 + n0 // 441
-            while (j < n_items and j - i < batch_size and sorted_lengths[j] <= SEG_LENGTH and
+            while (j < n_items and used + (1 if rows is None else rows[j]) <= batch_size and sorted_lengths[j] <= SEG_LENGTH and
                    t0 >= ragged_ratio * (1 + sorted_lengths[j] // 441)):
+                used += 1 if rows is None else rows[j]
                 j += 1
             plan.append(("ragged", list(range(i, j))))
         else:
-            while j < n_items and j - i < batch_size and sorted_lengths[j] == n0:
+            while j < n_items and used + (1 if rows is None else rows[j]) <= batch_size and sorted_lengths[j] == n0:
+                used += 1 if rows is None else rows[j]
                 j += 1
             plan.append(("samples", list(range(i, j))))
         i = j
@@ -223,6 +234,82 @@ def apply_loudness(full, lens, rate, target, peak_ceiling=-1.0, true_peak=False)
     return out, res
 
 
+def apply_loudness_groups(full, lens, groups, rate, target, peak_ceiling=-1.0, true_peak=False, channel_weights=None):
+    """``apply_loudness`` for PROGRAMMES of several channels (ops.loudness_groups; loudness.py): the rows of ``full`` are
+    ``groups`` = [C_0, C_1, ...] adjacent channels per programme, all rows of one programme lens[r] samples long; ONE
+    loudness, one peak and one float32 gain per programme, so the balance between its channels is kept.  Returns (rows,
+    device float64 (G, 4) of {L before, g, sample peak, true peak}); without ``true_peak`` the ceiling is a sample-peak one
+    and the fourth value repeats the sample peak.  ``channel_weights``: one list for every programme (all of one channel
+    count then), default loudness.channel_weights."""
+    from . import loudness, ops
+    target, peak_ceiling = loudness.check_target(target), loudness.check_ceiling(peak_ceiling)
+    true_peak = loudness.check_true_peak(true_peak)
+    if target is None:
+        return full, None
+    weights = None if channel_weights is None else [w for g in groups for w in loudness.channel_weights(g, channel_weights)]
+    x = full if full.stride(-1) == 1 else full.contiguous()
+    out = torch.empty_like(x)
+    res = ops.loudness_groups(x, [int(n) for n in lens], groups, rate, target, peak_ceiling, out=out, weights=weights,
+                              true_peak=true_peak)
+    return out, res
+
+
+def _check_channels(channels, channel_weights=None):
+    from . import loudness
+    if channel_weights is not None:
+        if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
+                or not 1 <= len(channel_weights) <= loudness.MAX_CHANNELS:
+            raise ValueError("channel_weights must be a list of 1..8 numbers >= 0, one per channel (got %r)" % (channel_weights,))
+        loudness.channel_weights(len(channel_weights), channel_weights)
+    return loudness.check_channels(channels)
+
+
+def _as_programme(x, channels, what):
+    """A waveform argument under ``channels``: -> (float32 (C, N), multi).  None: a 1-D array as it is (a 2-D one raises: it
+    used to be misread); "mix" / "first": a 2-D array is averaged / cut to channel 0; "all": every channel."""
+    from . import loudness
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim == 2 and channels is None:
+        raise ValueError('%s: a 2-D array of shape %r needs channels= -- channels="all" restores every channel of a '
+                         '(channels, N) array, "mix" / "first" take their average / the first' % (what, x.shape))
+    if x.ndim not in (1, 2):
+        raise ValueError("%s: a waveform is (N,) or (channels, N) (got shape %r)" % (what, x.shape))
+    if x.ndim == 2:
+        loudness.check_channel_count(x.shape[0])
+        if channels == "mix":
+            x = x.mean(axis=0, dtype=np.float32)
+        elif channels == "first":
+            x = x[0]
+    if channels == "all":
+        return (x[None] if x.ndim == 1 else x), True
+    return x[None], False
+
+
+def _stage_programmes(wav, channel_weights):
+    """One array or a list mixing (N,) and (C, N) arrays -> None when every array is 1-D and no weights are given (the
+    per-row path measures them), else (single, padded device rows, row lengths, channel counts, row weights or None)."""
+    from . import loudness
+    single = not isinstance(wav, (list, tuple))
+    items = [np.asarray(w, dtype=np.float32) for w in ([wav] if single else wav)]
+    if channel_weights is None and all(w.ndim != 2 for w in items):
+        return None
+    for w in items:
+        if w.ndim not in (1, 2):
+            raise ValueError("a waveform is (N,) or (channels, N) (got shape %r)" % (w.shape,))
+    items = [w[None] if w.ndim == 1 else w for w in items]
+    groups = [loudness.check_channel_count(w.shape[0]) for w in items]
+    weights = None if channel_weights is None else [v for g in groups for v in loudness.channel_weights(g, channel_weights)]
+    if not items:
+        return single, None, [], [], weights
+    lens = [w.shape[1] for w in items for _ in range(w.shape[0])]
+    host = np.zeros((len(lens), max(max(lens), 1)), np.float32)
+    r = 0
+    for w in items:
+        host[r:r + w.shape[0], :w.shape[1]] = w
+        r += w.shape[0]
+    return single, torch.from_numpy(host).to(_device()), lens, groups, weights
+
+
 def _check_loudness(loudness_target, peak_ceiling, true_peak=False):
     from . import loudness
     loudness.check_true_peak(true_peak)
@@ -243,11 +330,21 @@ def _stage_rows(wav):
     return single, torch.from_numpy(host).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev), lens
 
 
-def measure_true_peak(wav, sample_rate=44100):
+def measure_true_peak(wav, sample_rate=44100, channel_weights=None):
     """True peak in dBTP (after ITU-R BS.1770-4 Annex 2; loudness.py has the definition) of a float32 array (N,) -- or of
-    every array of a list, in one device call -- measured on the device.  -inf: an all-zero or empty array."""
+    every array of a list, in one device call -- measured on the device.  -inf: an all-zero or empty array.
+    A (C, N) array is a programme of C channels: its true peak is the largest over the channels (``channel_weights``
+    is accepted as by ``measure_loudness``; the peaks do not depend on it)."""
     from . import loudness, ops
     loudness.plan(sample_rate)
+    prog = _stage_programmes(wav, channel_weights)
+    if prog is not None:
+        single, x, lens, groups, weights = prog
+        if not groups:
+            return []
+        res = ops.loudness_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
+        out = [loudness.to_db(v) for v in res[:, 3]]
+        return out[0] if single else out
     single, x, n_rows, lens = _stage_rows(wav)
     if not lens:
         return []
@@ -256,28 +353,48 @@ def measure_true_peak(wav, sample_rate=44100):
     return out[0] if single else out
 
 
-def loudness_report(wav, sample_rate=44100):
+def loudness_report(wav, sample_rate=44100, channel_weights=None):
     """EBU R 128 figures of a float32 array (N,) -- or of every array of a list, in one device call -- all computed on the
     device (ops.loudness_report_rows; loudness.py has the definitions): a dict (a list of dicts) with ``integrated``
     (LUFS), ``loudness_range`` (LU), ``max_momentary`` and ``max_short_term`` (LUFS), ``sample_peak`` (dBFS) and
-    ``true_peak`` (dBTP).  -inf: nothing to measure (silence, too short a row); the range is then 0.0."""
+    ``true_peak`` (dBTP).  -inf: nothing to measure (silence, too short a row); the range is then 0.0.
+    A (C, N) array is ONE programme of C channels (ops.loudness_report_groups): one set of figures, the channels weighted by
+    ``channel_weights`` (default loudness.channel_weights(C)); lists may mix (N,) and (C, N) arrays."""
     from . import loudness, ops
     loudness.plan(sample_rate)
-    single, x, n_rows, lens = _stage_rows(wav)
-    if not lens:
-        return []
-    res = ops.loudness_report_rows(x, n_rows, sample_rate).cpu().numpy()
+    prog = _stage_programmes(wav, channel_weights)
+    if prog is not None:
+        single, x, lens, groups, weights = prog
+        if not groups:
+            return []
+        res = ops.loudness_report_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
+    else:
+        single, x, n_rows, lens = _stage_rows(wav)
+        if not lens:
+            return []
+        res = ops.loudness_report_rows(x, n_rows, sample_rate).cpu().numpy()
     out = [{"integrated": float(v[0]), "loudness_range": float(v[1]), "max_momentary": float(v[2]),
             "max_short_term": float(v[3]), "sample_peak": loudness.to_db(v[4]), "true_peak": loudness.to_db(v[5])}
            for v in res]
     return out[0] if single else out
 
 
-def measure_loudness(wav, sample_rate=44100):
-    """Integrated loudness (ITU-R BS.1770-4, one channel) in LUFS of a float32 array (N,) -- or of every array of a list,
-    in one device call -- measured on the device.  -inf: nothing above the gates (silence, or under 400 ms)."""
+def measure_loudness(wav, sample_rate=44100, channel_weights=None):
+    """Integrated loudness (ITU-R BS.1770-4) in LUFS of a float32 array (N,) -- or of every array of a list,
+    in one device call -- measured on the device.  -inf: nothing above the gates (silence, or under 400 ms).
+    A (C, N) array is ONE programme of C channels (1..8; loudness.py): one loudness, the channels weighted by
+    ``channel_weights`` (a list of C numbers >= 0; default loudness.channel_weights(C), BS.1770-4 Table 4).  Two identical
+    channels read 3.01 LU above the same signal as one channel.  Lists may mix (N,) and (C, N) arrays."""
     from . import loudness, ops
     loudness.plan(sample_rate)
+    prog = _stage_programmes(wav, channel_weights)
+    if prog is not None:
+        single, x, lens, groups, weights = prog
+        if not groups:
+            return []
+        res = ops.loudness_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
+        out = [float(v) for v in res[:, 0]]
+        return out[0] if single else out
     single = not isinstance(wav, (list, tuple))
     wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in ([wav] if single else wav)]
     if not wavs:
@@ -488,7 +605,8 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
-                      output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False):
+                      output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
+                      channel_weights=None):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
         ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
@@ -502,18 +620,30 @@ class VoiceFixer(nn.Module):
         normalised on the device to that integrated loudness (ITU-R BS.1770-4), limited by the SAMPLE-peak ceiling
         ``peak_ceiling`` (dBFS in [-20, 0]): one fp32 gain for the file (``apply_loudness``).  None (default): unchanged.
         ``true_peak=True`` (extension): ``peak_ceiling`` is read as dBTP, the gain is limited by the file's TRUE peak at the
-        output rate (measured on the device between the samples: loudness.py, EBU R 128's ceiling)."""
+        output rate (measured on the device between the samples: loudness.py, EBU R 128's ceiling).
+        ``channels="all"`` (extension): ``wav_10k`` is (C, N), 1 <= C <= 8, and (C, N') comes back: the model is mono, so
+        every channel goes through the path as ``restore_inmem(wav_10k[c])`` does -- the same segment cuts, mode-1 cut, seed,
+        rate conversions and peak rule per channel -- with the same segment of all channels in ONE batch; ``loudness`` is
+        then ONE linked gain for the file (BS.1770-4's sum over the channels weighted by ``channel_weights``, default
+        loudness.channel_weights(C); the largest peak over the channels: ``apply_loudness_groups``), which keeps the
+        balance between the channels.  "mix" / "first": a (C, N) input is averaged / cut to its first channel and restored
+        as one.  None (default): a 2-D input raises ValueError (it used to be misread as one long row)."""
         self._check_mode(mode, seed)
         rate_in, rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
         loud = _check_loudness(loudness, peak_ceiling, true_peak)
+        channels = _check_channels(channels, channel_weights)
+        wav, multi = _as_programme(wav_10k, channels, "restore_inmem")     # (C, n); C = 1 unless channels="all"
+        C = wav.shape[0]
+        if channel_weights is not None and len(channel_weights) != C:
+            raise ValueError("channel_weights: %d weights for %d channel(s)" % (len(channel_weights), C))
         pipe = self._get_pipe()
-        wav = np.asarray(wav_10k, dtype=np.float32)
-        n = wav.shape[0]
+        n = wav.shape[1]
         src = None           # the input converted to 44.1 kHz on the device (when it arrives at another rate)
         if rate_in != 44100:
-            x = torch.from_numpy(np.ascontiguousarray(wav))[None].to(pipe.device)
-            y, (n,) = convert_rows(x, [n], [rate_in])
-            src = y[0, :n]
+            x = torch.from_numpy(np.ascontiguousarray(wav)).to(pipe.device)
+            y, ns = convert_rows(x, [n] * C, [rate_in] * C)
+            n = ns[0]
+            src = y[:, :n]
         # Segment boundaries exactly as the reference's while-loop (base.py:117-120,137): full 30 s
         # segments, then a shorter tail.  Segments are independent in mode 0 (no carried state), so all
         # full segments of a long file go through the path as ONE batch (the reference runs them one
@@ -527,27 +657,33 @@ class VoiceFixer(nn.Module):
         full = [b for b in bounds if b[1] - b[0] == SEG_LENGTH]
         tail = [b for b in bounds if b[1] - b[0] != SEG_LENGTH]
 
+        per = max(1, self.segment_batch // C)      # segments per batch: row s * C + c is channel c of the batch's segment s
+
         def run():
             res = []
-            for i in range(0, len(full), self.segment_batch):
-                grp = full[i:i + self.segment_batch]
+            for i in range(0, len(full), per):
+                grp = full[i:i + per]
                 if src is None:
-                    seg = torch.from_numpy(np.stack([wav[a:b] for a, b in grp])).to(pipe.device)
+                    seg = torch.from_numpy(np.stack([wav[c, a:b] for a, b in grp for c in range(C)])).to(pipe.device)
                 else:
-                    seg = torch.stack([src[a:b] for a, b in grp])
-                out = self._restore_segments(pipe, seg, SEG_LENGTH, mode, your_vocoder_func, seed, range(i, i + len(grp)))
-                res.extend(out[k:k + 1] for k in range(len(grp)))
+                    seg = torch.stack([src[c, a:b] for a, b in grp for c in range(C)])
+                out = self._restore_segments(pipe, seg, SEG_LENGTH, mode, your_vocoder_func, seed,
+                                             [s for s in range(i, i + len(grp)) for _ in range(C)])
+                res.extend(out[k * C:(k + 1) * C] for k in range(len(grp)))
             for a, b in tail:
                 if src is None:
-                    seg = torch.from_numpy(np.ascontiguousarray(wav[a:b]))[None].to(pipe.device)
+                    seg = torch.from_numpy(np.ascontiguousarray(wav[:, a:b])).to(pipe.device)
                 else:
-                    seg = src[a:b][None].contiguous()
-                res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)]))
+                    seg = src[:, a:b].contiguous()
+                res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)] * C))
             out = torch.cat(res, -1)
             if rate_out != 44100:
-                y, (m,) = convert_output(out, [out.shape[-1]], rate_out)
-                out = y[:, :m]
-            if loud[0] is not None:
+                y, ms = convert_output(out, [out.shape[-1]] * C, rate_out)
+                out = y[:, :ms[0]]
+            if loud[0] is not None and multi:
+                out, _ = apply_loudness_groups(out, [out.shape[-1]] * C, [C], rate_out, *loud, true_peak=true_peak,
+                                               channel_weights=channel_weights)
+            elif loud[0] is not None:
                 out, _ = apply_loudness(out, [out.shape[-1]], rate_out, *loud, true_peak=true_peak)
             return out.cpu().numpy()  # (synchronises)
 
@@ -578,16 +714,25 @@ class VoiceFixer(nn.Module):
         return self._stream_pool[:max(1, int(streams))]
 
     def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None, loudness=None,
-                     peak_ceiling=-1.0, true_peak=False):
+                     peak_ceiling=-1.0, true_peak=False, channel_weights=None):
         """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates than
         44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) (loudness normalisation,) D2H of the result
         -- and of the per-row loudness results -- into pinned tensors, an event.  Nothing here waits for the device."""
         from . import ops
-        if len(item) not in (4, 5):
-            raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates)")
+        if len(item) not in (4, 5, 6):
+            raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates) or "
+                             "(tag, kind, host, lens, rates or None, groups)")
         tag, kind, host, lens = item[:4]
         lens = list(lens)
-        rates = _row_rates(item[4], len(lens)) if len(item) == 5 and item[4] is not None else None
+        rates = _row_rates(item[4], len(lens)) if len(item) >= 5 and item[4] is not None else None
+        groups = [int(g) for g in item[5]] if len(item) == 6 and item[5] is not None else None
+        if groups is not None:
+            starts = np.concatenate([[0], np.cumsum(groups)]).tolist()
+            if min(groups, default=0) < 1 or max(groups) > 8 or starts[-1] != len(lens) or \
+                    any(len(set(lens[a:b])) != 1 for a, b in zip(starts[:-1], starts[1:])) or \
+                    (rates is not None and any(len(set(rates[a:b])) != 1 for a, b in zip(starts[:-1], starts[1:]))):
+                raise ValueError("restore_batches: groups must be one channel count (1..8) per tag, summing to the rows, the "
+                                 "rows of a file adjacent, of one length and one rate")
         rate_out = _output_rate(output_sample_rate)
         if kind not in ("ragged", "samples") or len(lens) != host.shape[0] or max(lens) > host.shape[1]:
             raise ValueError("restore_batches: item must be (tag, 'ragged' | 'samples', host (B, >= max(lens)), lens (B))")
@@ -643,7 +788,11 @@ class VoiceFixer(nn.Module):
                 full, lens_out = convert_output(full, lens_out, rate_out)
             loud_host = None
             if loudness is not None:
-                full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling, true_peak)
+                if groups is not None:
+                    full, res = apply_loudness_groups(full, lens_out, groups, rate_out, loudness, peak_ceiling, true_peak,
+                                                      channel_weights)
+                else:
+                    full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling, true_peak)
                 loud_host = torch.empty(tuple(res.shape), dtype=torch.float64, pin_memory=True)
                 loud_host.copy_(res, non_blocking=True)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
@@ -654,7 +803,7 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
-                        loudness=None, peak_ceiling=-1.0, true_peak=False):
+                        loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -673,12 +822,17 @@ class VoiceFixer(nn.Module):
         generator yields ``(tag, out_host, lens_out, loud_host)``, ``loud_host`` a pinned float64 (B, 3) of {LUFS before,
         gain, sample peak} per row, copied with the batch.  ``true_peak=True``: the ceiling is a true-peak one (restore_inmem)
         and ``loud_host`` is (B, 4): {LUFS before, gain, sample peak, true peak}.
+        Multichannel files: an item may carry a 6th field, ``groups`` (the 5th may then be None): one channel count (1..8) per
+        tag; the channels of a file are adjacent rows of one length and rate, ``tag`` has one entry per FILE.  Every row goes
+        through the path on its own; ``loudness`` is then ONE linked gain per file (``apply_loudness_groups``, weights
+        ``channel_weights`` or loudness.channel_weights) and ``loud_host`` has one row per file: (G, 4).
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
         _check_loudness(loudness, peak_ceiling, true_peak)
+        _check_channels(None, channel_weights)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -710,7 +864,8 @@ class VoiceFixer(nn.Module):
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
                             inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed,
-                                                            output_sample_rate, loudness, peak_ceiling, true_peak)
+                                                            output_sample_rate, loudness, peak_ceiling, true_peak,
+                                                            channel_weights)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
@@ -719,7 +874,7 @@ class VoiceFixer(nn.Module):
 
             for item in batches:
                 inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed,
-                                                  output_sample_rate, loudness, peak_ceiling, true_peak))
+                                                  output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -740,7 +895,8 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
-                      sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False):
+                      sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False,
+                      channels=None, channel_weights=None):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -757,9 +913,22 @@ class VoiceFixer(nn.Module):
         ``sample_rate`` (extension): the rate of the inputs, one int or a list with one rate per wav; rows are staged at
         their own rates and converted on the device (one launch per distinct rate pair and batch), the batches are
         planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``, ``true_peak``: as
-        ``restore_inmem`` (each file is measured on its own row, whatever else its batch holds)."""
+        ``restore_inmem`` (each file is measured on its own row, whatever else its batch holds).
+        ``channels="all"`` (extension): items may be (N,) or (C, N), results are (C, N').  The channels of a file are adjacent
+        rows of one batch: the planning is by file, a file weighs C rows (ValueError when ``batch_size`` is smaller than the
+        largest C), and ``loudness`` is one linked gain per file (``restore_inmem``; ``channel_weights`` then applies to
+        every file and all must have that many channels).  "mix" / "first": (C, N) items are averaged / cut to their first
+        channel first.  None (default): as before."""
         self._check_mode(mode, seed)
         _check_loudness(loudness, peak_ceiling, true_peak)
+        if _check_channels(channels, channel_weights) is not None:
+            progs = [_as_programme(w, channels, "restore_batch")[0] for w in wavs]
+            if channels != "all":
+                wavs = [w[0] for w in progs]
+            else:
+                return self._restore_batch_programmes(progs, your_vocoder_func, batch_size, streams, ragged_ratio, mode, seed,
+                                                      sample_rate, output_sample_rate, loudness, peak_ceiling, true_peak,
+                                                      channel_weights)
         rates = _row_rates(sample_rate, len(wavs))
         _output_rate(output_sample_rate)
         native = all(r == 44100 for r in rates)
@@ -790,6 +959,48 @@ class VoiceFixer(nn.Module):
             ov = out_host.numpy()
             for r, k in enumerate(idx):
                 outs[k] = ov[r:r + 1, :lens_out[r]].copy()   # (the pinned block goes back to torch's host cache)
+        return outs
+
+    def _restore_batch_programmes(self, progs, your_vocoder_func, batch_size, streams, ragged_ratio, mode, seed, sample_rate,
+                                  output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights):
+        """``restore_batch(channels="all")``: ``progs`` are (C_i, N_i) arrays; planned by file, staged as adjacent rows."""
+        rates = _row_rates(sample_rate, len(progs))
+        _output_rate(output_sample_rate)
+        counts = [w.shape[0] for w in progs]
+        if channel_weights is not None and any(c != len(channel_weights) for c in counts):
+            raise ValueError("channel_weights: %d weights, but the files have %r channels" % (len(channel_weights), sorted(set(counts))))
+        n44 = [w.shape[1] if r == 44100 else audio_io.converted_length(w.shape[1], r, 44100) for w, r in zip(progs, rates)]
+        order = sorted(range(len(progs)), key=lambda i: n44[i])
+        outs = [None] * len(progs)
+        plan = plan_batches([n44[k] for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None,
+                            rows=[counts[k] for k in order])
+        native = all(r == 44100 for r in rates)
+
+        def staged():
+            for kind, grp in plan:
+                idx = [order[g] for g in grp]
+                groups = [counts[k] for k in idx]
+                lens = [progs[k].shape[1] for k in idx for _ in range(counts[k])]
+                host = torch.empty((len(lens), max(lens)), dtype=torch.float32, pin_memory=True)
+                hv = host.numpy()
+                r = 0
+                for k in idx:
+                    hv[r:r + counts[k], :progs[k].shape[1]] = progs[k]
+                    hv[r:r + counts[k], progs[k].shape[1]:] = 0.0
+                    r += counts[k]
+                yield (idx, kind, host, lens, None if native else [rates[k] for k in idx for _ in range(counts[k])], groups)
+
+        kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
+        if loudness is not None:
+            kw.update(loudness=loudness, peak_ceiling=peak_ceiling, channel_weights=channel_weights)
+            if true_peak:
+                kw["true_peak"] = True
+        for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
+            ov = out_host.numpy()
+            r = 0
+            for k in idx:
+                outs[k] = ov[r:r + counts[k], :lens_out[r]].copy()
+                r += counts[k]
         return outs
 
     @torch.no_grad()
@@ -878,7 +1089,7 @@ class VoiceFixer(nn.Module):
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
     def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None,
-                                  loudness=None, peak_ceiling=-1.0, true_peak=False):
+                                  loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
@@ -892,6 +1103,8 @@ class VoiceFixer(nn.Module):
             kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
             if true_peak:
                 kw["true_peak"] = True
+            if channel_weights is not None:
+                kw["channel_weights"] = channel_weights
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -928,11 +1141,19 @@ class VoiceFixer(nn.Module):
                 first = "%s: %s" % (type(exc).__name__, exc)
                 for it in bad:
                     tag, kind, host, lens = it[:4]
-                    rates = it[4] if len(it) == 5 else None
+                    rates = it[4] if len(it) >= 5 else None
+                    groups = it[5] if len(it) == 6 and it[5] is not None else None
+                    row0 = 0
                     for r in range(len(tag)):
-                        one = (tag[r:r + 1], kind, host[r:r + 1, :max(int(lens[r]), 1)], [lens[r]])
-                        if rates is not None:
-                            one += ([rates[r]],)
+                        if groups is not None:      # (a file of several channels is re-issued whole: rows a..b)
+                            a, b = row0, row0 + int(groups[r])
+                            row0 = b
+                            one = (tag[r:r + 1], kind, host[a:b, :max(int(lens[a]), 1)], list(lens[a:b]),
+                                   None if rates is None else list(rates[a:b]), [b - a])
+                        else:
+                            one = (tag[r:r + 1], kind, host[r:r + 1, :max(int(lens[r]), 1)], [lens[r]])
+                            if rates is not None:
+                                one += ([rates[r]],)
                         try:
                             for rec1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
                                 yield rec1
@@ -944,7 +1165,7 @@ class VoiceFixer(nn.Module):
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
                        skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False, loudness=None,
-                       peak_ceiling=-1.0, true_peak=False):
+                       peak_ceiling=-1.0, true_peak=False, channels=None, channel_weights=None):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -983,6 +1204,12 @@ class VoiceFixer(nn.Module):
         ``stats["loudness"]`` lists ``(output name, LUFS before, gain in dB)`` of the files written.  ``true_peak=True``:
         the ceiling is a true-peak one (restore_inmem) and ``stats["true_peak"]`` lists ``(output name, dBTP before, dBTP
         after)``.
+        ``channels`` (extension): None or "mix": files of several channels are averaged to one (the reference's
+        ``librosa.load``); "first": their first channel is restored; "all": EVERY channel is restored and the output is
+        written with the input's channel count (1..8; mixed counts in one folder are fine).  The count comes from the header
+        at scan time; the channels of a file are adjacent rows of one batch (a file weighs C rows in the planning and C * n
+        in the deal over ranks; a file with more channels than ``batch_size`` fails alone), ``loudness`` is one linked gain
+        per file (``restore_inmem``) and ``stats["loudness"]`` / ``stats["true_peak"]`` keep one entry per file.
         Returns the list of file names THIS rank wrote."""
         import threading
         import time
@@ -992,6 +1219,9 @@ class VoiceFixer(nn.Module):
         self._check_mode(mode, seed)
         rate_out = _output_rate(output_sample_rate)
         _check_loudness(loudness, peak_ceiling, true_peak)
+        channels = _check_channels(channels, channel_weights)
+        multi = channels == "all"
+        nch = {}               # index -> rows the file takes in a batch (its channel count with channels="all", else 1)
         rank, world = vdist.rank_world(rank, world)
         if io_threads is None:
             io_threads = vdist.default_io_threads(world)
@@ -1019,6 +1249,11 @@ class VoiceFixer(nn.Module):
             promises less than a restorable file (0 in a streamed / interrupted recording) is not believed: the file
             is decoded once to see what is really there."""
             try:
+                nch[i] = audio_io.wav_channels(paths[i]) if multi else 1
+                if not 1 <= nch[i] <= 8:
+                    raise RuntimeError("%d channels (1..8 are restored)" % nch[i])
+                if channel_weights is not None and multi and nch[i] != len(channel_weights):
+                    raise RuntimeError("%d channels, but channel_weights has %d" % (nch[i], len(channel_weights)))
                 if resample_on_device:
                     sr, n_nat, p_nat = audio_io.wav_info(paths[i])
                     n, promised = audio_io.converted_length(n_nat, sr, 44100), audio_io.converted_length(p_nat, sr, 44100)
@@ -1029,10 +1264,10 @@ class VoiceFixer(nn.Module):
                         truncated.append((i, promised, n))
                 if n < min_len:
                     if resample_on_device:
-                        n_nat = len(audio_io.load_wav_native(paths[i])[0])
+                        n_nat = audio_io.load_wav_native(paths[i])[0].shape[-1]
                         n = audio_io.converted_length(n_nat, sr, 44100)
                     else:
-                        n = len(audio_io.load_wav(paths[i], 44100))
+                        n = audio_io.load_wav(paths[i], 44100).shape[-1]
                 if resample_on_device:
                     stage[i] = (sr, n_nat) if on_device(sr) else (44100, n)
                 return n, None
@@ -1045,22 +1280,30 @@ class VoiceFixer(nn.Module):
             (audio_io.load_wav's steps, with the host resampling timed on its own; with resample_on_device the row stays
             at the file's rate unless the device does not take its ratio.)"""
             t0 = time.perf_counter()
-            x, sr = audio_io.load_wav_native(paths[i])
+            if channels in (None, "mix"):
+                x, sr = audio_io.load_wav_native(paths[i])
+            else:               # (row is then (C, n): the file's channels, or its first one)
+                x, sr = audio_io.load_wav_native(paths[i], mono=False)
+                x = audio_io.select_channels(x, channels)
+                x = x if multi else x[None]
+                if x.shape[0] != row.shape[0]:
+                    raise RuntimeError("the header promised %d channel(s), the decoder returned %d" % (row.shape[0], x.shape[0]))
             rs = 0.0
             if sr != 44100 and not (resample_on_device and stage[i][0] == sr):
                 t1 = time.perf_counter()
                 x = audio_io.resample_hq(x, sr, 44100)
                 rs = time.perf_counter() - t1
             x = np.ascontiguousarray(x, dtype=np.float32)
-            m = min(len(x), n)
-            row[:m] = x[:m]
-            row[m:] = 0.0
+            got = x.shape[-1]
+            m = min(got, n)
+            row[..., :m] = x[..., :m]
+            row[..., m:] = 0.0
             with lock:
                 cnt["decode_s"] += time.perf_counter() - t0
                 cnt["resample_s"] += rs
-                if len(x) != n and not any(t[0] == i for t in truncated):
+                if got != n and not any(t[0] == i for t in truncated):
                     sr_row = row_rate(i)
-                    truncated.append((i, audio_io.converted_length(n, sr_row, 44100), audio_io.converted_length(len(x), sr_row, 44100)))
+                    truncated.append((i, audio_io.converted_length(n, sr_row, 44100), audio_io.converted_length(got, sr_row, 44100)))
             return m
 
         def row_rate(i):
@@ -1071,7 +1314,10 @@ class VoiceFixer(nn.Module):
             final = os.path.join(outfolder, names[i])
             part = os.path.join(outfolder, ".part-%d-%s" % (os.getpid(), names[i]))   # (same extension: save_wave picks the container from it)
             try:
-                audio_io.save_wave(row, part, rate_out)
+                if multi:
+                    audio_io.save_wave(row, part, rate_out, channels_first=True)
+                else:
+                    audio_io.save_wave(row, part, rate_out)
                 os.replace(part, final)
             except BaseException:
                 if os.path.exists(part):
@@ -1094,33 +1340,51 @@ class VoiceFixer(nn.Module):
             for i, (n, why) in enumerate(scanned):
                 if why is None and n < min_len:
                     why = "too short to restore: %d samples at 44.1 kHz (mode %d needs >= %d)" % (n, mode, min_len)
+                if why is None and nch[i] > batch_size:
+                    why = "%d channels do not fit a batch of %d rows (the channels of a file share one batch)" % (nch[i], batch_size)
                 if why is not None:
                     if i % world == rank:
                         failed.append((i, why))
                 else:
                     usable.append(i)
             lengths = {i: scanned[i][0] for i in usable}
-            owner = vdist.deal_files([lengths[i] for i in usable], world)
+            owner = vdist.deal_files([lengths[i] * nch[i] for i in usable], world)
             mine = sorted((i for i, o in zip(usable, owner) if o == rank), key=lambda i: (lengths[i], i))
             if skip_existing:
                 # applied AFTER the deal and to this rank's own files only: the deal depends on nothing but the input headers,
                 # so ranks that look at the output folder at different moments still agree on who owns what
                 skipped = [names[i] for i in mine if os.path.exists(os.path.join(outfolder, names[i]))]
                 mine = [i for i in mine if not os.path.exists(os.path.join(outfolder, names[i]))]
-            plan = plan_batches([lengths[i] for i in mine], batch_size, ragged=your_vocoder_func is None)
+            plan = plan_batches([lengths[i] for i in mine], batch_size, ragged=your_vocoder_func is None,
+                                rows=[nch[i] for i in mine] if multi else None)
+
+            def rows_of(idx):
+                """File r of a batch of files ``idx`` has the staging / result rows rows_of(idx)[r] .. rows_of(idx)[r + 1] (one per
+                channel with channels="all", else one)."""
+                return np.concatenate([[0], np.cumsum([nch[i] for i in idx])]).tolist()
+
+            def item(idx, kind, host, real, rates):
+                """The ``restore_batches`` item of the files ``idx``: lengths and rates once per ROW; the channel counts go along
+                only with channels="all" (every other job yields the 4- or 5-field items it always did)."""
+                per_row = lambda v: [v[r] for r, i in enumerate(idx) for _ in range(nch[i])]     # noqa: E731
+                if multi:
+                    return (idx, kind, host, per_row(real), per_row(rates) if resample_on_device else None, [nch[i] for i in idx])
+                return (idx, kind, host, per_row(real)) + ((per_row(rates),) if resample_on_device else ())
 
             def submit_decode(b):
                 kind, grp = plan[b]
                 idx = [mine[g] for g in grp]
                 lens = [stage[i][1] if resample_on_device else lengths[i] for i in idx]     # (staging: at each row's rate)
+                row0 = rows_of(idx)
                 try:
-                    host = torch.empty((len(idx), max(lens)), dtype=torch.float32, pin_memory=self._pin_memory())
+                    host = torch.empty((row0[-1], max(lens)), dtype=torch.float32, pin_memory=self._pin_memory())
                 except Exception as e:    # noqa: BLE001 -- a staging block that cannot be had (host memory, pinning) costs THIS batch
                     for i in idx:
                         failed.append((i, "staging for a batch of %d x %d samples: %s: %s" % (len(idx), max(lens), type(e).__name__, e)))
                     return idx, kind, None, lens, []
                 hv = host.numpy()
-                return idx, kind, host, lens, [pool.submit(decode_into, i, hv[r], lens[r]) for r, i in enumerate(idx)]
+                return idx, kind, host, lens, [pool.submit(decode_into, i, hv[row0[r]:row0[r + 1]] if channels in ("first", "all")
+                                                           else hv[r], lens[r]) for r, i in enumerate(idx)]
 
             def decoded():
                 queue = [submit_decode(b) for b in range(min(ahead, len(plan)))]
@@ -1149,18 +1413,19 @@ class VoiceFixer(nn.Module):
                     if not keep:
                         continue
                     if len(keep) < len(idx):          # (rare) drop the failed rows: the batch shrinks, the others go on
-                        host = host[keep].contiguous()
+                        row0 = rows_of(idx)
+                        host = host[[q for r in keep for q in range(row0[r], row0[r + 1])]].contiguous()
                         if self._pin_memory():
                             host = host.pin_memory()
                         idx = [idx[r] for r in keep]
                     rates = [row_rate(i) for i in idx]
-                    tail = (rates,) if resample_on_device else ()
+                    row0 = rows_of(idx)
                     if kind == "samples" and min(real44) != max(real44):
-                        # equal-length bucket (several 30 s segments, plugin vocoder) with a truncated member: one batch per row
+                        # equal-length bucket (several 30 s segments, plugin vocoder) with a truncated member: one batch per file
                         for r in range(len(idx)):
-                            yield (idx[r:r + 1], kind, host[r:r + 1, :real[r]], real[r:r + 1]) + tuple(t[r:r + 1] for t in tail)
+                            yield item(idx[r:r + 1], kind, host[row0[r]:row0[r + 1], :real[r]], real[r:r + 1], rates[r:r + 1])
                         continue
-                    yield (idx, kind, host, real) + tail
+                    yield item(idx, kind, host, real, rates)
 
             writes = deque()           # per batch: the futures of its rows (their views keep the batch's pinned result alive)
             dev_failed = []
@@ -1184,6 +1449,8 @@ class VoiceFixer(nn.Module):
                     kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
                     if true_peak:
                         kw["true_peak"] = True
+                    if multi and channel_weights is not None:
+                        kw["channel_weights"] = channel_weights
                 for idx, out_host, lens_out, *extra in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func,
                                                                                        streams, mode, **kw):
                     ov = out_host.numpy()
@@ -1194,7 +1461,9 @@ class VoiceFixer(nn.Module):
                             if lv.shape[1] == 4:
                                 before = 20.0 * float(np.log10(lv[r, 3])) if lv[r, 3] > 0 else -float("inf")
                                 tp_rows[i] = (before, before + loud_rows[i][1])
-                    writes.append([(i, pool.submit(encode_from, ov[r:r + 1, :lens_out[r]], i)) for r, i in enumerate(idx)])
+                    row0 = rows_of(idx)
+                    writes.append([(i, pool.submit(encode_from, ov[row0[r]:row0[r + 1], :lens_out[row0[r]]], i))
+                                   for r, i in enumerate(idx)])
                     drain(ahead + 2)       # bounded backlog: pinned results do not pile up behind a slow disk
             except BatchSourceError as e:  # the source died: every batch it had handed over has been finished and is written below
                 source_error = str(e)
@@ -1208,7 +1477,7 @@ class VoiceFixer(nn.Module):
                     failed.append((i, "not processed: %s" % (source_error or "the device stage ended early")))
         if stats is not None:
             stats.update(rank=rank, world=world, files=len(written), folder_files=len(files), batches=len(plan),
-                         audio_s=sum(real_len[i] for i in done) / 44100.0, wall_s=time.perf_counter() - t_start,
+                         audio_s=sum(real_len[i] * nch[i] for i in done) / 44100.0, wall_s=time.perf_counter() - t_start,
                          decode_worker_s=cnt["decode_s"], encode_worker_s=cnt["encode_s"], resample_worker_s=cnt["resample_s"],
                          resample_on_device=bool(resample_on_device), output_sample_rate=rate_out,
                          device_waited_for_decode_s=cnt["stall_s"], io_threads=io_threads,
@@ -1224,14 +1493,30 @@ class VoiceFixer(nn.Module):
         return torch.cuda.is_available()
 
     def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
-                resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False):
+                resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
+                channel_weights=None):
         """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
         rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
         resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device);
-        ``loudness`` / ``peak_ceiling`` / ``true_peak``: as ``restore_inmem``."""
+        ``loudness`` / ``peak_ceiling`` / ``true_peak``: as ``restore_inmem``.  ``channels`` (extension): None or "mix": a file
+        of several channels is averaged to one (the reference's ``librosa.load``); "first": its first channel; "all": every
+        channel is restored (``restore_inmem(channels="all")``) and the output has the input's channel count."""
         rate_out = _output_rate(output_sample_rate)
         _check_loudness(loudness, peak_ceiling, true_peak)
         kw = {"true_peak": True} if true_peak else {}
+        if _check_channels(channels, channel_weights) in ("first", "all"):
+            x, sr = audio_io.load_wav_native(input, mono=False)
+            x = audio_io.select_channels(x, channels)
+            if sr != 44100 and not (resample_on_device and max(audio_io.rate_ratio(sr, 44100)) <= audio_io.DEVICE_MAX_RATIO):
+                x, sr = audio_io.resample_hq(x, sr, 44100), 44100
+            if channels == "all":
+                kw.update(channels="all", channel_weights=channel_weights)
+            out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
+                                            your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
+                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
+                                            **kw)
+            audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out, channels_first=True)
+            return
         if resample_on_device:
             x, sr = audio_io.load_wav_native(input)
             if sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) > audio_io.DEVICE_MAX_RATIO:

@@ -27,11 +27,17 @@ def to_int16(frames):
         return frames.astype(np.short)
 
 
-def save_wave(frames, fname, sample_rate=SR):
+def save_wave(frames, fname, sample_rate=SR, channels_first=False):
     """(1, N) or (N,) float waveform -> PCM16 WAV or FLAC by extension (voicefixer/tools/wav.py:9-37 writes through
-    soundfile, which picks the container from the extension the same way)."""
+    soundfile, which picks the container from the extension the same way).  ``channels_first=True``: ``frames`` is
+    (channels, N) with 1..8 channels whatever N (what ``load_wav(mono=False)`` and the multichannel restore calls return);
+    without it only (1, N) and (2, N) are recognised as channels-first, as the reference does."""
     frames = np.asarray(frames)
-    if frames.ndim == 1:
+    if channels_first:
+        if frames.ndim != 2 or not 1 <= frames.shape[0] <= 8:
+            raise ValueError("save_wave: channels_first takes (channels, N) with 1..8 channels (got shape %r)" % (frames.shape,))
+        frames = frames.T
+    elif frames.ndim == 1:
         frames = frames[..., None]
     elif frames.ndim == 2 and frames.shape[0] < frames.shape[1] and frames.shape[0] <= 2:
         frames = frames.T  # (channels, N) -> (N, channels), as the reference's (1, N) output
@@ -48,9 +54,10 @@ def save_wave(frames, fname, sample_rate=SR):
     wavfile.write(fname, sample_rate, pcm if pcm.shape[1] > 1 else pcm[:, 0])
 
 
-def _riff_info(path):
+def _riff_info(path, channels=False):
     """(sample_rate, frames, frames the header promises) of a RIFF/WAVE file from its ``fmt `` and ``data`` chunk headers alone
-    -- any bit depth (scipy's memory-mapped read refuses 24-bit PCM, a very common studio format)."""
+    -- any bit depth (scipy's memory-mapped read refuses 24-bit PCM, a very common studio format).  ``channels``: the channel
+    count of the ``fmt `` chunk instead."""
     with open(path, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] not in (b"RIFF", b"RF64") or head[8:12] != b"WAVE":
@@ -63,7 +70,9 @@ def _riff_info(path):
             cid, size = ck[:4], struct.unpack("<I", ck[4:])[0]
             if cid == b"fmt ":
                 fmt = f.read(size + (size & 1))
-                _, _, sr, _, block_align, _ = struct.unpack("<HHIIHH", fmt[:16])
+                _, nch, sr, _, block_align, _ = struct.unpack("<HHIIHH", fmt[:16])
+                if channels:
+                    return int(nch)
             elif cid == b"data":
                 if not block_align:
                     raise RuntimeError("WAV data chunk before the fmt chunk: %s" % path)
@@ -92,6 +101,25 @@ def wav_info(path):
     else:
         sr, n, promised = _riff_info(path)
     return int(sr), n, (n if promised is None else promised)
+
+
+def wav_channels(path):
+    """Channel count of a WAV / FLAC file from its header alone."""
+    if str(path).lower().endswith(".flac"):
+        from . import flac
+        return int(flac.info(path)[1])
+    return _riff_info(path, channels=True)
+
+
+def select_channels(x, channels):
+    """What a ``channels=`` argument makes of a decoded file (``load_wav(mono=False)``: (N,) or (C, N)): None / "mix": the
+    average of the channels (librosa's down-mix), (N,); "first": channel 0, (N,); "all": every channel, (C, N)."""
+    x = np.asarray(x)
+    if channels == "all":
+        return x[None] if x.ndim == 1 else x
+    if x.ndim == 1:
+        return x
+    return np.ascontiguousarray(x[0]) if channels == "first" else x.mean(axis=0)
 
 
 def wav_length(path, sample_rate=SR, with_promise=False):

@@ -1,4 +1,4 @@
-// vfx_loudness.hip -- integrated loudness (ITU-R BS.1770-4, one channel) of B rows and the gain that normalises it
+// vfx_loudness.hip -- integrated loudness (ITU-R BS.1770-4) of B rows, or of programmes of several rows, and the gain that normalises it
 // (vfx_loudness_rows_f32), its true peak and its EBU R 128 report.  Definition, chunk scan and measured cost: DESIGN.md 3.10, 3.11.
 //
 //   K-weighting: two cascaded biquads (shelf, then high-pass), transposed direct form II, fp32.  Quarter q = sum of the
@@ -375,19 +375,43 @@ __global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restri
 
 // RS = 3: result[r] = {L, g, P}, the gain limited by the sample peak P.  RS = 4: result[r] = {L, g, P, TP}, TP = max(P, the
 // row's true-peak partials of lk_truepeak_kernel), the gain limited by TP.
-template <int RS>
+//
+// GRP (a programme of adjacent rows per workgroup): workgroup g owns rows [start[g], start[g + 1]), all of
+// the length of the first; peaks and true-peak partials are folded over all of them, z_j sums the rows' quarter sums times
+// their weights in ascending row order (fp64; one row of weight 1.0: the bits of the per-row form), result[g] = {L, g, P, TP}
+// and, where rowres is given, the same four values once per row of the programme for lk_apply_kernel<., 4>.
+struct lk_grp {
+    const int* start;             // [G + 1]  first row of every programme, start[G] = B
+    const double* weight;         // [B]      channel weight of every row
+    double* rowres;               // [B][4]   the programme's result repeated per row (NULL: not written)
+    int B;
+};
+
+template <int RS, bool GRP = false>
 __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n_rows, long long n_max, int S, int hop,
                                                        double target, double ceiling_db, double* __restrict__ result,
-                                                       lk_ws w, lk_tp t) {
+                                                       lk_ws w, lk_tp t, lk_grp grp) {
     __shared__ double rs[LK_T];
     __shared__ long long rc[LK_T];
     __shared__ float rp[LK_T];
-    const int r = blockIdx.x, c = threadIdx.x;
-    long long n = n_rows[r];
+    const int c = threadIdx.x;
+    int r = blockIdx.x, r1 = r + 1;
+    if (GRP) {                                            // (whatever start holds, the rows stay inside [0, B])
+        r = grp.start[blockIdx.x];
+        r1 = grp.start[blockIdx.x + 1];
+        r = r < 0 ? 0 : (r > grp.B ? grp.B : r);
+        r1 = r1 < r ? r : (r1 > grp.B ? grp.B : r1);
+    }
+    long long n = !GRP || r < r1 ? n_rows[r] : 0;
     n = n < 0 ? 0 : (n > n_max ? n_max : n);
     const long long nspan = (n + (long long)LK_T * S - 1) / ((long long)LK_T * S);
     float pk = 0.f;
-    for (long long j = c; j < nspan; j += LK_T) pk = fmaxf(pk, w.peak[(long long)r * w.nspans + j]);
+    if (GRP) {
+        for (int rr = r; rr < r1; ++rr)
+            for (long long j = c; j < nspan; j += LK_T) pk = fmaxf(pk, w.peak[(long long)rr * w.nspans + j]);
+    } else {
+        for (long long j = c; j < nspan; j += LK_T) pk = fmaxf(pk, w.peak[(long long)r * w.nspans + j]);
+    }
     rp[c] = pk;
     __syncthreads();
     for (int h = LK_T / 2; h > 0; h >>= 1) {
@@ -399,9 +423,11 @@ __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n
     if (RS == 4) {
         float m = 0.f;
         const long long nt = t.R > 1 ? tp_tiles(n, t.R, t.c, t.Kal) : 0;
-        const float* __restrict__ pr = t.part + (long long)r * t.ntiles;
+        for (int rr = r; rr < r1; ++rr) {                 // (one row unless GRP)
+            const float* __restrict__ pr = t.part + (long long)rr * t.ntiles;
 #pragma unroll 8
-        for (long long j = c; j < nt; j += LK_T) m = fmaxf(m, pr[j]);     // (8 loads in flight: one workgroup, ~300 per lane for 30 min)
+            for (long long j = c; j < nt; j += LK_T) m = fmaxf(m, pr[j]); // (8 loads in flight: one workgroup, ~300 per lane for 30 min)
+        }
         __syncthreads();
         rp[c] = m;
         __syncthreads();
@@ -419,8 +445,19 @@ __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n
     double s1 = 0.0;
     long long c1 = 0;
     for (long long j = c; j < nblk; j += LK_T) {         // (each lane reads back only the z it wrote itself)
-        const double zj = (lk_quarter(parts, j, hop, S) + lk_quarter(parts, j + 1, hop, S) + lk_quarter(parts, j + 2, hop, S) +
-                           lk_quarter(parts, j + 3, hop, S)) * inv;
+        double zj;
+        if (GRP) {
+            double a = 0.0;
+            for (int rr = r; rr < r1; ++rr) {             // (ascending rows: a fixed order)
+                const double2* pc = w.parts + (long long)rr * w.nchunks;
+                a += grp.weight[rr] * (lk_quarter(pc, j, hop, S) + lk_quarter(pc, j + 1, hop, S) + lk_quarter(pc, j + 2, hop, S) +
+                                       lk_quarter(pc, j + 3, hop, S));
+            }
+            zj = a * inv;
+        } else {
+            zj = (lk_quarter(parts, j, hop, S) + lk_quarter(parts, j + 1, hop, S) + lk_quarter(parts, j + 2, hop, S) +
+                  lk_quarter(parts, j + 3, hop, S)) * inv;
+        }
         z[j] = zj;
         if (-0.691 + 10.0 * log10(zj) > -70.0) { s1 += zj; ++c1; }
     }
@@ -445,10 +482,18 @@ __global__ __launch_bounds__(LK_T) void lk_gate_kernel(const int* __restrict__ n
             const double lim = pow(10.0, ceiling_db / 20.0) / (RS == 4 ? tpk : peak);
             if (lim < g) g = lim;
         }
-        result[RS * r] = L;
-        result[RS * r + 1] = g;
-        result[RS * r + 2] = peak;
-        if (RS == 4) result[RS * r + 3] = tpk;
+        const int o = GRP ? blockIdx.x : r;
+        result[RS * o] = L;
+        result[RS * o + 1] = g;
+        result[RS * o + 2] = peak;
+        if (RS == 4) result[RS * o + 3] = tpk;
+        if (GRP && RS == 4 && grp.rowres)
+            for (int rr = r; rr < r1; ++rr) {
+                grp.rowres[4 * rr] = L;
+                grp.rowres[4 * rr + 1] = g;
+                grp.rowres[4 * rr + 2] = peak;
+                grp.rowres[4 * rr + 3] = tpk;
+            }
     }
 }
 
@@ -486,14 +531,24 @@ __device__ __forceinline__ unsigned long long lk_select(const unsigned long long
 // One workgroup per row, after lk_gate_kernel<4>: report[r] = {L, LRA, max momentary, max short-term, P, TP}.
 // qs [B][nqmax]: the row's quarter sums; st [B][nqmax]: its short-term energies, then their bit patterns as sort keys
 // (positive doubles order as their bits do; a block below a gate gets the key ~0 and is never counted).
+// GRP: one workgroup per programme, after lk_gate_kernel<4, true>: the quarter sums are Q_i = sum over the programme's rows of
+// weight * q_i (ascending rows, fp64), kept in the slices of its first row; res4 and report are indexed by programme.
+template <bool GRP>
 __global__ __launch_bounds__(LK_T) void lk_report_kernel(const int* __restrict__ n_rows, long long n_max, int S, int hop,
                                                          const double* __restrict__ res4, double* __restrict__ report,
                                                          double* __restrict__ qs, double* __restrict__ st,
-                                                         long long nqmax, lk_ws w) {
+                                                         long long nqmax, lk_ws w, lk_grp grp) {
     __shared__ double rs[LK_T];
     __shared__ long long rc[LK_T];
-    const int r = blockIdx.x, c = threadIdx.x;
-    long long n = n_rows[r];
+    const int c = threadIdx.x;
+    int r = blockIdx.x, r1 = r + 1;
+    if (GRP) {
+        r = grp.start[blockIdx.x];
+        r1 = grp.start[blockIdx.x + 1];
+        r = r < 0 ? 0 : (r > grp.B ? grp.B : r);
+        r1 = r1 < r ? r : (r1 > grp.B ? grp.B : r1);
+    }
+    long long n = !GRP || r < r1 ? n_rows[r] : 0;
     n = n < 0 ? 0 : (n > n_max ? n_max : n);
     const long long nq = n / hop;
     const long long nblk = nq > 3 ? nq - 3 : 0;
@@ -505,7 +560,15 @@ __global__ __launch_bounds__(LK_T) void lk_report_kernel(const int* __restrict__
     unsigned long long* key = reinterpret_cast<unsigned long long*>(e);
     double zm = -1.0;                                     // (max is exact: any order gives the same bits)
     for (long long j = c; j < nblk; j += LK_T) zm = fmax(zm, z[j]);
-    for (long long j = c; j < nq; j += LK_T) q[j] = lk_quarter(parts, j, hop, S);
+    if (GRP) {
+        for (long long j = c; j < nq; j += LK_T) {
+            double a = 0.0;
+            for (int rr = r; rr < r1; ++rr) a += grp.weight[rr] * lk_quarter(w.parts + (long long)rr * w.nchunks, j, hop, S);
+            q[j] = a;
+        }
+    } else {
+        for (long long j = c; j < nq; j += LK_T) q[j] = lk_quarter(parts, j, hop, S);
+    }
     __syncthreads();                                      // (q is read across lanes below)
     const double inv = 1.0 / ((double)LK_ST * hop);
     double em = -1.0, s1 = 0.0;
@@ -555,12 +618,13 @@ __global__ __launch_bounds__(LK_T) void lk_report_kernel(const int* __restrict__
         }
     }
     if (c == 0) {
-        report[6 * r] = res4[4 * r];
-        report[6 * r + 1] = lra;
-        report[6 * r + 2] = zm >= 0.0 ? -0.691 + 10.0 * log10(zm) : -INFINITY;
-        report[6 * r + 3] = em >= 0.0 ? -0.691 + 10.0 * log10(em) : -INFINITY;
-        report[6 * r + 4] = res4[4 * r + 2];
-        report[6 * r + 5] = res4[4 * r + 3];
+        const int o = GRP ? blockIdx.x : r;
+        report[6 * o] = res4[4 * o];
+        report[6 * o + 1] = lra;
+        report[6 * o + 2] = zm >= 0.0 ? -0.691 + 10.0 * log10(zm) : -INFINITY;
+        report[6 * o + 3] = em >= 0.0 ? -0.691 + 10.0 * log10(em) : -INFINITY;
+        report[6 * o + 4] = res4[4 * o + 2];
+        report[6 * o + 5] = res4[4 * o + 3];
     }
 }
 
@@ -629,12 +693,16 @@ static void lk_ext_layout(int B, long long n_max, int hop, bool report, size_t* 
     }
 }
 
-// mode 0: vfx_loudness_rows_f32 ({L, g, P});  1: with the true peak ({L, g, P, TP});  2: the report (measure only)
+// mode 0: vfx_loudness_rows_f32 ({L, g, P});  1: with the true peak ({L, g, P, TP});  2: the report (measure only).
+// G > 0 (modes 1 and 2): the rows form G programmes (group_start, weight: lk_grp), result / report have G rows.
 static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max, const double* coef,
                   const double* mpow, int S, int hop, int lookback, double target, double ceiling_db, const float* bank, int J,
-                  int R, int c, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream) {
+                  int R, int c, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream,
+                  int G = 0, const int32_t* group_start = nullptr, const double* weight = nullptr) {
     if (!x || !n_rows || !coef || !mpow || !result || !ws || B <= 0 || B > 65535 || n_max < 0 || n_max > INT32_MAX)
         return VFX_EINVAL;
+    const bool grouped = G != 0 || group_start || weight;
+    if (grouped && (G < 1 || G > B || !group_start || !weight || mode == 0)) return VFX_EINVAL;
     if (S < LK_P || S % LK_P != 0 || S > 8192 || hop < S || lookback < 1 || lookback > LK_T - 1) return VFX_EINVAL;
     if (x_stride < (B > 1 ? n_max : 0) || !std::isfinite(ceiling_db) || std::isinf(target)) return VFX_EINVAL;
     const bool apply = !std::isnan(target);
@@ -648,7 +716,9 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
     lk_ext e = {nullptr, nullptr, nullptr, nullptr, 0, 0};
     lk_layout(B, n_max, hop, S, &need, &w, (char*)ws);
     if (mode != 0) lk_ext_layout(B, n_max, hop, mode == 2, &more, &e, (char*)ws + need);
-    if (ws_bytes < need + more || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
+    const size_t rowres_bytes = grouped && mode == 1 ? lk_round((size_t)B * 4 * sizeof(double)) : 0;
+    if (ws_bytes < need + more + rowres_bytes || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
+    const lk_grp grp = {(const int*)group_start, weight, rowres_bytes ? (double*)((char*)ws + need + more) : nullptr, B};
     const lk_coef k = {(float)coef[0], (float)coef[1], (float)coef[2], (float)coef[3], (float)coef[4],
                        (float)coef[5], (float)coef[6], (float)coef[7], (float)coef[8], (float)coef[9]};
     hipStream_t s = (hipStream_t)stream;
@@ -679,14 +749,18 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
     } else {
         t.R = 1;                                          // (no partials: TP = P)
     }
-    if (mode == 0) hipLaunchKernelGGL(lk_gate_kernel<3>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
-                                      (long long)n_max, S, hop, target, ceiling_db, result, w, t);
-    else hipLaunchKernelGGL(lk_gate_kernel<4>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows, (long long)n_max, S,
-                            hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t);
+    if (mode == 0) hipLaunchKernelGGL((lk_gate_kernel<3, false>), dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
+                                      (long long)n_max, S, hop, target, ceiling_db, result, w, t, grp);
+    else if (!grouped) hipLaunchKernelGGL((lk_gate_kernel<4, false>), dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
+                                          (long long)n_max, S, hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t, grp);
+    else hipLaunchKernelGGL((lk_gate_kernel<4, true>), dim3((unsigned)G), dim3(LK_T), 0, s, (const int*)n_rows,
+                            (long long)n_max, S, hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t, grp);
     VFX_LAUNCHED();
     if (mode == 2) {
-        hipLaunchKernelGGL(lk_report_kernel, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows, (long long)n_max, S, hop,
-                           (const double*)e.res4, result, e.qs, e.st, e.nqmax, w);
+        if (!grouped) hipLaunchKernelGGL(lk_report_kernel<false>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
+                                         (long long)n_max, S, hop, (const double*)e.res4, result, e.qs, e.st, e.nqmax, w, grp);
+        else hipLaunchKernelGGL(lk_report_kernel<true>, dim3((unsigned)G), dim3(LK_T), 0, s, (const int*)n_rows,
+                                (long long)n_max, S, hop, (const double*)e.res4, result, e.qs, e.st, e.nqmax, w, grp);
         VFX_LAUNCHED();
     }
     if (apply) {
@@ -695,8 +769,8 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
         const bool vo = vx && vfx_aligned16(out) && out_stride % 4 == 0;
         const dim3 ga((unsigned)nbx, (unsigned)B);
 #define AP_LAUNCH(VV, RS) hipLaunchKernelGGL((lk_apply_kernel<VV, RS>), ga, dim3(LK_T), 0, s, x, (long long)x_stride, \
-                                             (const int*)n_rows, (long long)n_max, (const double*)result, out, \
-                                             (long long)out_stride)
+                                             (const int*)n_rows, (long long)n_max, \
+                                             (const double*)(grp.rowres ? grp.rowres : result), out, (long long)out_stride)
         if (mode == 0) { if (vo) AP_LAUNCH(true, 3); else AP_LAUNCH(false, 3); }
         else { if (vo) AP_LAUNCH(true, 4); else AP_LAUNCH(false, 4); }
 #undef AP_LAUNCH
@@ -743,4 +817,38 @@ extern "C" int vfx_loudness_report_rows_f32(const float* x, int64_t x_stride, co
                                             vfx_stream_t stream) {
     return lk_run(2, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, NAN, -1.0, bank, J, R, c, nullptr, 0, report,
                   ws, ws_bytes, stream);
+}
+
+/* ---- programmes of several channels ------------------------------------------------------------------------ */
+
+extern "C" size_t vfx_loudness_groups_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J) {
+    if (B <= 0 || n_max < 0 || n_max > INT32_MAX || hop <= 0 || S <= 0 || J < 1 || J > TP_JMAX || (R != 1 && R != 2 && R != 4))
+        return 0;
+    size_t total = 0, more = 0;
+    lk_layout(B, n_max, hop, S, &total, nullptr, nullptr);
+    lk_ext_layout(B, n_max, hop, false, &more, nullptr, nullptr);
+    return total + more + lk_round((size_t)B * 4 * sizeof(double));
+}
+
+extern "C" int vfx_loudness_groups_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                       const int32_t* group_start, const double* weight, int G, const double* coef,
+                                       const double* mpow, int S, int hop, int lookback, double target, double ceiling_db,
+                                       const float* bank, int J, int R, int c, float* out, int64_t out_stride, double* result,
+                                       void* ws, size_t ws_bytes, vfx_stream_t stream) {
+    if (G < 1 || !group_start || !weight) return VFX_EINVAL;
+    return lk_run(1, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, target, ceiling_db, bank, J, R, c, out,
+                  out_stride, result, ws, ws_bytes, stream, G, group_start, weight);
+}
+
+extern "C" size_t vfx_loudness_report_groups_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J) {
+    return vfx_loudness_report_workspace_bytes(B, n_max, hop, S, R, J);
+}
+
+extern "C" int vfx_loudness_report_groups_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                              const int32_t* group_start, const double* weight, int G, const double* coef,
+                                              const double* mpow, int S, int hop, int lookback, const float* bank, int J, int R,
+                                              int c, double* report, void* ws, size_t ws_bytes, vfx_stream_t stream) {
+    if (G < 1 || !group_start || !weight) return VFX_EINVAL;
+    return lk_run(2, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, NAN, -1.0, bank, J, R, c, nullptr, 0, report,
+                  ws, ws_bytes, stream, G, group_start, weight);
 }

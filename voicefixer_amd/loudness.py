@@ -1,4 +1,4 @@
-"""Loudness normalisation of restored audio (ITU-R BS.1770-4 integrated loudness, one channel): the host half.
+"""Loudness normalisation of restored audio (ITU-R BS.1770-4 integrated loudness): the host half.
 
 The measurement and the gain run on the device (``vfx_loudness_rows_f32``, csrc/vfx_loudness.hip; ``ops.loudness_rows``);
 this module designs what the kernel is given, in float64, once per rate:
@@ -28,6 +28,23 @@ integrated measurement, the maximum momentary loudness is the largest -0.691 + 1
 loudness the largest of theirs, and the loudness range LRA is taken over the short-term values above -70 LUFS and above
 the loudness of their mean energy - 20 LU: sorted ascending (n values s), LRA = s[((n-1) 95 + 50) // 100] -
 s[((n-1) + 5) // 10]; 0.0 when no block survives, -inf for a maximum without a block.
+
+Programmes of several channels (``vfx_loudness_groups_f32``, ``vfx_loudness_report_groups_f32``).  A
+programme is C rows of equal length n at fs, 1 <= C <= 8, with weights G_c >= 0.  With q_{c,i} the quarter sums, P_c the
+sample peak and TP_c the true peak of channel c as defined above:
+
+  * block energy  z_j = (sum_c G_c (q_{c,j} + q_{c,j+1} + q_{c,j+2} + q_{c,j+3})) * 1/(4 hop), channels summed in ascending
+    c in float64 (C = 1, G = 1.0: bit for bit the z_j of one row); both gates and L exactly as for one row on these z_j,
+    L = -inf when no block passes;
+  * P = max_c P_c, TP = max_c TP_c -- channels of weight 0 included: an LFE channel can clip too;
+  * g = min(10^((T - L)/20), 10^(ceiling/20) / (TP or P)), 1 when L = -inf; every channel's output is float32(g) x_c, ONE
+    factor for the programme: the balance between the channels is kept;
+  * report: the programme quarter sums are Q_i = sum_c G_c q_{c,i} (ascending c, float64); the maximum short-term loudness
+    and the LRA are the recipe above on Q, the maximum momentary loudness the largest z_j (ungated), the peaks P and TP.
+
+``channel_weights(C)`` are the weights of BS.1770-4 Table 4 in the WAVE / FLAC channel order (L R C LFE Ls Rs ...: the
+surrounds weigh 1.41, the LFE 0).  Two identical channels therefore read 10 log10 2 = 3.0103 LU above the same signal as
+one channel: that is the recommendation's sum over channels, not an error.
 """
 import math
 
@@ -41,6 +58,12 @@ SPAN = 256                    # chunks per workgroup of the kernel (LK_T)
 NPOW = 16                     # M^(2^i), i < NPOW (LK_NPOW)
 TARGET_RANGE = (-70.0, 0.0)   # LUFS, [lo, hi)
 CEILING_RANGE = (-20.0, 0.0)  # dBFS, [lo, hi]
+MAX_CHANNELS = 8
+_SURROUND = 1.41              # BS.1770-4 Table 4 (Ls, Rs)
+_TABLE4 = {1: [1.0], 2: [1.0, 1.0], 3: [1.0, 1.0, 1.0], 4: [1.0, 1.0, _SURROUND, _SURROUND],
+           5: [1.0, 1.0, 1.0, _SURROUND, _SURROUND], 6: [1.0, 1.0, 1.0, 0.0, _SURROUND, _SURROUND],
+           7: [1.0, 1.0, 1.0, 0.0, 1.0, _SURROUND, _SURROUND], 8: [1.0, 1.0, 1.0, 0.0, 1.0, 1.0, _SURROUND, _SURROUND]}
+CHANNEL_MODES = ("mix", "first", "all")
 
 
 def oversampling(fs):
@@ -171,3 +194,33 @@ def check_ceiling(ceiling_db):
     if not CEILING_RANGE[0] <= v <= CEILING_RANGE[1]:
         raise ValueError("peak_ceiling must be in [-20, 0] dBFS (got %r)" % ceiling_db)
     return v
+
+
+def check_channel_count(C):
+    """A channel count in 1..8."""
+    if isinstance(C, (bool, np.bool_)) or not isinstance(C, (int, np.integer)) or not 1 <= int(C) <= MAX_CHANNELS:
+        raise ValueError("a programme has 1..%d channels (got %r)" % (MAX_CHANNELS, C))
+    return int(C)
+
+
+def channel_weights(C, override=None):
+    """The channel weights G_c of a programme of C channels: BS.1770-4 Table 4 in the WAVE / FLAC channel order, or
+    ``override``: a list of C finite floats >= 0 (anything else raises ValueError)."""
+    C = check_channel_count(C)
+    if override is None:
+        return list(_TABLE4[C])
+    if isinstance(override, (str, bytes)) or not isinstance(override, (list, tuple, np.ndarray)) or len(override) != C:
+        raise ValueError("channel_weights must be a list of %d numbers >= 0 (got %r)" % (C, override))
+    out = [_number(v, "channel_weights[%d]" % i) for i, v in enumerate(override)]
+    if min(out) < 0.0:
+        raise ValueError("channel_weights must be >= 0 (got %r)" % (override,))
+    return out
+
+
+def check_channels(channels, allow_none=True):
+    """``channels``: None (only where a default exists), "mix", "first" or "all"."""
+    if channels is None and allow_none:
+        return None
+    if not isinstance(channels, str) or channels not in CHANNEL_MODES:
+        raise ValueError("channels must be 'mix', 'first' or 'all' (got %r)" % (channels,))
+    return channels

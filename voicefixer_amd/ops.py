@@ -6,6 +6,7 @@ strides and calls the C entry point on ``torch.cuda.current_stream()``.  No torc
 arithmetic happens on this path.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -636,4 +637,106 @@ def loudness_report_rows(x, n_rows, rate):
     check(h.vfx_loudness_report_rows_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, coef, _ptr(mpow),
                                          p["S"], p["hop"], p["lookback"], _ptr(bank), J, R, c, _ptr(rep), _ptr(ws), nb,
                                          _stream()), "vfx_loudness_report_rows_f32")
+    return rep
+
+
+_LOUDNESS_GROUPS = {}
+
+
+def _loudness_groups_plan(x, n_rows, groups, weights):
+    """Host checks of a grouped call and its cached uploads: (device n_rows, group_start, weight, G).  The uploads are keyed
+    by (device, groups, weights, lengths): a repeated call with the lengths as a LIST uploads nothing and never waits for
+    the device; a device ``n_rows`` is read back for the checks (one synchronising copy per call)."""
+    from . import loudness
+    B = x.shape[0]
+    groups = [loudness.check_channel_count(g) for g in groups]
+    if sum(groups) != B:
+        raise ValueError("loudness_groups: the channel counts sum to %d, the batch has %d rows" % (sum(groups), B))
+    lens = [int(v) for v in (n_rows.tolist() if torch.is_tensor(n_rows) else n_rows)]
+    if len(lens) != B:
+        raise ValueError("loudness_groups: %d lengths for %d rows" % (len(lens), B))
+    if weights is None:
+        weights = [w for g in groups for w in loudness.channel_weights(g)]
+    else:
+        weights = [float(w) for w in weights]
+        if len(weights) != B or not all(math.isfinite(w) and w >= 0.0 for w in weights):
+            raise ValueError("loudness_groups: weights must be %d finite numbers >= 0" % B)
+    start = [0]
+    for g in groups:
+        if len(set(lens[start[-1]:start[-1] + g])) != 1:
+            raise ValueError("loudness_groups: the rows of a programme must have one length (rows %d..%d have %r)"
+                             % (start[-1], start[-1] + g - 1, lens[start[-1]:start[-1] + g]))
+        start.append(start[-1] + g)
+    if min(lens) < 0 or max(lens) > x.shape[1]:
+        raise ValueError("loudness_groups: row lengths must be in [0, %d]" % x.shape[1])
+    key = (str(x.device), tuple(groups), tuple(weights), tuple(lens))
+    hit = _LOUDNESS_GROUPS.get(key)
+    if hit is None:
+        if len(_LOUDNESS_GROUPS) >= 64:
+            _LOUDNESS_GROUPS.clear()
+        hit = (torch.tensor(start, dtype=torch.int32).to(x.device), torch.tensor(weights, dtype=torch.float64).to(x.device),
+               torch.tensor(lens, dtype=torch.int32).to(x.device))
+        _LOUDNESS_GROUPS[key] = hit
+    return (n_rows if torch.is_tensor(n_rows) else hit[2]), hit[0], hit[1], len(groups)
+
+
+def loudness_groups(x, n_rows, groups, fs, target=None, peak_ceiling=-1.0, out=None, weights=None, true_peak=True):
+    """Integrated loudness of PROGRAMMES of several channels (vfx_loudness_groups_f32; loudness.py): the
+    rows of x (B, >= max n) are ``groups`` = [C_0, C_1, ...] adjacent channels per programme (each 1..8, summing to B), row
+    r holding n_rows[r] samples -- one length per programme.  ``n_rows`` as a LIST of ints is the non-blocking form: the
+    checks run on the list and the uploaded lengths, group starts and weights are cached, so a repeated call neither copies
+    nor waits.  A device int32 (B,) is accepted too, but it is read back to the host for the equal-length check on every
+    call, which synchronises with the device.  ``weights``: B channel weights (default: loudness.channel_weights of every programme).
+    Returns a device float64 (G, 4) of {L, gain, sample peak, true peak} per programme; with ``target`` every row is
+    scaled by its programme's float32(gain) into ``out`` (default: in place).  The launches of
+    loudness_rows(true_peak=True); ValueError before anything is launched on groups or lengths that do not fit.
+    ``true_peak=False``: nothing is oversampled (the entry point's R = 1 form, one launch fewer), the fourth value repeats
+    the sample peak and ``peak_ceiling`` is a sample-peak ceiling."""
+    from . import loudness
+    _need_cuda(x, out)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    target = loudness.check_target(target)
+    peak_ceiling = loudness.check_ceiling(peak_ceiling)
+    n_rows, start, wt, G = _loudness_groups_plan(x, n_rows, groups, weights)
+    _need_cuda(n_rows)
+    assert n_rows.dtype == torch.int32 and n_rows.numel() == x.shape[0]
+    p, mpow, coef, (bank, J, R, c) = _loudness_plan(x, fs)
+    if not loudness.check_true_peak(true_peak):
+        bank, J, R, c = mpow, 1, 1, 0                      # (R = 1: the bank is never read, must not be null)
+    if target is not None and out is None:
+        out = x
+    if out is not None:
+        assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == x.shape[0]
+        assert out.shape[1] >= x.shape[1]
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_groups_workspace_bytes(B, n_max, p["hop"], p["S"], R, J)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    res = torch.empty((G, 4), dtype=torch.float64, device=x.device)
+    check(h.vfx_loudness_groups_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, _ptr(start), _ptr(wt),
+                                    G, coef, _ptr(mpow), p["S"], p["hop"], p["lookback"],
+                                    float("nan") if target is None else target, peak_ceiling, _ptr(bank), J, R, c, _ptr(out),
+                                    (out.stride(0) if B > 1 else out.shape[1]) if out is not None else 0, _ptr(res),
+                                    _ptr(ws), nb, _stream()), "vfx_loudness_groups_f32")
+    return res
+
+
+def loudness_report_groups(x, n_rows, groups, fs, weights=None):
+    """Loudness report of programmes of several channels (vfx_loudness_report_groups_f32; arguments as loudness_groups): a
+    device float64 (G, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample
+    peak, true peak} per programme.  Measures only; the launches of loudness_report_rows."""
+    _need_cuda(x)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    n_rows, start, wt, G = _loudness_groups_plan(x, n_rows, groups, weights)
+    _need_cuda(n_rows)
+    assert n_rows.dtype == torch.int32 and n_rows.numel() == x.shape[0]
+    p, mpow, coef, (bank, J, R, c) = _loudness_plan(x, fs)
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_report_groups_workspace_bytes(B, n_max, p["hop"], p["S"], R, J)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    rep = torch.empty((G, 6), dtype=torch.float64, device=x.device)
+    check(h.vfx_loudness_report_groups_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, _ptr(start),
+                                           _ptr(wt), G, coef, _ptr(mpow), p["S"], p["hop"], p["lookback"], _ptr(bank), J, R,
+                                           c, _ptr(rep), _ptr(ws), nb, _stream()), "vfx_loudness_report_groups_f32")
     return rep
