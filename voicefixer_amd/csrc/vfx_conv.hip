@@ -147,6 +147,7 @@ struct ConvArgs {
     float mid_slope;        // leaky-ReLU between the two convolutions
     int rb_nq1;             // resblk4_kernel: quads of the first (dilated) half per tile = whole blocks of 4d columns x d
     int rs_pshift, rs_nseg; // resblk4s_kernel: log2 of the strip pitch P, segments of W = P - 4 positions per block of 4d
+    unsigned tw_rdiv;       // convtw_kernel: ceil(2^32 / stride), row -> (channel, phase) without a division
 };
 
 // Staging slots per thread.  The host picks KC (8 or 4) so that the activation tile never needs
@@ -1692,7 +1693,7 @@ extern "C" int vfx_convtr1d_f32(const vfx_tensor* x, const float* w_packed, cons
     // out[o] = x[q]*w[r] + x[q-1]*w[r+s],  u = o + pad = q*s + r   
     if (stride < 1 || stride > VFX_MAXPH) return VFX_EINVAL;
     if (act && act->w_wino4) {                    // the Winograd F(3,2) form (vfx_convtw.inc): 2/3 of the direct sum's MFMAs
-        const int rc = try_launch_convtw(x, act->w_wino4, bias, y, B, Cin, Cout, Lin, stride, act, (hipStream_t)stream);
+        const int rc = try_launch_convtw(x, w_packed, act->w_wino4, bias, y, B, Cin, Cout, Lin, stride, act, (hipStream_t)stream);
         if (rc != VFX_ENOTSUP) return rc;
     }
     const int pad = stride / 2 + stride % 2;
