@@ -436,3 +436,157 @@ def test_selfcheck_compare_and_report_on_made_up_stages(capsys):
     assert "above 1e-04" in buf.getvalue() and buf.getvalue().count("\n") == len(selfcheck.STAGES) + 2
     bad, _ = selfcheck.report({"default": same, "direct": base}, 1e-4, out=io.StringIO())
     assert bad == []
+
+
+# ---- the records the restore API threads its options and batch items through ---------------------------------------------------
+
+def test_output_record_defaults_and_kwargs():
+    """api._Output: a default job forwards no keyword; every option forwards exactly its own."""
+    O = api._Output
+    assert O().kwargs() == {} and O().rate_out == 44100
+    assert O(output_sample_rate=44100).kwargs() == {}
+    assert O(output_sample_rate=48000).kwargs() == {"output_sample_rate": 48000}
+    assert O(loudness=-16).kwargs() == {"loudness": -16.0, "peak_ceiling": -1.0}
+    assert O(loudness=-16, peak_ceiling=-3).kwargs() == {"loudness": -16.0, "peak_ceiling": -3.0}
+    assert O(loudness=-16, true_peak=True).kwargs() == {"loudness": -16.0, "peak_ceiling": -1.0, "true_peak": True}
+    assert O(loudness=-16, channel_weights=[1.0, 0.5]).kwargs() == {"loudness": -16.0, "peak_ceiling": -1.0,
+                                                                      "channel_weights": [1.0, 0.5]}
+    # the ceiling, the true-peak flag and the weights mean something with a target only
+    assert O(peak_ceiling=-3).kwargs() == {} and O(true_peak=True).kwargs() == {} and O(channel_weights=[1.0]).kwargs() == {}
+    # the seed belongs to mode 2
+    assert O(mode=2, seed=5).kwargs() == {"seed": 5} and O(mode=2, seed=0).kwargs() == {"seed": 0}
+    assert O(mode=0, seed=5).kwargs() == {} and O(mode=1, seed=5).kwargs() == {}
+    everything = O(22050, -23, -2.0, True, [1.0, 1.0], 2, 9)
+    assert everything.kwargs() == {"seed": 9, "output_sample_rate": 22050, "loudness": -23.0, "peak_ceiling": -2.0,
+                                   "true_peak": True, "channel_weights": [1.0, 1.0]}
+    assert (everything.rate_out, everything.loudness, everything.peak_ceiling, everything.true_peak, everything.seed) == \
+        (22050, -23.0, -2.0, True, 9)
+    for bad in (dict(output_sample_rate=0), dict(output_sample_rate=44100.5), dict(output_sample_rate=True), dict(loudness=3),
+                dict(loudness=-71), dict(loudness="loud"), dict(peak_ceiling=0.5), dict(loudness=-16, peak_ceiling=-21),
+                dict(true_peak=1), dict(true_peak=None), dict(channel_weights="11"), dict(channel_weights=[]),
+                dict(channel_weights=[1.0] * 9), dict(channel_weights=[1.0, -1.0]), dict(channel_weights=1.0)):
+        with pytest.raises(ValueError):
+            O(**bad)
+    O(channel_weights=[1.0, 0.5]).check_channel_counts([2, 2])
+    O().check_channel_counts([1, 6])
+    with pytest.raises(ValueError):
+        O(channel_weights=[1.0, 0.5]).check_channel_counts([2, 1])
+    # without a target or another rate the tail launches nothing and hands the rows back
+    assert O().finish("rows", [5, 6]) == ("rows", [5, 6], None) and O().finish("rows", [5, 5], [2]) == ("rows", [5, 5], None)
+
+
+def _same_item(a, b):
+    assert len(a) == len(b)
+    for u, v in zip(a, b):
+        assert (u is v) if isinstance(u, torch.Tensor) else (u == v), (u, v)
+
+
+def test_batch_record_round_trips_the_item_tuples():
+    B = api._Batch
+    host = torch.zeros((3, 10))
+    four = (["a", "b", "c"], "ragged", host, [10, 8, 9])
+    five = four + ([44100, 16000, 48000],)
+    six = (["a", "b"], "samples", host, [10, 7, 7], [48000, 16000, 16000], [1, 2])
+    for item in (four, five, six, four[:3] + ([7, 7, 7],) + (None, [3]), five[:4] + ([44100] * 3,)):
+        _same_item(B.parse(item).as_item(), item)
+    _same_item(B.parse(four + (None,)).as_item(), four)                   # no rates: the 4-field form
+    _same_item(B.parse(four + (None, None)).as_item(), four)              # groups=None: not a 6-field item
+    _same_item(B.parse(five + (None,)).as_item(), five)
+    _same_item(B.parse(four[:3] + ((10, 8, 9),)).as_item(), four)         # lens as any sequence -> a list
+    _same_item(B.parse(four + (16000,)).as_item(), four + ([16000] * 3,))  # one rate for every row
+    b = B.parse(six)
+    assert (b.tag, b.kind, b.lens, b.rates, b.groups) == (["a", "b"], "samples", [10, 7, 7], [48000, 16000, 16000], [1, 2])
+    assert b.host is host and b.starts() == [0, 1, 3] and B.parse(four).starts() == [0, 1, 2, 3]
+
+
+def test_batch_record_cuts_an_item_into_its_files():
+    B = api._Batch
+    host = torch.arange(6 * 12, dtype=torch.float32).reshape(6, 12)
+    lens, rates = [5, 5, 12, 9, 9, 9], [16000, 16000, 44100, 48000, 48000, 48000]
+    files = list(B.parse((["a", "b", "c"], "ragged", host, lens, rates, [2, 1, 3])).files())
+    assert len(files) == 3
+    for f, tag, (a, z) in zip(files, "abc", ((0, 2), (2, 3), (3, 6))):
+        assert f.tag == [tag] and f.kind == "ragged" and f.lens == lens[a:z] and f.rates == rates[a:z] and f.groups == [z - a]
+        assert torch.equal(f.host, host[a:z, :lens[a]])
+        assert len(f.as_item()) == 6
+        _same_item(B.parse(f.as_item()).as_item(), f.as_item())           # what the row-by-row re-issue hands to restore_batches
+    assert [f.rates for f in B.parse((["a", "b", "c"], "ragged", host, lens, None, [2, 1, 3])).files()] == [None] * 3
+    mono = list(B.parse((["a", "b", "c"], "ragged", host[:3], [5, 0, 12])).files())
+    assert [len(f.as_item()) for f in mono] == [4, 4, 4] and [f.tag for f in mono] == [["a"], ["b"], ["c"]]
+    assert [f.lens for f in mono] == [[5], [0], [12]] and [f.groups for f in mono] == [None] * 3
+    assert [tuple(f.host.shape) for f in mono] == [(1, 5), (1, 1), (1, 12)] and torch.equal(mono[2].host, host[2:3])   # (a row of 0 samples keeps one column)
+    with_rates = list(B.parse((["a", "b", "c"], "ragged", host[:3], [5, 7, 12], [8000, 44100, 48000])).files())
+    assert [f.as_item()[4] for f in with_rates] == [[8000], [44100], [48000]] and all(len(f.as_item()) == 5 for f in with_rates)
+
+
+def test_batch_record_refuses_what_the_device_stage_refused():
+    B = api._Batch
+    host = torch.zeros((4, 10))
+    good = (["a", "b"], "ragged", host, [6, 6, 8, 8], [16000, 16000, 48000, 48000], [2, 2])
+    B.parse(good)
+    bad = {"three fields": good[:3], "seven fields": good + (None,), "a group of 0": good[:5] + ([4, 0],),
+           "a group of 9": (["a"], "ragged", torch.zeros((9, 4)), [4] * 9, None, [9]),
+           "groups short of the rows": good[:5] + ([2, 1],), "groups beyond the rows": good[:5] + ([2, 3],),
+           "no groups at all": good[:5] + ([],),
+           "unequal lengths in a group": good[:3] + ([6, 7, 8, 8],) + good[4:],
+           "unequal rates in a group": good[:4] + ([16000, 44100, 48000, 48000],) + good[5:],
+           "another kind": (good[0], "padded") + good[2:], "more lens than rows": (["a"], "ragged", host, [6] * 5),
+           "fewer lens than rows": (["a"], "ragged", host, [6] * 3), "a row longer than host": (["a"], "ragged", host, [6, 6, 11, 6]),
+           "rates short of the rows": (["a"], "ragged", host, [6] * 4, [44100] * 3), "a rate of 0": (["a"], "ragged", host, [6] * 4, 0)}
+    for what, item in bad.items():
+        with pytest.raises(ValueError):
+            B.parse(item)
+            pytest.fail(what)
+
+
+def test_restore_batch_items_and_scatter_with_a_stub_device():
+    """restore_batch's host side: which items the device stage is handed -- 4 fields, 5 with mixed rates, 6 (the channel counts)
+    only with channels="all" -- and the scatter of the results back into the caller's order."""
+    items, calls = [], []
+
+    class Stub(api.VoiceFixer):
+        def __init__(self):
+            pass
+
+        def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, **kw):
+            calls.append(kw)
+            for item in batches:
+                items.append(item)
+                yield item[0], item[2].clone(), list(item[3])
+
+    vf = Stub()
+    rng = np.random.default_rng(0)
+    wavs = [rng.standard_normal(n).astype(np.float32) for n in (3000, 2000, 2500)]
+    outs = vf.restore_batch(wavs, batch_size=2)
+    assert calls == [{}] and [len(it) for it in items] == [4, 4]
+    assert [(it[0], it[1], it[3]) for it in items] == [([1, 2], "ragged", [2000, 2500]), ([0], "ragged", [3000])]
+    assert [o.shape for o in outs] == [(1, 3000), (1, 2000), (1, 2500)]
+    assert all(np.array_equal(o[0], w) for o, w in zip(outs, wavs))
+    assert np.array_equal(items[0][2].numpy()[0, 2000:], np.zeros(500, np.float32))        # the padding of a shorter row is cleared
+
+    del items[:], calls[:]
+    outs = vf.restore_batch(wavs, batch_size=4, sample_rate=[44100, 22050, 44100])         # 2000 samples at 22.05 kHz are 4000
+    assert calls == [{}] and [len(it) for it in items] == [5]
+    assert items[0][0] == [2, 0, 1] and items[0][3] == [2500, 3000, 2000] and items[0][4] == [44100, 44100, 22050]
+    assert all(np.array_equal(o[0], w) for o, w in zip(outs, wavs))
+
+    del items[:], calls[:]
+    progs = [rng.standard_normal((2, 3000)).astype(np.float32), wavs[1], rng.standard_normal((1, 2500)).astype(np.float32)]
+    outs = vf.restore_batch(progs, batch_size=2, channels="all", loudness=-20, mode=2, seed=4)
+    assert calls == [{"seed": 4, "loudness": -20.0, "peak_ceiling": -1.0}]
+    assert [len(it) for it in items] == [6, 6]
+    assert [(it[0], it[3], it[4], it[5]) for it in items] == [([1, 2], [2000, 2500], None, [1, 1]), ([0], [3000, 3000], None, [2])]
+    assert [o.shape for o in outs] == [(2, 3000), (1, 2000), (1, 2500)]
+    assert np.array_equal(outs[0], progs[0]) and np.array_equal(outs[1][0], progs[1]) and np.array_equal(outs[2], progs[2])
+
+    del items[:], calls[:]
+    outs = vf.restore_batch(progs, batch_size=3, channels="all", sample_rate=[44100, 48000, 44100], output_sample_rate=48000)
+    assert calls == [{"output_sample_rate": 48000}]
+    assert [(it[0], it[3], it[4], it[5]) for it in items] == [([1, 2], [2000, 2500], [48000, 44100], [1, 1]),
+                                                              ([0], [3000, 3000], [44100, 44100], [2])]
+    assert [o.shape for o in outs] == [(2, 3000), (1, 2000), (1, 2500)]
+
+    del items[:], calls[:]
+    outs = vf.restore_batch(progs, batch_size=3, channels="first")                         # one row per file again: 4 fields
+    assert calls == [{}] and [(len(it), it[0], it[3]) for it in items] == [(4, [1, 2, 0], [2000, 2500, 3000])]
+    assert [o.shape for o in outs] == [(1, 3000), (1, 2000), (1, 2500)] and np.array_equal(outs[0][0], progs[0][0])

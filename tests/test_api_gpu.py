@@ -864,6 +864,39 @@ def test_restore_batches_generator_order_and_gru_miss(vf):
     check(list(vf.restore_batches(iter(items), streams=1)))
 
 
+def test_reissue_after_a_gru_miss_carries_the_output_options(vf):
+    """The re-issue of the batches in flight runs with the options of the first issue: a 4-field item (rows of 20000 and 21000
+    samples) and a 6-field one (one 2-channel file of 22050 samples) with loudness=-16, true_peak=True and
+    output_sample_rate=48000 give the same tags, lengths, loudness shapes ((2, 4) per row, (1, 4) per file) and -- within
+    the RMS bound of test_restore_batches_generator_order_and_gru_miss -- the same waveforms whether or not a GRU hand-off is
+    missed on the way."""
+    pipe = vf._get_pipe()
+    rng = np.random.default_rng(41)
+    rows = torch.zeros((2, 21000), dtype=torch.float32, pin_memory=True)
+    for r, n in enumerate((20000, 21000)):
+        rows[r, :n] = torch.from_numpy((0.1 * rng.standard_normal(n)).astype(np.float32))
+    stereo = torch.from_numpy((0.1 * rng.standard_normal((2, 22050))).astype(np.float32)).pin_memory()
+    items = [(["a", "b"], "ragged", rows, [20000, 21000]), (["c"], "ragged", stereo, [22050, 22050], None, [2])]
+
+    def run():
+        return [(tag, out.numpy().copy(), list(lens_out), loud.numpy().copy()) for tag, out, lens_out, loud in
+                vf.restore_batches(iter(items), streams=2, loudness=-16, true_peak=True, output_sample_rate=48000)]
+
+    plain = run()
+    retries = getattr(pipe, "gru_retries", 0)
+    pipe.restorer._force_gru_miss = 1
+    again = run()
+    assert pipe.gru_retries == retries + 1
+    assert [t for t, _, _, _ in plain] == [t for t, _, _, _ in again] == [["a", "b"], ["c"]]
+    want_lens = [[audio_io.converted_length(n, 44100, 48000) for n in ls] for ls in ([20000, 21000], [22050, 22050])]
+    for (_, out0, lens0, loud0), (_, out1, lens1, loud1), ls, shape in zip(plain, again, want_lens, ((2, 4), (1, 4))):
+        assert lens0 == lens1 == ls and loud0.shape == loud1.shape == shape
+        for r, n in enumerate(ls):
+            err = _rms(out0[r, :n], out1[r, :n])
+            print("row %d of %r: rms %.3g" % (r, shape, err))
+            assert err < 2e-5 and np.abs(out0[r, :n]).max() > 1e-3
+
+
 def test_restore_folder_two_ranks_in_one_process_equal_the_unsharded_folder(vf, tmp_path):
     """rank= / world= on the real device path: the two halves dist.deal_files deals are disjoint, cover the folder, and every
     file equals (to one PCM16 step: other batch shapes) what the unsharded folder run writes; counters add up."""

@@ -85,18 +85,9 @@ def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=Fals
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
     start = time.time()
-    kw = {}
-    if output_sample_rate is not None:
-        kw["output_sample_rate"] = output_sample_rate
-    if resample_on_device:
-        kw["resample_on_device"] = True
-    if loudness is not None:
-        kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
-        if true_peak:
-            kw["true_peak"] = True
-    if channels is not None:
-        kw["channels"] = channels
-    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, **kw)
+    voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, output_sample_rate=output_sample_rate,
+                       resample_on_device=resample_on_device, loudness=loudness, peak_ceiling=peak_ceiling, true_peak=true_peak,
+                       channels=channels)
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 

@@ -113,6 +113,24 @@ def plan_stream_chunks(n, chunk, overlap, min_tail=1024):
     return [tuple(c) for c in plan]
 
 
+def _check_stream_mode(mode, what):
+    """The overlap-add modes (``restore_stream``, ``open_stream``) take modes 0 and 1."""
+    if mode == 2:
+        raise NotImplementedError("%s: mode=2 is not built -- its per-segment statistics have no overlap-add form" % what)
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0, 1 or 2")
+
+
+def _stream_geometry(chunk_seconds, overlap_seconds, mode):
+    """(chunk, overlap, min_tail) in 44.1 kHz samples of the overlap-add modes.  Mode 1's pre-filter returns 512 * (len // 512)
+    samples, so its chunks are a multiple of 512 long (every full chunk keeps its length) and its shortest tail is 1535
+    (``plan_stream_chunks``)."""
+    chunk, overlap = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
+    if mode == 1:
+        chunk -= chunk % 512
+    return chunk, overlap, 1535 if mode == 1 else 1024
+
+
 class StreamPlanner:
     """``plan_stream_chunks`` for a waveform whose length is not known yet: ``feed(n_new)`` announces ``n_new`` more
     samples and returns the chunks (start, length) that are settled now, ``finish()`` the rest.  Everything returned,
@@ -254,14 +272,117 @@ def apply_loudness_groups(full, lens, groups, rate, target, peak_ceiling=-1.0, t
     return out, res
 
 
-def _check_channels(channels, channel_weights=None):
+def _check_channels(channels):
     from . import loudness
-    if channel_weights is not None:
-        if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
-                or not 1 <= len(channel_weights) <= loudness.MAX_CHANNELS:
-            raise ValueError("channel_weights must be a list of 1..8 numbers >= 0, one per channel (got %r)" % (channel_weights,))
-        loudness.channel_weights(len(channel_weights), channel_weights)
     return loudness.check_channels(channels)
+
+
+class _Output:
+    """What happens to restored rows before they leave the device: the output rate, the loudness target with its ceiling
+    and channel weights, and mode 2's seed.  Built ONCE per public call from its keywords -- the checks are made here, before
+    anything touches the device -- and handed down as it is.  ``kwargs()`` is the one place that knows which keywords a
+    ``restore_batches`` call is given, ``finish()`` the one tail of the device stage."""
+    __slots__ = ("rate_out", "loudness", "peak_ceiling", "true_peak", "channel_weights", "seed")
+
+    def __init__(self, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None,
+                 mode=0, seed=None):
+        from . import loudness as ld
+        self.rate_out = _output_rate(output_sample_rate)
+        self.true_peak = ld.check_true_peak(true_peak)
+        self.loudness, self.peak_ceiling = ld.check_target(loudness), ld.check_ceiling(peak_ceiling)
+        if channel_weights is not None:
+            if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
+                    or not 1 <= len(channel_weights) <= ld.MAX_CHANNELS:
+                raise ValueError("channel_weights must be a list of 1..8 numbers >= 0, one per channel (got %r)" % (channel_weights,))
+            ld.channel_weights(len(channel_weights), channel_weights)
+        self.channel_weights = channel_weights
+        self.seed = seed if mode == 2 else None     # (modes 0 and 1 ignore a seed: VoiceFixer._check_mode)
+
+    def check_channel_counts(self, counts):
+        """``channel_weights`` is one list for every file of the call: each must have that many channels."""
+        if self.channel_weights is not None and any(c != len(self.channel_weights) for c in counts):
+            raise ValueError("channel_weights: %d weights, but the input has %r channel(s)"
+                             % (len(self.channel_weights), sorted(set(counts))))
+
+    def kwargs(self):
+        """The keywords that differ from ``restore_batches``' defaults and nothing else: a default job forwards none (a
+        stand-in for the device stage takes ``(batches, your_vocoder_func, streams, mode)`` only)."""
+        kw = {} if self.seed is None else {"seed": self.seed}
+        if self.rate_out != 44100:
+            kw["output_sample_rate"] = self.rate_out
+        if self.loudness is not None:
+            kw.update(loudness=self.loudness, peak_ceiling=self.peak_ceiling)
+            if self.true_peak:
+                kw.update(true_peak=True)
+            if self.channel_weights is not None:
+                kw["channel_weights"] = self.channel_weights
+        return kw
+
+    def finish(self, full, lens, groups=None):
+        """Restored 44.1 kHz device rows -> (rows, lengths, loudness results or None): ``convert_output`` when the rate differs,
+        then, with a target, ONE linked gain per file of ``groups`` adjacent channels (``apply_loudness_groups``) or, without
+        ``groups``, one gain per row (``apply_loudness``)."""
+        if self.rate_out != 44100:
+            full, lens = convert_output(full, lens, self.rate_out)
+        res = None
+        if self.loudness is not None and groups is not None:
+            full, res = apply_loudness_groups(full, lens, groups, self.rate_out, self.loudness, self.peak_ceiling,
+                                              self.true_peak, self.channel_weights)
+        elif self.loudness is not None:
+            full, res = apply_loudness(full, lens, self.rate_out, self.loudness, self.peak_ceiling, self.true_peak)
+        return full, lens, res
+
+
+class _Batch:
+    """One item of ``restore_batches``: ``tag`` one entry per FILE, ``host`` the staging rows, ``lens`` / ``rates`` per ROW
+    (``rates`` None: 44.1 kHz), ``groups`` the channel count of every file (None: one row each).  The tuple of 4, 5 or 6
+    fields stays what callers and stand-ins see (``parse`` / ``as_item``); the code in between works on this."""
+    __slots__ = ("tag", "kind", "host", "lens", "rates", "groups")
+
+    def __init__(self, tag, kind, host, lens, rates=None, groups=None):
+        self.tag, self.kind, self.host, self.lens, self.rates, self.groups = tag, kind, host, lens, rates, groups
+
+    @classmethod
+    def parse(cls, item):
+        """A checked record from a tuple as ``restore_batches`` documents it."""
+        if len(item) not in (4, 5, 6):
+            raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates) or "
+                             "(tag, kind, host, lens, rates or None, groups)")
+        b = cls(*item)
+        b.lens = lens = list(b.lens)
+        b.rates = rates = None if b.rates is None else _row_rates(b.rates, len(lens))
+        if b.groups is not None:
+            b.groups = groups = [int(g) for g in b.groups]
+            starts = b.starts()
+            if min(groups, default=0) < 1 or max(groups) > 8 or starts[-1] != len(lens) or \
+                    any(len(set(lens[a:z])) != 1 for a, z in zip(starts[:-1], starts[1:])) or \
+                    (rates is not None and any(len(set(rates[a:z])) != 1 for a, z in zip(starts[:-1], starts[1:]))):
+                raise ValueError("restore_batches: groups must be one channel count (1..8) per tag, summing to the rows, the "
+                                 "rows of a file adjacent, of one length and one rate")
+        if b.kind not in ("ragged", "samples") or len(lens) != b.host.shape[0] or max(lens) > b.host.shape[1]:
+            raise ValueError("restore_batches: item must be (tag, 'ragged' | 'samples', host (B, >= max(lens)), lens (B))")
+        return b
+
+    def starts(self):
+        """File r has the rows starts()[r] .. starts()[r + 1]."""
+        if self.groups is None:
+            return list(range(len(self.tag) + 1))
+        return np.concatenate([[0], np.cumsum(self.groups)]).tolist()
+
+    def as_item(self):
+        """The shortest tuple that carries the content."""
+        item = (self.tag, self.kind, self.host, self.lens)
+        if self.groups is not None:
+            return item + (self.rates, self.groups)
+        return item if self.rates is None else item + (self.rates,)
+
+    def files(self):
+        """One single-file batch per tag: that file's rows of ``host``, cut to its own length."""
+        starts = self.starts()
+        for r, (a, z) in enumerate(zip(starts[:-1], starts[1:])):
+            a, z = int(a), int(z)
+            yield _Batch(self.tag[r:r + 1], self.kind, self.host[a:z, :max(int(self.lens[a]), 1)], list(self.lens[a:z]),
+                         None if self.rates is None else list(self.rates[a:z]), None if self.groups is None else [z - a])
 
 
 def _as_programme(x, channels, what):
@@ -310,12 +431,6 @@ def _stage_programmes(wav, channel_weights):
     return single, torch.from_numpy(host).to(_device()), lens, groups, weights
 
 
-def _check_loudness(loudness_target, peak_ceiling, true_peak=False):
-    from . import loudness
-    loudness.check_true_peak(true_peak)
-    return loudness.check_target(loudness_target), loudness.check_ceiling(peak_ceiling)
-
-
 def _stage_rows(wav):
     """One array or a list of them -> (single, padded device rows (B, >= 1), device int32 lengths, lengths)."""
     single = not isinstance(wav, (list, tuple))
@@ -330,27 +445,35 @@ def _stage_rows(wav):
     return single, torch.from_numpy(host).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev), lens
 
 
+def _measure(wav, sample_rate, channel_weights, rows, groups, pick):
+    """The staging and dispatch the three measurements share: ``groups(x, lens, counts, weights)`` when an input is 2-D or
+    weights are given (every array one programme), else ``rows(x, n_rows)`` (every array one row); ``pick`` turns a line of
+    the float64 result into what the caller returns for that array."""
+    from . import loudness
+    loudness.plan(sample_rate)
+    prog = _stage_programmes(wav, channel_weights)
+    if prog is not None:
+        single, x, lens, counts, weights = prog
+        res = groups(x, lens, counts, weights) if counts else None
+    else:
+        single, x, n_rows, lens = _stage_rows(wav)
+        res = rows(x, n_rows) if lens else None
+    if res is None:
+        return []
+    out = [pick(v) for v in res.cpu().numpy()]
+    return out[0] if single else out
+
+
 def measure_true_peak(wav, sample_rate=44100, channel_weights=None):
     """True peak in dBTP (after ITU-R BS.1770-4 Annex 2; loudness.py has the definition) of a float32 array (N,) -- or of
     every array of a list, in one device call -- measured on the device.  -inf: an all-zero or empty array.
     A (C, N) array is a programme of C channels: its true peak is the largest over the channels (``channel_weights``
     is accepted as by ``measure_loudness``; the peaks do not depend on it)."""
     from . import loudness, ops
-    loudness.plan(sample_rate)
-    prog = _stage_programmes(wav, channel_weights)
-    if prog is not None:
-        single, x, lens, groups, weights = prog
-        if not groups:
-            return []
-        res = ops.loudness_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
-        out = [loudness.to_db(v) for v in res[:, 3]]
-        return out[0] if single else out
-    single, x, n_rows, lens = _stage_rows(wav)
-    if not lens:
-        return []
-    res = ops.loudness_rows(x, n_rows, sample_rate, true_peak=True).cpu().numpy()
-    out = [loudness.to_db(v) for v in res[:, 3]]
-    return out[0] if single else out
+    return _measure(wav, sample_rate, channel_weights,
+                    lambda x, n_rows: ops.loudness_rows(x, n_rows, sample_rate, true_peak=True),
+                    lambda x, lens, counts, weights: ops.loudness_groups(x, lens, counts, sample_rate, weights=weights),
+                    lambda v: loudness.to_db(v[3]))
 
 
 def loudness_report(wav, sample_rate=44100, channel_weights=None):
@@ -361,22 +484,12 @@ def loudness_report(wav, sample_rate=44100, channel_weights=None):
     A (C, N) array is ONE programme of C channels (ops.loudness_report_groups): one set of figures, the channels weighted by
     ``channel_weights`` (default loudness.channel_weights(C)); lists may mix (N,) and (C, N) arrays."""
     from . import loudness, ops
-    loudness.plan(sample_rate)
-    prog = _stage_programmes(wav, channel_weights)
-    if prog is not None:
-        single, x, lens, groups, weights = prog
-        if not groups:
-            return []
-        res = ops.loudness_report_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
-    else:
-        single, x, n_rows, lens = _stage_rows(wav)
-        if not lens:
-            return []
-        res = ops.loudness_report_rows(x, n_rows, sample_rate).cpu().numpy()
-    out = [{"integrated": float(v[0]), "loudness_range": float(v[1]), "max_momentary": float(v[2]),
-            "max_short_term": float(v[3]), "sample_peak": loudness.to_db(v[4]), "true_peak": loudness.to_db(v[5])}
-           for v in res]
-    return out[0] if single else out
+    return _measure(wav, sample_rate, channel_weights,
+                    lambda x, n_rows: ops.loudness_report_rows(x, n_rows, sample_rate),
+                    lambda x, lens, counts, weights: ops.loudness_report_groups(x, lens, counts, sample_rate, weights=weights),
+                    lambda v: {"integrated": float(v[0]), "loudness_range": float(v[1]), "max_momentary": float(v[2]),
+                               "max_short_term": float(v[3]), "sample_peak": loudness.to_db(v[4]),
+                               "true_peak": loudness.to_db(v[5])})
 
 
 def measure_loudness(wav, sample_rate=44100, channel_weights=None):
@@ -385,29 +498,11 @@ def measure_loudness(wav, sample_rate=44100, channel_weights=None):
     A (C, N) array is ONE programme of C channels (1..8; loudness.py): one loudness, the channels weighted by
     ``channel_weights`` (a list of C numbers >= 0; default loudness.channel_weights(C), BS.1770-4 Table 4).  Two identical
     channels read 3.01 LU above the same signal as one channel.  Lists may mix (N,) and (C, N) arrays."""
-    from . import loudness, ops
-    loudness.plan(sample_rate)
-    prog = _stage_programmes(wav, channel_weights)
-    if prog is not None:
-        single, x, lens, groups, weights = prog
-        if not groups:
-            return []
-        res = ops.loudness_groups(x, lens, groups, sample_rate, weights=weights).cpu().numpy()
-        out = [float(v) for v in res[:, 0]]
-        return out[0] if single else out
-    single = not isinstance(wav, (list, tuple))
-    wavs = [np.asarray(w, dtype=np.float32).reshape(-1) for w in ([wav] if single else wav)]
-    if not wavs:
-        return []
-    dev = _device()
-    lens = [len(w) for w in wavs]
-    host = np.zeros((len(wavs), max(max(lens), 1)), np.float32)
-    for r, w in enumerate(wavs):
-        host[r, :len(w)] = w
-    x = torch.from_numpy(host).to(dev)
-    res = ops.loudness_rows(x, torch.tensor(lens, dtype=torch.int32).to(dev), sample_rate).cpu().numpy()
-    out = [float(v) for v in res[:, 0]]
-    return out[0] if single else out
+    from . import ops
+    return _measure(wav, sample_rate, channel_weights,
+                    lambda x, n_rows: ops.loudness_rows(x, n_rows, sample_rate),
+                    lambda x, lens, counts, weights: ops.loudness_groups(x, lens, counts, sample_rate, weights=weights),
+                    lambda v: float(v[0]))
 
 
 class Vocoder(nn.Module):
@@ -629,13 +724,11 @@ class VoiceFixer(nn.Module):
         balance between the channels.  "mix" / "first": a (C, N) input is averaged / cut to its first channel and restored
         as one.  None (default): a 2-D input raises ValueError (it used to be misread as one long row)."""
         self._check_mode(mode, seed)
-        rate_in, rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
-        loud = _check_loudness(loudness, peak_ceiling, true_peak)
-        channels = _check_channels(channels, channel_weights)
-        wav, multi = _as_programme(wav_10k, channels, "restore_inmem")     # (C, n); C = 1 unless channels="all"
+        rate_in = _check_rate(sample_rate)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        wav, multi = _as_programme(wav_10k, _check_channels(channels), "restore_inmem")     # (C, n); C = 1 unless channels="all"
         C = wav.shape[0]
-        if channel_weights is not None and len(channel_weights) != C:
-            raise ValueError("channel_weights: %d weights for %d channel(s)" % (len(channel_weights), C))
+        job.check_channel_counts([C])
         pipe = self._get_pipe()
         n = wav.shape[1]
         src = None           # the input converted to 44.1 kHz on the device (when it arrives at another rate)
@@ -677,15 +770,8 @@ class VoiceFixer(nn.Module):
                     seg = src[:, a:b].contiguous()
                 res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)] * C))
             out = torch.cat(res, -1)
-            if rate_out != 44100:
-                y, ms = convert_output(out, [out.shape[-1]] * C, rate_out)
-                out = y[:, :ms[0]]
-            if loud[0] is not None and multi:
-                out, _ = apply_loudness_groups(out, [out.shape[-1]] * C, [C], rate_out, *loud, true_peak=true_peak,
-                                               channel_weights=channel_weights)
-            elif loud[0] is not None:
-                out, _ = apply_loudness(out, [out.shape[-1]], rate_out, *loud, true_peak=true_peak)
-            return out.cpu().numpy()  # (synchronises)
+            out, ms, _ = job.finish(out, [out.shape[-1]] * C, [C] if multi else None)
+            return out[:, :ms[0]].cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
 
@@ -713,29 +799,13 @@ class VoiceFixer(nn.Module):
             self._stream_pool.append(torch.cuda.Stream(device=pipe.device))
         return self._stream_pool[:max(1, int(streams))]
 
-    def _issue_batch(self, pipe, stream, item, mode, your_vocoder_func, seed=None, output_sample_rate=None, loudness=None,
-                     peak_ceiling=-1.0, true_peak=False, channel_weights=None):
-        """Queue ONE batch on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates than
-        44.1 kHz,) the launch sequence, (conversion to ``output_sample_rate``,) (loudness normalisation,) D2H of the result
-        -- and of the per-row loudness results -- into pinned tensors, an event.  Nothing here waits for the device."""
+    def _issue_batch(self, pipe, stream, batch, mode, your_vocoder_func, job):
+        """Queue ONE batch (a ``_Batch``) on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates
+        than 44.1 kHz,) the launch sequence, the tail ``job`` (an ``_Output``) asks for -- (conversion to the output rate,)
+        (loudness normalisation) -- D2H of the result and of the loudness results into pinned tensors, an event.  Nothing here
+        waits for the device."""
         from . import ops
-        if len(item) not in (4, 5, 6):
-            raise ValueError("restore_batches: item must be (tag, kind, host, lens) or (tag, kind, host, lens, rates) or "
-                             "(tag, kind, host, lens, rates or None, groups)")
-        tag, kind, host, lens = item[:4]
-        lens = list(lens)
-        rates = _row_rates(item[4], len(lens)) if len(item) >= 5 and item[4] is not None else None
-        groups = [int(g) for g in item[5]] if len(item) == 6 and item[5] is not None else None
-        if groups is not None:
-            starts = np.concatenate([[0], np.cumsum(groups)]).tolist()
-            if min(groups, default=0) < 1 or max(groups) > 8 or starts[-1] != len(lens) or \
-                    any(len(set(lens[a:b])) != 1 for a, b in zip(starts[:-1], starts[1:])) or \
-                    (rates is not None and any(len(set(rates[a:b])) != 1 for a, b in zip(starts[:-1], starts[1:]))):
-                raise ValueError("restore_batches: groups must be one channel count (1..8) per tag, summing to the rows, the "
-                                 "rows of a file adjacent, of one length and one rate")
-        rate_out = _output_rate(output_sample_rate)
-        if kind not in ("ragged", "samples") or len(lens) != host.shape[0] or max(lens) > host.shape[1]:
-            raise ValueError("restore_batches: item must be (tag, 'ragged' | 'samples', host (B, >= max(lens)), lens (B))")
+        kind, host, lens, rates, seed = batch.kind, batch.host, batch.lens, batch.rates, job.seed
         if rates is not None and all(r == 44100 for r in rates):
             rates = None
         lens_native = lens
@@ -784,22 +854,16 @@ class VoiceFixer(nn.Module):
                          for s0 in range(0, n, SEG_LENGTH)]
                 full = parts[0] if len(parts) == 1 else torch.cat(parts, -1)
                 lens_out = [full.shape[-1]] * len(lens)
-            if rate_out != 44100:
-                full, lens_out = convert_output(full, lens_out, rate_out)
+            full, lens_out, res = job.finish(full, lens_out, batch.groups)
             loud_host = None
-            if loudness is not None:
-                if groups is not None:
-                    full, res = apply_loudness_groups(full, lens_out, groups, rate_out, loudness, peak_ceiling, true_peak,
-                                                      channel_weights)
-                else:
-                    full, res = apply_loudness(full, lens_out, rate_out, loudness, peak_ceiling, true_peak)
+            if res is not None:
                 loud_host = torch.empty(tuple(res.shape), dtype=torch.float64, pin_memory=True)
                 loud_host.copy_(res, non_blocking=True)
             out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
             out_host.copy_(full, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-        return [item, out_host, lens_out, ev, loud_host]
+        return [batch, out_host, lens_out, ev, loud_host]
 
     @torch.no_grad()
     def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
@@ -831,8 +895,7 @@ class VoiceFixer(nn.Module):
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
-        _check_loudness(loudness, peak_ceiling, true_peak)
-        _check_channels(None, channel_weights)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -863,18 +926,15 @@ class VoiceFixer(nn.Module):
                     pipe.vocoder.read_f16_flag()
                     with pipe.fallback(e):
                         for q in range(len(inflight)):
-                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, seed,
-                                                            output_sample_rate, loudness, peak_ceiling, true_peak,
-                                                            channel_weights)
+                            inflight[q] = self._issue_batch(pipe, pool[0], inflight[q][0], mode, your_vocoder_func, job)
                         torch.cuda.synchronize(pipe.device)
                         pipe.check()
                     rec = inflight[0]
                 inflight.popleft()
-                return (rec[0][0], rec[1], rec[2]) + ((rec[4],) if loudness is not None else ())
+                return (rec[0].tag, rec[1], rec[2]) + ((rec[4],) if job.loudness is not None else ())
 
             for item in batches:
-                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], item, mode, your_vocoder_func, seed,
-                                                  output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights))
+                inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], _Batch.parse(item), mode, your_vocoder_func, job))
                 nb += 1
                 while len(inflight) > len(pool) + 1:
                     yield finish_oldest()
@@ -920,87 +980,46 @@ class VoiceFixer(nn.Module):
         every file and all must have that many channels).  "mix" / "first": (C, N) items are averaged / cut to their first
         channel first.  None (default): as before."""
         self._check_mode(mode, seed)
-        _check_loudness(loudness, peak_ceiling, true_peak)
-        if _check_channels(channels, channel_weights) is not None:
-            progs = [_as_programme(w, channels, "restore_batch")[0] for w in wavs]
-            if channels != "all":
-                wavs = [w[0] for w in progs]
-            else:
-                return self._restore_batch_programmes(progs, your_vocoder_func, batch_size, streams, ragged_ratio, mode, seed,
-                                                      sample_rate, output_sample_rate, loudness, peak_ceiling, true_peak,
-                                                      channel_weights)
-        rates = _row_rates(sample_rate, len(wavs))
-        _output_rate(output_sample_rate)
-        native = all(r == 44100 for r in rates)
-        n44 = [len(w) if r == 44100 else audio_io.converted_length(len(w), r, 44100) for w, r in zip(wavs, rates)]
-        order = sorted(range(len(wavs)), key=lambda i: n44[i])
-        outs = [None] * len(wavs)
-        plan = plan_batches([n44[k] for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None)
-
-        def staged():
-            for kind, grp in plan:
-                idx = [order[g] for g in grp]
-                lens = [len(wavs[k]) for k in idx]
-                # rows are padded in a PINNED staging buffer (torch caches pinned blocks) and uploaded without
-                # blocking the host, so that the next batch is staged while this one's copy and kernels run
-                host = torch.empty((len(idx), max(lens)), dtype=torch.float32, pin_memory=True)
-                hv = host.numpy()
-                for r, k in enumerate(idx):
-                    hv[r, :lens[r]] = wavs[k]
-                    hv[r, lens[r]:] = 0.0
-                yield (idx, kind, host, lens) if native else (idx, kind, host, lens, [rates[k] for k in idx])
-
-        kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
-        if loudness is not None:
-            kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
-            if true_peak:
-                kw["true_peak"] = True
-        for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
-            ov = out_host.numpy()
-            for r, k in enumerate(idx):
-                outs[k] = ov[r:r + 1, :lens_out[r]].copy()   # (the pinned block goes back to torch's host cache)
-        return outs
-
-    def _restore_batch_programmes(self, progs, your_vocoder_func, batch_size, streams, ragged_ratio, mode, seed, sample_rate,
-                                  output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights):
-        """``restore_batch(channels="all")``: ``progs`` are (C_i, N_i) arrays; planned by file, staged as adjacent rows."""
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        multi = _check_channels(channels) == "all"
+        progs = [_as_programme(w, channels, "restore_batch")[0] for w in wavs]     # (C_i, N_i); C_i = 1 unless channels="all"
         rates = _row_rates(sample_rate, len(progs))
-        _output_rate(output_sample_rate)
         counts = [w.shape[0] for w in progs]
-        if channel_weights is not None and any(c != len(channel_weights) for c in counts):
-            raise ValueError("channel_weights: %d weights, but the files have %r channels" % (len(channel_weights), sorted(set(counts))))
+        if multi:
+            job.check_channel_counts(counts)
+        native = all(r == 44100 for r in rates)
         n44 = [w.shape[1] if r == 44100 else audio_io.converted_length(w.shape[1], r, 44100) for w, r in zip(progs, rates)]
         order = sorted(range(len(progs)), key=lambda i: n44[i])
         outs = [None] * len(progs)
         plan = plan_batches([n44[k] for k in order], batch_size, ragged_ratio, ragged=your_vocoder_func is None,
-                            rows=[counts[k] for k in order])
-        native = all(r == 44100 for r in rates)
+                            rows=[counts[k] for k in order] if multi else None)
+
+        def rows_of(idx):
+            """(file, its first row, the row behind its last) of a batch of the files ``idx``: one row per channel."""
+            row0 = 0
+            for k in idx:
+                yield k, row0, row0 + counts[k]
+                row0 += counts[k]
 
         def staged():
             for kind, grp in plan:
                 idx = [order[g] for g in grp]
-                groups = [counts[k] for k in idx]
                 lens = [progs[k].shape[1] for k in idx for _ in range(counts[k])]
-                host = torch.empty((len(lens), max(lens)), dtype=torch.float32, pin_memory=True)
+                # rows are padded in a PINNED staging buffer (torch caches pinned blocks) and uploaded without
+                # blocking the host, so that the next batch is staged while this one's copy and kernels run
+                host = torch.empty((len(lens), max(lens)), dtype=torch.float32, pin_memory=self._pin_memory())
                 hv = host.numpy()
-                r = 0
-                for k in idx:
-                    hv[r:r + counts[k], :progs[k].shape[1]] = progs[k]
-                    hv[r:r + counts[k], progs[k].shape[1]:] = 0.0
-                    r += counts[k]
-                yield (idx, kind, host, lens, None if native else [rates[k] for k in idx for _ in range(counts[k])], groups)
+                for k, a, b in rows_of(idx):
+                    hv[a:b, :progs[k].shape[1]] = progs[k]
+                    hv[a:b, progs[k].shape[1]:] = 0.0
+                # (only channels="all" sends the channel counts along: they are what makes the loudness gain a linked one)
+                yield _Batch(idx, kind, host, lens, None if native else [rates[k] for k in idx for _ in range(counts[k])],
+                             [counts[k] for k in idx] if multi else None).as_item()
 
-        kw = {} if output_sample_rate is None else {"output_sample_rate": output_sample_rate}
-        if loudness is not None:
-            kw.update(loudness=loudness, peak_ceiling=peak_ceiling, channel_weights=channel_weights)
-            if true_peak:
-                kw["true_peak"] = True
-        for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, seed, **kw):
+        for idx, out_host, lens_out, *_ in self.restore_batches(staged(), your_vocoder_func, streams, mode, **job.kwargs()):
             ov = out_host.numpy()
-            r = 0
-            for k in idx:
-                outs[k] = ov[r:r + counts[k], :lens_out[r]].copy()
-                r += counts[k]
+            for k, a, b in rows_of(idx):
+                outs[k] = ov[a:b, :lens_out[a]].copy()   # (the pinned block goes back to torch's host cache)
         return outs
 
     @torch.no_grad()
@@ -1021,12 +1040,13 @@ class VoiceFixer(nn.Module):
         device, and the chunks are cut from the converted waveform.  ``output_sample_rate`` other than 44.1 kHz raises
         NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries; so
         does ``loudness``, and ``true_peak=True`` with it: the stretches leave before a whole-file measurement exists."""
-        self._check_mode(mode)
+        _check_stream_mode(mode, "restore_stream")
         rate_in = _check_rate(sample_rate)
-        if _check_loudness(loudness, peak_ceiling, true_peak)[0] is not None or true_peak:
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak)
+        if job.loudness is not None or job.true_peak:
             raise NotImplementedError("restore_stream: loudness normalisation is not built -- the on_chunk stretches leave before "
                                       "the whole file has been measured; use restore_inmem or restore_folder")
-        if _output_rate(output_sample_rate) != 44100:
+        if job.rate_out != 44100:
             raise NotImplementedError("restore_stream: output_sample_rate is not built -- converting the on_chunk stretches "
                                       "would need the resampler's filter state at every chunk boundary; use restore_inmem")
         pipe = self._get_pipe()
@@ -1037,10 +1057,8 @@ class VoiceFixer(nn.Module):
             x = torch.from_numpy(np.ascontiguousarray(wav))[None].to(pipe.device)
             y, (n,) = convert_rows(x, [n], [rate_in])
             src = y[0, :n]
-        chunk, ov = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
-        if mode == 1:
-            chunk -= chunk % 512
-        plan = plan_stream_chunks(n, chunk, ov, 1535 if mode == 1 else 1024)
+        chunk, ov, min_tail = _stream_geometry(chunk_seconds, overlap_seconds, mode)
+        plan = plan_stream_chunks(n, chunk, ov, min_tail)
         out = np.zeros((1, n), np.float32)
         fade_in = (np.arange(ov, dtype=np.float32) / max(ov, 1))[None]
         done = 0  # output is final below this sample
@@ -1088,23 +1106,14 @@ class VoiceFixer(nn.Module):
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
     MIN_SAMPLES = {0: 1025, 1: 1536, 2: 441 * (engine.TRAIN_MIN_FRAMES - 1)}
 
-    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, seed=None, output_sample_rate=None,
-                                  loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None):
+    def _restore_batches_isolated(self, items, failed, your_vocoder_func, streams, mode, **kw):
         """``restore_batches`` with per-row fault isolation (the folder job's device stage): when a batch raises -- a
         length a kernel refuses, an allocation that does not fit, a plugin vocoder error -- the batches that were in
         flight are re-issued ROW BY ROW, every row that still fails is recorded as ``(tag, reason)`` in ``failed`` and
         the stream of batches continues; the job loses the failing file, nothing else (the reference's serial loop,
-        voicefixer/__main__.py:187-212, keeps every file it finished before a bad one)."""
+        voicefixer/__main__.py:187-212, keeps every file it finished before a bad one).  ``kw``: what ``_Output.kwargs()`` gave the
+        caller, passed on to every ``restore_batches`` call as it is (none for a default job)."""
         from collections import deque
-        kw = {"seed": seed} if mode == 2 else {}
-        if output_sample_rate is not None:
-            kw["output_sample_rate"] = output_sample_rate
-        if loudness is not None:
-            kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
-            if true_peak:
-                kw["true_peak"] = True
-            if channel_weights is not None:
-                kw["channel_weights"] = channel_weights
         src = iter(items)
         pending = deque()
         src_exc = []           # what the batch SOURCE raised (a generator that has raised is finished: nothing more will come)
@@ -1140,27 +1149,14 @@ class VoiceFixer(nn.Module):
                     raise
                 first = "%s: %s" % (type(exc).__name__, exc)
                 for it in bad:
-                    tag, kind, host, lens = it[:4]
-                    rates = it[4] if len(it) >= 5 else None
-                    groups = it[5] if len(it) == 6 and it[5] is not None else None
-                    row0 = 0
-                    for r in range(len(tag)):
-                        if groups is not None:      # (a file of several channels is re-issued whole: rows a..b)
-                            a, b = row0, row0 + int(groups[r])
-                            row0 = b
-                            one = (tag[r:r + 1], kind, host[a:b, :max(int(lens[a]), 1)], list(lens[a:b]),
-                                   None if rates is None else list(rates[a:b]), [b - a])
-                        else:
-                            one = (tag[r:r + 1], kind, host[r:r + 1, :max(int(lens[r]), 1)], [lens[r]])
-                            if rates is not None:
-                                one += ([rates[r]],)
+                    for one in _Batch(*it).files():     # (a file of several channels is re-issued whole)
                         try:
-                            for rec1 in self.restore_batches(iter([one]), your_vocoder_func, streams, mode, **kw):
+                            for rec1 in self.restore_batches(iter([one.as_item()]), your_vocoder_func, streams, mode, **kw):
                                 yield rec1
                         except (KeyboardInterrupt, GeneratorExit):
                             raise
                         except Exception as e1:    # noqa: BLE001
-                            failed.append((tag[r], "%s: %s" % (type(e1).__name__, e1) if str(e1) else first))
+                            failed.append((one.tag[0], "%s: %s" % (type(e1).__name__, e1) if str(e1) else first))
 
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
@@ -1217,9 +1213,9 @@ class VoiceFixer(nn.Module):
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
-        rate_out = _output_rate(output_sample_rate)
-        _check_loudness(loudness, peak_ceiling, true_peak)
-        channels = _check_channels(channels, channel_weights)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        rate_out = job.rate_out
+        channels = _check_channels(channels)
         multi = channels == "all"
         nch = {}               # index -> rows the file takes in a batch (its channel count with channels="all", else 1)
         rank, world = vdist.rank_world(rank, world)
@@ -1367,9 +1363,8 @@ class VoiceFixer(nn.Module):
                 """The ``restore_batches`` item of the files ``idx``: lengths and rates once per ROW; the channel counts go along
                 only with channels="all" (every other job yields the 4- or 5-field items it always did)."""
                 per_row = lambda v: [v[r] for r, i in enumerate(idx) for _ in range(nch[i])]     # noqa: E731
-                if multi:
-                    return (idx, kind, host, per_row(real), per_row(rates) if resample_on_device else None, [nch[i] for i in idx])
-                return (idx, kind, host, per_row(real)) + ((per_row(rates),) if resample_on_device else ())
+                return _Batch(idx, kind, host, per_row(real), per_row(rates) if resample_on_device else None,
+                              [nch[i] for i in idx] if multi else None).as_item()
 
             def submit_decode(b):
                 kind, grp = plan[b]
@@ -1442,17 +1437,8 @@ class VoiceFixer(nn.Module):
 
             source_error = None
             try:
-                kw = {"seed": seed} if mode == 2 else {}
-                if output_sample_rate is not None:
-                    kw["output_sample_rate"] = output_sample_rate
-                if loudness is not None:
-                    kw.update(loudness=loudness, peak_ceiling=peak_ceiling)
-                    if true_peak:
-                        kw["true_peak"] = True
-                    if multi and channel_weights is not None:
-                        kw["channel_weights"] = channel_weights
                 for idx, out_host, lens_out, *extra in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func,
-                                                                                       streams, mode, **kw):
+                                                                                       streams, mode, **job.kwargs()):
                     ov = out_host.numpy()
                     if extra:
                         lv = extra[0].numpy()
@@ -1484,7 +1470,7 @@ class VoiceFixer(nn.Module):
                          failed=sorted((files[i], why) for i, why in failed), skipped=sorted(skipped),
                          truncated=sorted((files[i], n, m) for i, n, m in truncated if i in real_len or i in mine),
                          loudness=sorted((names[i],) + loud_rows[i] for i in done if i in loud_rows))
-            if true_peak and loudness is not None:
+            if job.true_peak and job.loudness is not None:
                 stats["true_peak"] = sorted((names[i],) + tp_rows[i] for i in done if i in tp_rows)
         return sorted(written)
 
@@ -1501,36 +1487,24 @@ class VoiceFixer(nn.Module):
         ``loudness`` / ``peak_ceiling`` / ``true_peak``: as ``restore_inmem``.  ``channels`` (extension): None or "mix": a file
         of several channels is averaged to one (the reference's ``librosa.load``); "first": its first channel; "all": every
         channel is restored (``restore_inmem(channels="all")``) and the output has the input's channel count."""
-        rate_out = _output_rate(output_sample_rate)
-        _check_loudness(loudness, peak_ceiling, true_peak)
-        kw = {"true_peak": True} if true_peak else {}
-        if _check_channels(channels, channel_weights) in ("first", "all"):
-            x, sr = audio_io.load_wav_native(input, mono=False)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights)
+        channels = _check_channels(channels)
+
+        per_channel = channels in ("first", "all")
+        if per_channel or resample_on_device:       # decoded at the file's own rate, channel by channel or averaged by the decoder
+            x, sr = audio_io.load_wav_native(input, mono=not per_channel)
             x = audio_io.select_channels(x, channels)
             if sr != 44100 and not (resample_on_device and max(audio_io.rate_ratio(sr, 44100)) <= audio_io.DEVICE_MAX_RATIO):
                 x, sr = audio_io.resample_hq(x, sr, 44100), 44100
-            if channels == "all":
-                kw.update(channels="all", channel_weights=channel_weights)
-            out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
-                                            your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
-                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
-                                            **kw)
-            audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out, channels_first=True)
-            return
-        if resample_on_device:
-            x, sr = audio_io.load_wav_native(input)
-            if sr != 44100 and max(audio_io.rate_ratio(sr, 44100)) > audio_io.DEVICE_MAX_RATIO:
-                x, sr = audio_io.resample_hq(x, sr, 44100), 44100
-            out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
-                                            your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
-                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
-                                            **kw)
         else:
-            wav_10k = self._load_wav(input, sample_rate=44100)
-            out_np_wav = self.restore_inmem(wav_10k, cuda=cuda, mode=mode, your_vocoder_func=your_vocoder_func, seed=seed,
-                                            output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
-                                            **kw)
-        audio_io.save_wave(out_np_wav, fname=output, sample_rate=rate_out)
+            x, sr = self._load_wav(input, sample_rate=44100), 44100
+        kw = {"channels": "all", "channel_weights": channel_weights} if channels == "all" else {}
+        out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
+                                        your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
+                                        output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
+                                        true_peak=true_peak, **kw)
+        # (channels_first: what came back is (C, N') whatever its sizes; for one channel this is what the default does)
+        audio_io.save_wave(out_np_wav, fname=output, sample_rate=job.rate_out, channels_first=True)
 
 
 class _SpanConverter:
@@ -1597,19 +1571,15 @@ class RestoreSession:
 
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                  sample_rate=44100, output_sample_rate=None):
-        if mode == 2:
-            raise NotImplementedError("open_stream: mode=2 is not built -- its per-segment statistics have no overlap-add form")
-        VoiceFixer._check_mode(mode)
+        _check_stream_mode(mode, "open_stream")
         self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
         for r in (self._rate_in, self._rate_out):
             if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
                 raise ValueError("open_stream: the device resampler does not take the ratio of %d Hz to 44100 Hz" % r)
         if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
             raise ValueError("batch_size must be a positive integer")
-        chunk, ov = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
-        if mode == 1:
-            chunk -= chunk % 512
-        self._planner = StreamPlanner(chunk, ov, 1535 if mode == 1 else 1024)     # (ValueError: chunk <= overlap + 1024)
+        chunk, ov, min_tail = _stream_geometry(chunk_seconds, overlap_seconds, mode)
+        self._planner = StreamPlanner(chunk, ov, min_tail)     # (ValueError: chunk <= overlap + 1024)
         self._vf, self._mode, self._voc, self._batch, self._ov = vf, mode, your_vocoder_func, int(batch_size), ov
         self._conv_in = _SpanConverter(self._rate_in, 44100) if self._rate_in != 44100 else None
         self._conv_out = _SpanConverter(44100, self._rate_out) if self._rate_out != 44100 else None
