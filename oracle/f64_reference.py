@@ -8,7 +8,8 @@ compute, written from torch primitives (``torch.nn.GRU`` with packed sequences, 
 through ``oracle.py``, so the two can check each other: tests/test_seq_reference_cpu.py and tests/test_conv_reference_cpu.py
 pin these statements against the oracle and the torch operators on the CPU, tests/test_seq_kernels_gpu.py and
 tests/test_conv_taps_gpu.py hold the kernels to them.  Ragged batches are given as a list of per-row lengths; every function
-returns float64 CPU tensors.
+returns float64 CPU tensors.  The last section is the yardstick of tests/test_convwg4s_gpu.py: the 3x3 convolution as a plain
+fp32 Winograd F(4,3) (conv2d_f43_f32, the one function here that returns float32) and the per-quad error figure.
 """
 import torch
 
@@ -344,6 +345,82 @@ def conv_error(got, ref, mag, lipschitz=1.0):
     ok = ~torch.isnan(ref)
     e = (got.to(torch.float64) - ref).abs() / (lipschitz * mag + ref.abs()).clamp(min=1e-300)
     e = torch.where(ok, e, torch.zeros_like(e))      # a NaN in `got` at a valid output stays NaN and fails the bound
+    bad = torch.isnan(got.to(torch.float64)) & ok
+    mx = float("inf") if bool(bad.any()) else float(e.max())
+    return mx, float((e * e).sum()), int(ok.sum())
+
+
+# --------------------------------------------------------------------------------------
+# the 3x3 convolution as Winograd F(4,3) along the map rows, in fp32 (the error yardstick of convwg4s_kernel)
+# --------------------------------------------------------------------------------------
+# An F(4,3) kernel cannot be held to a multiple of the DIRECT fp32 operator's error: a plain fp32 F(4,3) is 4.3 x (maximum)
+# and 2.2 x (RMS) the direct operator against float64 at 64 -> 64 channels (transform constants up to 8).  So the bound of
+# tests/test_convwg4s_gpu.py is measured on this fp32 statement of the same algorithm: standard matrices (the header of
+# voicefixer_amd/csrc/vfx_convwg.inc writes them out), every operation separately rounded, bias and residual added after
+# the output transform.  It is the reference, not a model of the kernel.
+def _f43_weights(w):
+    """U = G w along the kernel's row axis, formed in float64 and rounded once (as packing.pack_wino4_2d does):
+    w (Cout, Cin, 3, 3) -> (6 planes, Cout, Cin, 3 kernel columns) float32."""
+    g0, g1, g2 = (w[:, :, ky].to(torch.float64) for ky in range(3))
+    return torch.stack([g0 / 4, -(g0 + g1 + g2) / 6, -(g0 - g1 + g2) / 6, g0 / 24 + g1 / 12 + g2 / 6,
+                        g0 / 24 - g1 / 12 + g2 / 6, g2]).to(torch.float32)
+
+
+def conv2d_f43_f32(x, w, bias=None, res=None, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE,
+                   post_slope=0.0, lengths=None):
+    """conv2d (k = 3) computed in float32 as F(4,3) along the map rows and direct along the columns: V = B^T d of the
+    pre-activated, zero-padded input rows 4k - 1 .. 4k + 4, six planes m_p = sum_{c,kx} U_p V_p, y = A^T m, then bias,
+    residual and the post-activation.  x (B, Cin, H, W), w (Cout, Cin, 3, 3) -> (B, Cout, H, W) float32 (NaN past a
+    row's own height when `lengths` is given)."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: conv2d_f43_f32(xb, w, bias, rb, pre, pre_slope, scale, shift, post, post_slope).double(),
+                        x, res, lengths, lambda n: n).float()
+    assert tuple(w.shape[2:]) == (3, 3)
+    B, Cin, Hh, W = x.shape
+    f32 = torch.float32
+    xa = x.to(f32)
+    if pre == PRE_AFFINE_LRELU:
+        xa = xa * scale.to(f32).reshape(1, -1, 1, 1) + shift.to(f32).reshape(1, -1, 1, 1)
+    if pre in (PRE_LRELU, PRE_AFFINE_LRELU):
+        xa = torch.where(xa > 0, xa, xa * torch.tensor(float(pre_slope), dtype=f32))
+    nblk = (Hh + 3) // 4
+    xp = torch.zeros((B, Cin, 4 * nblk + 2, W + 2), dtype=f32)
+    xp[:, :, 1:1 + Hh, 1:1 + W] = xa
+    d = xp.unfold(2, 6, 4)                              # (B, Cin, nblk, W + 2, 6): rows 4k - 1 .. 4k + 4 of quad-row k
+    d0, d1, d2, d3, d4, d5 = (d[..., j] for j in range(6))
+    V = [4 * d0 - 5 * d2 + d4, -4 * d1 - 4 * d2 + d3 + d4, 4 * d1 - 4 * d2 - d3 + d4,
+         -2 * d1 - d2 + 2 * d3 + d4, 2 * d1 - d2 - 2 * d3 + d4, 4 * d1 - 5 * d3 + d5]
+    U = _f43_weights(w)
+    m = []
+    for p in range(6):
+        acc = torch.zeros((B, w.shape[0], nblk, W), dtype=f32)
+        for kx in range(3):
+            acc = acc + torch.einsum("nc,bckw->bnkw", U[p, :, :, kx], V[p][..., kx:kx + W])
+        m.append(acc)
+    y = torch.stack([m[0] + m[1] + m[2] + m[3] + m[4], m[1] - m[2] + 2 * (m[3] - m[4]), m[1] + m[2] + 4 * (m[3] + m[4]),
+                     m[1] - m[2] + 8 * (m[3] - m[4]) + m[5]], dim=3)          # (B, Cout, nblk, 4, W)
+    y = y.reshape(B, w.shape[0], 4 * nblk, W)[:, :, :Hh]
+    if bias is not None:
+        y = y + bias.to(f32).reshape(1, -1, 1, 1)
+    if res is not None:
+        y = y + res.to(f32)
+    return conv_post(y, post, post_slope)
+
+
+def quad_figure(got, ref, mag, lipschitz=1.0):
+    """The figure natural to F(4,3), whose four vertically adjacent outputs share six products and six input rows:
+    |got - ref| / M with M the maximum of lipschitz * magnitude + |ref| over the outputs of the same quad -- map rows
+    4k .. 4k + 3 of one batch row (cut at that row's own height: where ref is NaN), same channel and column.  Dense maps
+    (B, C, H, W).  Returns (max, sum of squares, count), like conv_error, and is never larger than it."""
+    ok = ~torch.isnan(ref)
+    den = torch.where(ok, lipschitz * mag + ref.abs(), torch.zeros_like(ref))
+    B, Cn, Hh, W = ref.shape
+    Hp = (Hh + 3) // 4 * 4
+    dp = torch.zeros((B, Cn, Hp, W), dtype=den.dtype)
+    dp[:, :, :Hh] = den
+    M = dp.reshape(B, Cn, Hp // 4, 4, W).amax(dim=3, keepdim=True).expand(B, Cn, Hp // 4, 4, W).reshape(B, Cn, Hp, W)[:, :, :Hh]
+    e = (got.to(torch.float64) - ref).abs() / M.clamp(min=1e-300)
+    e = torch.where(ok, e, torch.zeros_like(e))
     bad = torch.isnan(got.to(torch.float64)) & ok
     mx = float("inf") if bool(bad.any()) else float(e.max())
     return mx, float((e * e).sum()), int(ok.sum())

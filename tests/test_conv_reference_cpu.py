@@ -180,3 +180,133 @@ def test_conv_statements_equal_the_oracle_modules(seeded_states):
     x = _rand((2, w.shape[1], 19), 23)
     want = F.leaky_relu(F.conv1d(F.pad(x, (3, 3), mode="reflect"), w, sd["generator.1.bias"]), 0.2)
     _close(ref64.conv1d(x, w, sd["generator.1.bias"], reflect=True, post=ref64.POST_LRELU, post_slope=0.2), want)
+
+
+# --------------------------------------------------------------------------------------
+# the fp32 F(4,3) statement and the per-quad figure (the yardstick of tests/test_convwg4s_gpu.py)
+# --------------------------------------------------------------------------------------
+ULP = 2.0 ** -23
+
+
+def _f43_operands(B, Cin, Cout, H, lp, pre, bias, res, seed):
+    W = (1 << lp) - 1
+    x, w = _rand((B, Cin, H, W), seed), _rand((Cout, Cin, 3, 3), seed + 1, (Cin * 9) ** -0.5)
+    affine = pre == ref64.PRE_AFFINE_LRELU
+    scale = 0.8 + 0.4 * torch.rand(Cin, generator=torch.Generator().manual_seed(seed + 2)) if affine else None
+    shift = _rand((Cin,), seed + 3, 0.3) if affine else None
+    return x, w, (_rand((Cout,), seed + 4, 0.3) if bias else None), (_rand((B, Cout, H, W), seed + 5) if res else None), scale, shift
+
+
+# pre, post, bias, residual: what tests/test_convwg4s_gpu.py launches (the product's two convolutions of a ConvBlockRes, the
+# train-mode first convolution, and the edge rows' bias + residual + post-activation / ELU / slope 0 and 1 combinations)
+F43_COMBOS = [(ref64.PRE_AFFINE_LRELU, 0.01, ref64.POST_LRELU, 0.01, True, False), (ref64.PRE_NONE, 0.0, ref64.POST_NONE, 0.0, False, True),
+              (ref64.PRE_NONE, 0.0, ref64.POST_NONE, 0.0, False, False), (ref64.PRE_AFFINE_LRELU, 0.01, ref64.POST_LRELU, 0.01, True, True),
+              (ref64.PRE_NONE, 0.0, ref64.POST_LRELU, 0.01, True, True), (ref64.PRE_AFFINE_LRELU, 0.0, ref64.POST_ELU, 0.0, True, True),
+              (ref64.PRE_AFFINE_LRELU, 1.0, ref64.POST_LRELU, 0.0, True, False), (ref64.PRE_NONE, 0.0, ref64.POST_NONE, 0.0, True, True)]
+
+
+@pytest.mark.parametrize("combo", range(len(F43_COMBOS)))
+@pytest.mark.parametrize("H,lp", [(8, 1), (9, 4), (6, 4), (7, 1), (4, 4), (1, 1)])
+def test_f43_f32_statement_equals_the_float64_convolution(combo, H, lp):
+    """conv2d_f43_f32 is the same operator as conv2d: its conv_error figure against the float64 statement is at most
+    16 x 2^-23 (a plain fp32 F(4,3) measures 3 - 4 x 2^-23 at these channel counts: the bound leaves room for the draw,
+    not for a wrong row, column, plane or coefficient, which is off by the order of the output).  Map heights with
+    H % 4 in {0, 1, 2, 3}, P in {2, 16}, per-row heights."""
+    pre, pre_slope, post, post_slope, bias, res = F43_COMBOS[combo]
+    x, w, b, r, scale, shift = _f43_operands(3, 16, 8, H, lp, pre, bias, res, 100 + 7 * combo + H)
+    kw = dict(pre=pre, pre_slope=pre_slope, scale=scale, shift=shift, post=post, post_slope=post_slope)
+    for lengths in (None, [H, 1, max(1, H - 3)]):
+        got = ref64.conv2d_f43_f32(x, w, b, r, lengths=lengths, **kw)
+        assert got.dtype == torch.float32
+        ref = ref64.conv2d(x, w, b, r, lengths=lengths, **kw)
+        mag = ref64.conv2d(x, w, b, r, lengths=lengths, magnitude=True, **kw)
+        assert torch.equal(torch.isnan(got), torch.isnan(ref))
+        mx, ss, n = ref64.conv_error(got, ref, mag)
+        assert n == int((~torch.isnan(ref)).sum()) and mx <= 16 * ULP, mx
+        assert ref64.quad_figure(got, ref, mag)[0] <= mx
+
+
+def test_f43_weights_are_the_packed_ones():
+    """U = G w of the statement holds bit for bit the values packing.pack_wino4_2d hands the kernel in slab kx * 6 + plane
+    (compared as sorted values: the order within a slab is pack_direct's MFMA operand layout)."""
+    from voicefixer_amd import packing
+    w = _rand((32, 16, 3, 3), 300, 0.1)
+    U = ref64._f43_weights(w)                                              # (6, Cout, Cin, 3)
+    packed = packing.pack_wino4_2d(packing.pack_conv2d(w))                 # [18][Cin / 8][Cout][8]
+    assert packed.shape == (18, 2, 32, 8)
+    for kx in range(3):
+        for p in range(6):
+            assert torch.equal(packed[kx * 6 + p].flatten().sort().values, U[p, :, :, kx].flatten().sort().values)
+
+
+def test_quad_figure_reduces_to_conv_error_and_is_never_larger():
+    g = torch.Generator().manual_seed(41)
+    B, Cn, H, W = 2, 3, 11, 5
+    ref = torch.randn((B, Cn, H, W), generator=g, dtype=torch.float64)
+    ref[1, :, 6:] = float("nan")                                           # row 1 is 6 map rows high
+    got = ref + 1e-6 * torch.randn((B, Cn, H, W), generator=g, dtype=torch.float64)
+    got[1, :, 6:] = 123.0                                                  # whatever lies past a row's end is not scored
+    # equal denominators within every quad: |ref| and the magnitude constant over the four rows
+    blk = torch.arange(H) // 4
+    ref_eq = torch.where(torch.isnan(ref), ref, ref[:, :, blk * 4])
+    mag_eq = torch.rand((B, Cn, 3, W), generator=g, dtype=torch.float64)[:, :, blk]
+    got_eq = ref_eq + (got - ref)
+    a, b = ref64.quad_figure(got_eq, ref_eq, mag_eq, 2.0), ref64.conv_error(got_eq, ref_eq, mag_eq, 2.0)
+    assert a[2] == b[2] == B * Cn * H * W - Cn * 5 * W and abs(a[0] - b[0]) <= 1e-15 * b[0] and abs(a[1] - b[1]) <= 1e-12 * b[1]
+    # unequal ones: never larger, and one large neighbour lowers the figure of the small output next to it
+    mag = torch.rand((B, Cn, H, W), generator=g, dtype=torch.float64)
+    a, b = ref64.quad_figure(got, ref, mag), ref64.conv_error(got, ref, mag)
+    assert a[2] == b[2] and a[0] <= b[0] and a[1] < b[1]
+    ref1 = torch.tensor([1.0, 100.0, 1.0, 1.0, 1.0], dtype=torch.float64).reshape(1, 1, 5, 1)
+    got1 = ref1 + torch.tensor([1e-3, 0.0, 0.0, 0.0, 1e-3], dtype=torch.float64).reshape(1, 1, 5, 1)
+    mx, ss, n = ref64.quad_figure(got1, ref1, torch.zeros_like(ref1))
+    assert n == 5 and abs(mx - 1e-3) < 1e-15 and abs(ss - (1e-6 + 1e-10)) < 1e-15     # row 4 is a quad of its own: 1e-3 / 1
+    assert ref64.quad_figure(torch.full_like(ref1, float("nan")), ref1, torch.zeros_like(ref1))[0] == float("inf")
+    # a quad is cut at the row's own height: the NaN rows of a ragged batch do not enter its maximum
+    ref2 = ref1.clone()
+    ref2[0, 0, 1] = float("nan")
+    assert abs(ref64.quad_figure(got1, ref2, torch.zeros_like(ref1))[0] - 1e-3) < 1e-15
+
+
+def _start_values_f32(t, scheme):
+    """fp32 emulation of carrying a residual quad t = (t0 .. t3) through the accumulators of an F(4,3) kernel whose
+    products are all zero: start values m with A^T m = t, then the output transform as convwg4s_kernel writes it.
+    'planes0135': m2 = m4 = 0, m3 = (t2 - t1) / 2, m1 = 2 t1 - t2, m0 = t0 - m1 - m3, m5 = t3 - m1 - 8 m3;
+    'planes0125': m3 = m4 = 0, m1 = (t1 + t2) / 2, m2 = (t2 - t1) / 2, m0 = t0 - t2, m5 = t3 - t1."""
+    import numpy as np
+    f32 = np.float32
+    t0, t1, t2, t3 = t
+    z = np.zeros_like(t0)
+    if scheme == "planes0135":
+        m3 = f32(0.5) * (t2 - t1)
+        m1 = f32(2) * t1 - t2
+        m = [t0 - m1 - m3, m1, z, m3, z, t3 - m1 - f32(8) * m3]
+    else:
+        m = [t0 - t2, f32(0.5) * (t1 + t2), f32(0.5) * (t2 - t1), z, z, t3 - t1]
+    p12, m12, p34, m34 = m[1] + m[2], m[1] - m[2], m[3] + m[4], m[3] - m[4]
+    out = np.stack([(m[0] + p12) + p34, f32(2) * m34 + m12, f32(4) * p34 + p12, (f32(8) * m34 + m12) + m[5]])
+    assert out.dtype == f32
+    return out
+
+
+@pytest.mark.parametrize("scheme", ["planes0135", "planes0125"])
+@pytest.mark.parametrize("dist", ["gauss", "lognormal"])
+def test_start_values_carry_a_residual_within_the_floor(scheme, dist):
+    """The floor of test_residual_pass_through (tests/test_convwg4s_gpu.py) is within reach of an fp32 kernel that carries
+    the residual in its accumulators' start values: it returns it within 4 x 2^-23 in quad_figure (measured: 2.9 x 2^-23
+    with planes 0, 1, 3, 5 and 0.98 x 2^-23 with planes 0, 1, 2, 5), on unit Gaussian residuals and on ones scaled by a
+    log-normal factor (sigma 1.5) per output.  Zero weights: the magnitude is |residual|, the reference the residual.
+    (convwg4s_kernel now adds the residual after the output transform and is exact here; the 1-D kernels still use
+    planes 0, 1, 3, 5.)"""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    n = 500000
+    t = rng.standard_normal((4, n))
+    if dist == "lognormal":
+        t = t * np.exp(1.5 * rng.standard_normal((4, n)))
+    t = t.astype(np.float32)
+    got = torch.from_numpy(_start_values_f32(t, scheme)).reshape(1, 1, 4, n)
+    ref = torch.from_numpy(t).to(torch.float64).reshape(1, 1, 4, n)
+    mx, ss, cnt = ref64.quad_figure(got, ref, ref.abs())
+    print("start values %s %s: quad figure max %.2f x 2^-23, rms %.3f x 2^-23" % (scheme, dist, mx / ULP, (ss / cnt) ** 0.5 / ULP))
+    assert cnt == 4 * n and mx <= 4 * ULP

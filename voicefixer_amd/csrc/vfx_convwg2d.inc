@@ -20,16 +20,24 @@
 //
 // Everything else follows convwg4_kernel: quad index space (q = 4P*blk + r is output 0 of quad blk*P + r: the four outputs
 // are vertical neighbours), weights packing.pack_wino4_2d = [kx*6 + plane][Cin/8][Cout][8] straight from L2 as 16-byte
-// A-operand vectors in two register sets (one 8-channel group ahead), bias / residual through the accumulators, staging
+// A-operand vectors in two register sets (one 8-channel group ahead), staging
 // woven between the MFMAs, per-row lengths (ragged batches), XCD-aware tile order with the channel blocks of a tile folded in.
+// NOT from convwg4_kernel: bias and residual are added after the output transform (see the accumulators' start below).
 // Instances: <2,2,16> (64 output channels x 64 quads, levels 1-4: P <= 64) and <1,4,8> (32 x 128, UNet level 0: Cout = 32).
 // AFF (round 4): false = the launch has no pre-activation (the SECOND convolution of a ConvBlockRes: bn2 is folded into the first one's
 // weights, whose epilogue applies the leaky ReLU), so the staging is the B^T transform alone -- a tap outside the map or in the pad
 // column reads 0 through its out-of-range offset and needs neither the scale / shift, nor the leaky ReLU, nor the select that zeroes
 // it AFTER the activation: 12 VALU operations per staged element instead of 36.  (The fp32 MFMA shares its issue cycles with the
 // VALU on this chip, profiles/r04_convwg4_prologue_ab.txt: instructions that compute nothing are matrix-pipe time.)
-template <int WGM, int WGP, int KC, bool AFF = true>
-__global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
+// TWO (contractions longer than WG4S_TWO_CIN channels): a two-level sum.  One accumulator chain per plane adds 3 * Cin / 2
+// MFMA results in sequence, and its rounding error grows with the square root of that count while a blocked fp32 sum's does
+// not: the maximum error was 3.2 - 3.4 x a plain fp32 F(4,3) statement's at Cin = 384, 3.9 - 4.1 x at 512 and 4.7 x at 768 (the
+// decoder's 768 -> 384), against the bound of 4 of tests/test_convwg4s_gpu.py; two-level it is 0.7 - 1.1 x.  So every 64 channels the accumulators are added to a second set and
+// start again at zero (conv_taps_kernel's remedy).  The second set is 96 more registers, which do not fit two waves per SIMD:
+// this instance runs one wave per SIMD, and only the launches that need it take it.
+constexpr int WG4S_TWO_CIN = 384;
+template <int WGM, int WGP, int KC, bool AFF = true, bool TWO = false>
+__global__ __launch_bounds__(256, TWO ? 1 : 2) void convwg4s_kernel(const ConvArgs a) {
     static_assert(WGM * WGP == 4 && (KC == 8 || KC == 16), "four waves; 8- or 16-channel chunks");
     constexpr int NSTEP = KC / 2;                 // k-pair steps per kernel column and chunk
     constexpr int NG = KC / 8;                    // 8-channel weight groups per chunk
@@ -164,74 +172,25 @@ __global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
         aw[SET][k] = make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
     };
 
-    // ---- accumulator start values (as convwg4_kernel): the residual is fetched raw into the accumulator registers of
-    // planes 0, 1, 3, 5, the tap loads of chunk 0 and the A vectors of group 0 follow at once, and the start values are
-    // formed only after chunk 0 has been staged (acc_start): one HBM round trip in the prologue instead of two
+    // ---- accumulators start at zero.  Bias and residual do NOT enter through them (convwg4_kernel's scheme, which this kernel
+    // used before): an accumulator that starts at a residual or bias of order 1 rounds every product added to it at 2^-24 of
+    // THAT value, so where the weights are small next to the skip connection (heavy-tailed gains) the convolution came out
+    // 10 - 80 x less exact than an fp32 F(4,3) that adds them last -- and any solution of A^T m = residual couples the four
+    // outputs of a quad (a small residual between large vertical neighbours was off by 2^-24 of the neighbours).
+    // tests/test_convwg4s_gpu.py, profiles/convwg4s_parity.txt.  Both are added after the output transform (below), as
+    // conv_taps_kernel does.
     const int row0 = m0 + wm * 32;
     f32x16 acc[6];
-    // the issue block, in the order in which the results are consumed (see convwg4_kernel): bias, taps of chunk 0, first A
-    // vectors, residual last
-    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
-    u32x4 bq[4];
-    {
-        const int bvoff = a.bias ? (row0 + 4 * hi) * 4 : VFX_W_OOB;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(brsrc, bvoff, g * 32, 0);
-    }
+    // the issue block, in the order in which the results are consumed (see convwg4_kernel): taps of chunk 0, first A vectors
     x_load(0);
 #pragma unroll
     for (int k = 0; k < 6; ++k) a_load_one(std::integral_constant<int, 0>{}, k, 0);
-    {
-        int rv[4];
-        const int q = quad_q(Q0 + wp * 32 + lo);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rv[i] = q + i * d < Lrow ? (4 * hi * (int)a.r_cs + q + i * d) * 4 : VFX_W_OOB;
-        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(a.res ? a.res : a.x) + (long long)b * a.r_bs, (short)0, 0x7fffffff, 0x00020000);
-        const int cs4 = (int)a.r_cs * 4;
-        if (a.res) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * cs4;
-                acc[0][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[0], soff, 0));
-                acc[1][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[1], soff, 0));
-                acc[3][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[2], soff, 0));
-                acc[5][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[3], soff, 0));
-            }
-        }
-    }
     __builtin_amdgcn_sched_barrier(0);            // (nothing that consumes a loaded value may be scheduled up into the issue block)
     auto acc_start = [&]() {
-        if (!a.res) {                             // no residual: the solution of A^T m = bias is m1 = bias, everything else 0
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
+        for (int k = 0; k < 6; ++k)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e;
-                    acc[0][r] = 0.f;
-                    acc[1][r] = __uint_as_float(e == 0 ? bq[g].x : (e == 1 ? bq[g].y : (e == 2 ? bq[g].z : bq[g].w)));
-                    acc[2][r] = 0.f; acc[3][r] = 0.f; acc[4][r] = 0.f; acc[5][r] = 0.f;
-                }
-            return;
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * g + e;
-                const float bb = __uint_as_float(e == 0 ? bq[g].x : (e == 1 ? bq[g].y : (e == 2 ? bq[g].z : bq[g].w)));
-                const float t0 = acc[0][r] + bb, t1 = acc[1][r] + bb, t2 = acc[3][r] + bb, t3 = acc[5][r] + bb;
-                const float m3 = 0.5f * (t2 - t1);
-                const float m1 = 2.f * t1 - t2;
-                acc[0][r] = t0 - m1 - m3;
-                acc[1][r] = m1;
-                acc[2][r] = 0.f;
-                acc[3][r] = m3;
-                acc[4][r] = 0.f;
-                acc[5][r] = t3 - m1 - 8.f * m3;
-            }
-        }
+            for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
     };
 
     // ---- B fragments: lane (column lo, k-half hi) of k-pair u of plane k for kernel column kx reads
@@ -293,6 +252,13 @@ __global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
     x_load(S > 1 ? 1 : 0);
     __builtin_amdgcn_sched_barrier(0);
     acc_start();
+    f32x16 tot[TWO ? 6 : 1];
+    if constexpr (TWO) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tot[k][r] = 0.f;
+    }
     __syncthreads();
 #pragma unroll 1
     for (int s = 0; s < S; s += 2) {
@@ -302,9 +268,24 @@ __global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
         // chunk s+1 (buffer 1): stages chunk s+2 into buffer 0, loads x of chunk s+3
         mma_chunk(std::integral_constant<int, 1>{}, smem + BUF, wbase, min(s + 2, S - 1), min(s + 3, S - 1), s + 1, min(s + 2, S - 1));
         __syncthreads();
+        if constexpr (TWO) {
+            if (((s + 2) * KC) % 64 == 0) {       // 64 channels done: close the partial sum (the last one below)
+#pragma unroll
+                for (int k = 0; k < 6; ++k)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tot[k][r] += acc[k][r];
+                acc_start();
+            }
+        }
+    }
+    if constexpr (TWO) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[k][r] += tot[k][r];
     }
 
-    // ---- output transform, activation, stores; the outputs of a quad in the map's pad column are written as zero
+    // ---- output transform, bias, residual, activation, stores; the outputs of a quad in the map's pad column are written as zero
     const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
         a.y + (long long)b * a.y_bs, (short)0, 0x7fffffff, 0x00020000);
     const int ycs4 = (int)a.y_cs * 4;
@@ -318,13 +299,45 @@ __global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
         for (int i = 0; i < 4; ++i) yv[i] = q + i * d < Lrow ? (4 * hi * (int)a.y_cs + q + i * d) * 4 : VFX_W_OOB;
         keep = (q & a.out_mask) != a.out_mask;
     }
+    // the residual of the lane's 16 rows x 4 outputs, all fetched before the first store: res may be y (the in-place update
+    // of a ConvBlockRes), and a lane reads exactly the elements it later writes
+    f32x16 rres[4];
+    __builtin_amdgcn_sched_barrier(0);            // (after the last chunk: 64 more live registers do not fit next to the A operands)
+    u32x4 bq[4];                                  // bias of rows row0 + 4 hi + 8 g + e (0 without: out-of-range offset)
+    {
+        const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
+        const int bvoff = a.bias ? (row0 + 4 * hi) * 4 : VFX_W_OOB;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(brsrc, bvoff, g * 32, 0);
+    }
+    if (a.res) {
+        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(a.res) + (long long)b * a.r_bs, (short)0, 0x7fffffff, 0x00020000);
+        const int cs4 = (int)a.r_cs * 4;
+        const int q = quad_q(Q0 + wp * 32 + lo);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rvo = q + i * d < Lrow ? (4 * hi * (int)a.r_cs + q + i * d) * 4 : VFX_W_OOB;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                rres[i][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rvo, (row0 + (r & 3) + 8 * (r >> 2)) * cs4, 0));
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rres[i][r] = 0.f;
+    }
     auto outs = [&](int r, float (&y)[4]) {
         const float p12 = acc[1][r] + acc[2][r], m12 = acc[1][r] - acc[2][r];
         const float p34 = acc[3][r] + acc[4][r], m34 = acc[3][r] - acc[4][r];
-        y[0] = (acc[0][r] + p12) + p34;
-        y[1] = fmaf(2.f, m34, m12);
-        y[2] = fmaf(4.f, p34, p12);
-        y[3] = fmaf(8.f, m34, m12) + acc[5][r];
+        const u32x4 b4 = bq[r >> 2];
+        const float bb = __uint_as_float((r & 3) == 0 ? b4.x : ((r & 3) == 1 ? b4.y : ((r & 3) == 2 ? b4.z : b4.w)));
+        y[0] = (((acc[0][r] + p12) + p34) + bb) + rres[0][r];
+        y[1] = (fmaf(2.f, m34, m12) + bb) + rres[1][r];
+        y[2] = (fmaf(4.f, p34, p12) + bb) + rres[2][r];
+        y[3] = ((fmaf(8.f, m34, m12) + acc[5][r]) + bb) + rres[3][r];
     };
     if (post == VFX_POST_NONE) {
 #pragma unroll
@@ -359,12 +372,12 @@ __global__ __launch_bounds__(256, 2) void convwg4s_kernel(const ConvArgs a) {
     }
 }
 
-template <int WGM, int WGP, int KC, bool AFF>
+template <int WGM, int WGP, int KC, bool AFF, bool TWO>
 static int launch_wg4s_aff(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
     int attr_dev = 0;
     if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = convwg4s_kernel<WGM, WGP, KC, AFF>;
+    auto kern = convwg4s_kernel<WGM, WGP, KC, AFF, TWO>;
     if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -378,8 +391,11 @@ static int launch_wg4s_aff(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t
 
 template <int WGM, int WGP, int KC>
 static int launch_wg4s_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    return a.pre_act == VFX_PRE_NONE ? launch_wg4s_aff<WGM, WGP, KC, false>(a, grid, lds, s)
-                                     : launch_wg4s_aff<WGM, WGP, KC, true>(a, grid, lds, s);
+    if (a.Cin > WG4S_TWO_CIN)
+        return a.pre_act == VFX_PRE_NONE ? launch_wg4s_aff<WGM, WGP, KC, false, true>(a, grid, lds, s)
+                                         : launch_wg4s_aff<WGM, WGP, KC, true, true>(a, grid, lds, s);
+    return a.pre_act == VFX_PRE_NONE ? launch_wg4s_aff<WGM, WGP, KC, false, false>(a, grid, lds, s)
+                                     : launch_wg4s_aff<WGM, WGP, KC, true, false>(a, grid, lds, s);
 }
 
 // 3x3 convolution on a pitch map on convwg4s_kernel (weights packing.pack_wino4_2d); same contract as

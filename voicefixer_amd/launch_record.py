@@ -1,6 +1,6 @@
 """Recorder of the conv-family launches of a run (development and test infrastructure; shared by tools/launch_table.py and
 tests/test_conv_taps_gpu.py).  Inside ``with LaunchRecorder() as rec:`` every call of ops.conv1d / convtr1d / conv2d /
-convtr2d_3x3s2 / resblock / resblock_wino4 appends one record to ``rec.records``: what the caller asked for (shape, activations, residual,
+convtr2d_3x3s2 / resblock / resblock_wino4 appends one record to ``rec.records``: what the caller asked for (shape, activations, bias, residual,
 row tags, guard, output strides) and what the library did with it (vfx_last_conv_tile(), the vfx_launch_count() delta).
 Nothing on the launch path changes: the wrappers call the real launchers."""
 import inspect
@@ -38,6 +38,7 @@ def _describe(name, a):
         d.update(H=a["h"], pitch=1 << a["in_pitch_log2"], k=3, step=2, pad="zero")
     d["pre"] = act.c.pre_act if isinstance(act, ops.Act) else _lib.PRE_NONE
     d["post"] = act.c.post_act if isinstance(act, ops.Act) else (a.get("post", _lib.POST_NONE) if name.startswith("resblock") else _lib.POST_NONE)
+    d["bias"] = a.get("bias") is not None
     d["res"] = "none" if res is None else ("in place" if res.data_ptr() == y.data_ptr() else "separate")
     d["rows"] = getattr(x, "_vfx_rows", None) is not None
     d["guarded"] = getattr(x, "_vfx_guard", 0) > 0
@@ -83,6 +84,10 @@ class LaunchRecorder:
     def taps(self):
         """The records that ran on the first-generation conv_taps_kernel (codes 4 / 8)."""
         return [r for r in self.records if r["code"] in (4, 8)]
+
+    def wg4s(self):
+        """The records that ran on convwg4s_kernel (code 88: the 3x3 Winograd F(4,3) kernel of the ResUNet)."""
+        return [r for r in self.records if r["code"] == 88]
 
 
 def split_k(rec):

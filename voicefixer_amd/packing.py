@@ -93,8 +93,7 @@ def _f43(g0, g1, g2):
 
 def pack_wino4_2d(w_packed):
     """[9][CinPad][Cout] (3x3 slabs ky*3 + kx) -> [18][CinPad/8][Cout][8], slab kx*6 + plane: the Winograd F(4,3) weight
-    transform along the kernel's ROW axis for every kernel column (convwg4_kernel with NKX = 3, vfx_act.w_wino4 of
-    vfx_conv2d_f32)."""
+    transform along the kernel's ROW axis for every kernel column (convwg4s_kernel, vfx_act.w_wino4 of vfx_conv2d_f32)."""
     assert w_packed.shape[0] == 9
     g = w_packed.double().reshape(3, 3, w_packed.shape[1], w_packed.shape[2])   # [ky][kx]
     planes = []
