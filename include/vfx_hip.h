@@ -108,8 +108,9 @@ typedef struct {
                                [4 planes][Cin/8][s Cout][8] whose row c s + r is (channel c, phase r), phase fastest
                                (packing.py::pack_wino32_tr; a blob in the earlier [4 r + plane][Cin/8][Cout][8] order
                                gives wrong results, there is no way to tell the two apart); launches of >= 512 workgroups with Cin % 32 == 0, Cout % 64
-                               == 0 and no activation run on convtw_kernel: three consecutive q of a phase share four
-                               products instead of six (transform constants 1 and 1/2: rounding as the direct sum's). */
+                               == 0, stride <= 32 and no activation run on convtw_kernel: three consecutive q of a phase share four
+                               products instead of six (transform constants 1 and 1/2: rounding as the direct sum's; the bias is
+                               added after the output transform). */
 } vfx_act;
 
 #define VFX_PAD_ZERO 0
@@ -218,7 +219,9 @@ int vfx_resblock_wino4_f32(const vfx_tensor* x, const vfx_tensor* y, const vfx_r
 
 /* ConvTranspose1d(Cin, Cout, kernel 2s, stride s, padding s/2 + s%2, output_padding s%2):
  * Lin -> s*Lin.  Polyphase: s phases x 2 taps.  w_packed = [2s][CinPad][Cout], slab k is
- * kernel tap k.  Replaces voicefixer/vocoder/model/modules.py:449-459,519 (UpsampleNet.layer). */
+ * kernel tap k.  Replaces voicefixer/vocoder/model/modules.py:449-459,519 (UpsampleNet.layer).
+ * stride 1 .. 8; a launch that convtw_kernel takes (vfx_act.w_wino4) may have a stride up to 32.  VFX_EINVAL for any other
+ * stride, nothing launched. */
 int vfx_convtr1d_f32(const vfx_tensor* x, const float* w_packed, const float* bias,
                      const vfx_tensor* y, int B, int Cin, int Cout, int Lin, int stride,
                      const vfx_act* act, vfx_stream_t stream);

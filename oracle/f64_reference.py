@@ -8,8 +8,9 @@ compute, written from torch primitives (``torch.nn.GRU`` with packed sequences, 
 through ``oracle.py``, so the two can check each other: tests/test_seq_reference_cpu.py and tests/test_conv_reference_cpu.py
 pin these statements against the oracle and the torch operators on the CPU, tests/test_seq_kernels_gpu.py and
 tests/test_conv_taps_gpu.py hold the kernels to them.  Ragged batches are given as a list of per-row lengths; every function
-returns float64 CPU tensors.  The last section is the yardstick of tests/test_convwg4s_gpu.py: the 3x3 convolution as a plain
-fp32 Winograd F(4,3) (conv2d_f43_f32, the one function here that returns float32) and the per-quad error figure.
+returns float64 CPU tensors.  The last sections are the yardsticks of tests/test_convwg4s_gpu.py and tests/test_convtw_gpu.py:
+the 3x3 convolution as a plain fp32 Winograd F(4,3) (conv2d_f43_f32) with the per-quad error figure, and the transposed 1-D
+convolution as a plain fp32 Winograd F(3,2) (convtr1d_f32_f32) -- the two functions here that return float32.
 """
 import torch
 
@@ -405,6 +406,49 @@ def conv2d_f43_f32(x, w, bias=None, res=None, pre=PRE_NONE, pre_slope=0.0, scale
     if res is not None:
         y = y + res.to(f32)
     return conv_post(y, post, post_slope)
+
+
+# --------------------------------------------------------------------------------------
+# the transposed 1-D convolution as Winograd F(3,2) along the input axis, in fp32 (the error yardstick of convtw_kernel)
+# --------------------------------------------------------------------------------------
+# Same spirit as conv2d_f43_f32: a plain fp32 statement of the algorithm the header of voicefixer_amd/csrc/vfx_convtw.inc
+# writes out, every operation separately rounded, the bias added after the output transform.  The reference, not a model
+# of the kernel: tests/test_convtw_gpu.py allows the device MARGIN times this statement's own figure.
+def _f32_tr_weights(w, stride):
+    """U = G g for every output phase r, g0 = w[r + s], g1 = w[r], formed in float64 and rounded once (as
+    packing.pack_wino32_tr does): w (Cin, Cout, 2 s) -> (4 planes, Cin, Cout, s phases) float32."""
+    s = stride
+    g0, g1 = w[:, :, s:].to(torch.float64), w[:, :, :s].to(torch.float64)
+    return torch.stack([g0, (g0 + g1) * 0.5, (g0 - g1) * 0.5, g1]).to(torch.float32)
+
+
+def convtr1d_f32_f32(x, w, bias=None, stride=2, lengths=None):
+    """convtr1d (no activations) computed in float32 as F(3,2) along the input axis: every output phase r is the two-tap
+    correlation out[q s + r - pad] = w[r + s] x[q - 1] + w[r] x[q], q = 0 .. Lin; three consecutive q share d_j =
+    x[3T - 1 + j]: V = B^T d, four planes m_k = sum_ci U_k V_k, y(3T) = m0 + m1 + m2, y(3T + 1) = m1 - m2, y(3T + 2) =
+    m1 + m2 + m3, then the bias.  x (B, Cin, Lin), w (Cin, Cout, 2 s) -> (B, Cout, s Lin) float32 (NaN past a row's own
+    end when `lengths` is given)."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: convtr1d_f32_f32(xb, w, bias, stride).double(), x, None, lengths,
+                        lambda n: n * stride).float()
+    s = stride
+    assert w.shape[2] == 2 * s
+    f32 = torch.float32
+    B, Cin, Lin = x.shape
+    pad = s // 2 + s % 2
+    nT = (Lin + 1 + 2) // 3                             # triples of q = 0 .. Lin
+    xp = torch.zeros((B, Cin, 3 * nT + 2), dtype=f32)
+    xp[:, :, 1:1 + Lin] = x.to(f32)
+    d = xp.unfold(2, 4, 3)                              # (B, Cin, nT, 4): x[3T - 1 .. 3T + 2]
+    d0, d1, d2, d3 = (d[..., j] for j in range(4))
+    V = [d0 - d2, d1 + d2, d2 - d1, d3 - d1]
+    U = _f32_tr_weights(w, s)
+    m = [torch.einsum("cnr,bct->bnrt", U[k], V[k]) for k in range(4)]       # (B, Cout, s, nT)
+    y = torch.stack([m[0] + m[1] + m[2], m[1] - m[2], m[1] + m[2] + m[3]], dim=4)      # (B, Cout, s, nT, 3): q = 3T + i
+    y = y.permute(0, 1, 3, 4, 2).reshape(B, w.shape[1], 3 * nT * s)[:, :, pad:pad + s * Lin]    # position q s + r - pad
+    if bias is not None:
+        y = y + bias.to(f32).reshape(1, -1, 1)
+    return y.contiguous()
 
 
 def quad_figure(got, ref, mag, lipschitz=1.0):

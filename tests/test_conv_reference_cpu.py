@@ -310,3 +310,79 @@ def test_start_values_carry_a_residual_within_the_floor(scheme, dist):
     mx, ss, cnt = ref64.quad_figure(got, ref, ref.abs())
     print("start values %s %s: quad figure max %.2f x 2^-23, rms %.3f x 2^-23" % (scheme, dist, mx / ULP, (ss / cnt) ** 0.5 / ULP))
     assert cnt == 4 * n and mx <= 4 * ULP
+
+
+# --------------------------------------------------------------------------------------
+# the fp32 F(3,2) statement of the transposed 1-D convolution (the yardstick of tests/test_convtw_gpu.py)
+# --------------------------------------------------------------------------------------
+MARGIN = 4.0
+RMS_FLOOR = 2.0 ** -24 / 3.0 ** 0.5 / 2.0      # the floors of tests/test_conv_taps_gpu.py
+F32_TR_LENGTHS = [1, 2, 3, 95, 96, 97, "ragged"]
+
+
+def _rms(fig):
+    return (fig[1] / max(fig[2], 1)) ** 0.5
+
+
+@pytest.mark.parametrize("with_bias", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("Lin", F32_TR_LENGTHS)
+@pytest.mark.parametrize("s", [1, 2, 3, 7, 8])
+def test_convtr1d_f32_f32_statement_equals_the_float64_convolution(s, Lin, with_bias):
+    """convtr1d_f32_f32 is the same operator as convtr1d.  Its conv_error figure against the float64 statement is held to
+    the level torch's own direct fp32 conv_transpose1d reaches on the same inputs: at most MARGIN = 4 times that
+    operator's figure, maximum and RMS, with the floors of the GPU tests (2^-23; 2^-24 / sqrt(3) / 2) where the operator
+    is (nearly) exact -- the relation tests/test_convtw_gpu.py then asks of the device against this statement.  A wrong
+    tap, phase, triple or coefficient is off by the order of the output.  Lengths of one and two triples and one to
+    either side, and per-row lengths."""
+    B, Cin, Cout = 6, 64, 5
+    lengths = [97, 1, 2, 3, 95, 96] if Lin == "ragged" else None
+    L = 97 if Lin == "ragged" else Lin
+    seed = 4000 + 10 * s + F32_TR_LENGTHS.index(Lin)
+    x, w = _rand((B, Cin, L), seed), _rand((Cin, Cout, 2 * s), seed + 1, (2 * Cin) ** -0.5)
+    bias = _rand((Cout,), seed + 2, 0.3) if with_bias else None
+    got = ref64.convtr1d_f32_f32(x, w, bias, s, lengths=lengths)
+    assert got.dtype == torch.float32
+    ref = ref64.convtr1d(x, w, bias, s, lengths=lengths)
+    mag = ref64.convtr1d(x, w, bias, s, lengths=lengths, magnitude=True)
+    assert got.shape == ref.shape == (B, Cout, s * L) and torch.equal(torch.isnan(got), torch.isnan(ref))
+    direct = torch.full(ref.shape, float("nan"))
+    for b, n in enumerate(lengths or [L] * B):
+        # (the full transposed convolution, cut: torch takes no output_padding of 1 at stride 1)
+        pad = s // 2 + s % 2
+        direct[b:b + 1, :, :n * s] = F.conv_transpose1d(x[b:b + 1, :, :n], w, bias, stride=s)[:, :, pad:pad + n * s]
+    fs, fd = ref64.conv_error(got, ref, mag), ref64.conv_error(direct, ref, mag)
+    print("F32TR s%d Lin %s %s: statement max %.3e rms %.3e, torch direct max %.3e rms %.3e" % (
+        s, Lin, "bias" if with_bias else "nobias", fs[0], _rms(fs), fd[0], _rms(fd)))
+    assert fs[2] == fd[2] == int((~torch.isnan(ref)).sum()) > 0
+    assert fs[0] <= MARGIN * max(fd[0], ULP), (fs[0], fd[0])
+    assert _rms(fs) <= MARGIN * max(_rms(fd), RMS_FLOOR), (_rms(fs), _rms(fd))
+
+
+@pytest.mark.parametrize("s", [1, 3, 7])
+def test_f32_tr_weights_are_the_packed_ones(s):
+    """U = G g of the statement holds bit for bit the values packing.pack_wino32_tr hands the kernel, once its blob
+    [4 planes][Cin / 8][s Cout][8] is un-permuted: row c s + r is (channel c, phase r), and position e of a group of 8
+    input channels is channel (0, 2, 4, 6, 1, 3, 5, 7)[e] (packing.pack_direct)."""
+    from voicefixer_amd import packing
+    Cin, Cout = 24, 10
+    w = _rand((Cin, Cout, 2 * s), 310 + s, 0.1)
+    U = ref64._f32_tr_weights(w, s)                                        # (4, Cin, Cout, s)
+    blob = packing.pack_wino32_tr(packing.pack_convtr1d(w), s)             # [4][Cin / 8][s Cout][8]
+    assert blob.shape == (4, Cin // 8, s * Cout, 8) and U.shape == (4, Cin, Cout, s)
+    lane_ci = torch.tensor([0, 2, 4, 6, 1, 3, 5, 7])
+    un = torch.empty_like(U)
+    b5 = blob.reshape(4, Cin // 8, Cout, s, 8)
+    for grp in range(Cin // 8):
+        un[:, grp * 8 + lane_ci] = b5[:, grp].permute(0, 3, 1, 2)          # (4, 8, Cout, s)
+    assert torch.equal(un, U)
+
+
+@pytest.mark.parametrize("s", [1, 2, 7])
+def test_convtr1d_f32_f32_zero_weights_return_the_bias(s):
+    B, Cin, Cout, Lin = 3, 16, 4, 11
+    x, bias = _rand((B, Cin, Lin), 320 + s), _rand((Cout,), 330 + s)
+    for lengths in (None, [11, 1, 5]):
+        got = ref64.convtr1d_f32_f32(x, torch.zeros((Cin, Cout, 2 * s)), bias, s, lengths=lengths)
+        for b, n in enumerate(lengths or [Lin] * B):
+            assert torch.equal(got[b, :, :n * s], bias.reshape(-1, 1).expand(Cout, n * s))
+            assert torch.isnan(got[b, :, n * s:]).all()

@@ -1691,11 +1691,12 @@ extern "C" int vfx_convtr1d_f32(const vfx_tensor* x, const float* w_packed, cons
                                 const vfx_tensor* y, int B, int Cin, int Cout, int Lin, int stride,
                                 const vfx_act* act, vfx_stream_t stream) {
     // out[o] = x[q]*w[r] + x[q-1]*w[r+s],  u = o + pad = q*s + r   
-    if (stride < 1 || stride > VFX_MAXPH) return VFX_EINVAL;
+    if (stride < 1) return VFX_EINVAL;
     if (act && act->w_wino4) {                    // the Winograd F(3,2) form (vfx_convtw.inc): 2/3 of the direct sum's MFMAs
         const int rc = try_launch_convtw(x, w_packed, act->w_wino4, bias, y, B, Cin, Cout, Lin, stride, act, (hipStream_t)stream);
         if (rc != VFX_ENOTSUP) return rc;
     }
+    if (stride > VFX_MAXPH) return VFX_EINVAL;    // (the phase table below; convtw_kernel alone takes strides up to 32)
     const int pad = stride / 2 + stride % 2;
     PhaseSpec ph[VFX_MAXPH];
     for (int r = 0; r < stride; ++r) {

@@ -19,8 +19,8 @@
 // wave 32 rows x 32 triples x 4 planes (64 accumulators); taps as dword buffer loads with one vector offset per tap (outside the row:
 // out-of-range offset = the zero padding, per-row lengths cost nothing), B^T, four planes to LDS [plane][channel][triple], double
 // buffered, 16 channels per chunk, the staging of chunk c + 1 woven between the MFMAs of chunk c; weights as 16-byte A vectors straight
-// from L2 ([plane][Cin/8][s Cout][8], packing.pack_wino32_tr), two register sets.  The bias (of the row's channel) enters as the C operand of plane
-// 1's first MFMA (y = m1 + ... for all three outputs).  No pre- / post-activation (the UpsampleNet has none: the x + sin x in front of it
+// from L2 ([plane][Cin/8][s Cout][8], packing.pack_wino32_tr), two register sets.  All four planes start at zero; the bias (of the row's channel) is
+// added after the output transform (see the epilogue).  Strides 1 .. 32.  No pre- / post-activation (the UpsampleNet has none: the x + sin x in front of it
 // is the producing kernel's epilogue); anything else stays on convw_kernel.
 template <int WGM, int WGP>
 __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
@@ -117,21 +117,7 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
         c = (int)__umulhi((unsigned)R, a.tw_rdiv) + (R & s1mask);
         p = R - c * s;
     };
-    // the issue block: bias (per channel: a gather), taps of chunk 0, first A vectors (nothing but loads)
-    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
-    unsigned bq[16];
-    {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int k = (r & 3) + 8 * (r >> 2);
-            int c0, p0, c1, p1;
-            row_cp(row0 + k, c0, p0);
-            row_cp(row0 + k + 4, c1, p1);
-            const int bvoff = a.bias ? (hi ? c1 : c0) * 4 : VFX_W_OOB;
-            bq[r] = __builtin_amdgcn_raw_buffer_load_b32(brsrc, bvoff, 0, 0);
-        }
-    }
+    // the issue block: taps of chunk 0, first A vectors (nothing but loads)
     x_load(0);
 #pragma unroll
     for (int k = 0; k < NPL; ++k) a_load_one(S0{}, k, 0);
@@ -139,9 +125,6 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
 
     f32x16 acc[NPL];
     const int boffs = hi * BT + wp * 32 + lo;
-    f32x16 biasv;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) biasv[r] = __uint_as_float(bq[r]);
     // one chunk: 8 k-pair steps x 4 MFMAs; element el of the thread is staged during steps SPAN el (transform + four LDS writes) and
     // SPAN el + SPAN / 2 (its four tap loads for the chunk after next); A vectors of the next 8-channel group in the first step of each group
     auto mma_chunk = [&](auto first_tag, const float* xs, float* wdst, int xchunk, int agrp0) {
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
                 const float av = kk == 0 ? av4.x : (kk == 1 ? av4.y : (kk == 2 ? av4.z : av4.w));
                 if (FIRST && u == 0) {
                     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], k == 1 ? biasv : zero16, 0, 0, 0);
+                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], zero16, 0, 0, 0);
                 } else {
                     acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], acc[k], 0, 0, 0);
                 }
@@ -226,6 +209,21 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
     row_cp(32 - jf, nfull, rem);
     const int jt = 32 - rem;
     const int cspan = 3 * HT * s, sL = s * Lrow;
+    // The bias of each register row's channel (a gather), added AFTER the output transform in both paths below: as a start value of plane 1
+    // it would round every partial sum of that plane at the size of the bias (up to 15 x the error of a plain fp32 F(3,2) per output on
+    // channels with a small weight-norm gain, tests/test_convtw_gpu.py).  Gathered here, not before the K loop: 16 registers less through it.
+    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
+    float bv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int k = (r & 3) + 8 * (r >> 2);
+        int c0, p0, c1, p1;
+        row_cp(rowe + k, c0, p0);
+        row_cp(rowe + k + 4, c1, p1);
+        const int bvoff = a.bias ? (hi ? c1 : c0) * 4 : VFX_W_OOB;
+        bv[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brsrc, bvoff, 0, 0));
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {               // the shared channels' rows
         const int k = (r & 3) + 8 * (r >> 2);
@@ -235,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
             row_cp(rowe + k, c0, p0);
             row_cp(rowe + k + 4, c1, p1);
             const float p12 = acc[1][r] + acc[2][r];
-            const float yo[3] = {acc[0][r] + p12, acc[1][r] - acc[2][r], p12 + acc[3][r]};
+            const float yo[3] = {acc[0][r] + p12 + bv[r], acc[1][r] - acc[2][r] + bv[r], p12 + acc[3][r] + bv[r]};
             const int rowb = hi ? (c1 * ycs + p1 - pad) * 4 : (c0 * ycs + p0 - pad) * 4;
             const int o0 = hi ? p1 - pad : p0 - pad;
             const bool mine = hi ? part1 : part0;
@@ -263,9 +261,9 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
                 if (whole) {
                     const float p12 = acc[1][r] + acc[2][r];
                     float* const d = lt + (hi ? (c1 - cf) * cspan + p1 : (c0 - cf) * cspan + p0) + 3 * tl * s;
-                    d[0] = acc[0][r] + p12;
-                    d[s] = acc[1][r] - acc[2][r];
-                    d[2 * s] = p12 + acc[3][r];
+                    d[0] = acc[0][r] + p12 + bv[r];
+                    d[s] = acc[1][r] - acc[2][r] + bv[r];
+                    d[2 * s] = p12 + acc[3][r] + bv[r];
                 }
             }
         }
@@ -310,7 +308,9 @@ static int try_launch_convtw(const vfx_tensor* x, const float* w_packed, const f
     static const bool off = VFX_DEV_ENV("VFX_CONVTW") && atoi(VFX_DEV_ENV("VFX_CONVTW")) == 0;   // development: A/B against convw_kernel
     if (off || !w_packed || !w32 || !vfx_aligned16(w32) || !x || !y || !x->ptr || !y->ptr) return VFX_ENOTSUP;
     if (act && (act->pre_act != VFX_PRE_NONE || act->post_act != VFX_POST_NONE || act->math != VFX_MATH_F32)) return VFX_ENOTSUP;
-    if (Cin < 32 || Cout <= 0 || Cin % 32 != 0 || Cout % 64 != 0 || B <= 0 || B > 65535 || Lin < 1 || stride < 1) return VFX_ENOTSUP;
+    // (stride > 32: a wave's 32 rows would lie inside one channel -- the epilogue's split into whole and shared channels, 32 - jf rows from
+    // the first whole one, assumes s <= 32)
+    if (Cin < 32 || Cout <= 0 || Cin % 32 != 0 || Cout % 64 != 0 || B <= 0 || B > 65535 || Lin < 1 || stride < 1 || stride > 32) return VFX_ENOTSUP;
     if (x->lstride != 1 || y->lstride != 1 || (bias && !vfx_aligned16(bias))) return VFX_ENOTSUP;
     const long long lim = (1ll << 31) - (1ll << 20);
     if (((long long)Cin * x->cstride + Lin) * 4 >= lim || ((long long)Cout * y->cstride + (long long)stride * Lin) * 4 >= lim) return VFX_ENOTSUP;

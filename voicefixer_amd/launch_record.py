@@ -89,6 +89,10 @@ class LaunchRecorder:
         """The records that ran on convwg4s_kernel (code 88: the 3x3 Winograd F(4,3) kernel of the ResUNet)."""
         return [r for r in self.records if r["code"] == 88]
 
+    def tw(self):
+        """The records that ran on convtw_kernel (code 83: the Winograd F(3,2) transposed convolution of the UpsampleNet)."""
+        return [r for r in self.records if r["code"] == 83]
+
 
 def split_k(rec):
     """Did split-K run?  A conv_taps launch of the product is one grid when every tile takes the same instance (guarded
