@@ -21,8 +21,9 @@
 // (16 VGPR each).  LDS is double buffered, the next K-chunk travels global -> VGPR while
 // the MFMAs of the current one run, one barrier per chunk; 33 KB of LDS and 127-155 VGPR
 // keep three to four workgroups per CU so that some stage while others compute.
-// Accumulators start at bias (+ residual); interior tiles (guard bands) run a branch-free
-// instance, instantiated per number of activation staging slots.
+// conv_taps_kernel's accumulators start at zero and bias and residual are added to the finished
+// sum in the epilogue (conv_x3_kernel and convw_kernel start theirs at bias (+ residual)); interior
+// tiles (guard bands) run a branch-free instance, instantiated per number of activation staging slots.
 #include "vfx_common.h"
 #include <cstdio>
 #include <cstdlib>
@@ -92,7 +93,9 @@ struct ConvTables {
     PhaseTab ph[VFX_MAXPH];
 };
 
+// One argument record for the whole family (the fields keep their order and size: development tools read the record as words).
 struct ConvArgs {
+    // ---- every kernel: tensors, shape, strides (w: conv_taps_kernel's packing; tab: conv_taps_kernel's tap tables)
     const float* x;
     const float* w;
     const float* bias;
@@ -103,17 +106,22 @@ struct ConvArgs {
     const ConvTables* tab;
     int B, Cin, CinPad, Cout, Lin, Lq, Lout;
     long long x_bs, x_cs, y_bs, y_cs, y_ls, r_bs, r_cs, r_ls;
+    // ---- conv_taps_kernel and convw_kernel: LDS layout and output index map
     int segw;       // LDS row pitch of the activation tile (floats, multiple of 4)
     int xs_floats;  // LDS floats reserved for the activation tile (per buffer)
-    int ws_floats;  // LDS floats reserved for the weight tile (per buffer)
+    int ws_floats;  // LDS floats reserved for the weight tile (per buffer; conv_taps_kernel)
     int q_shift, q_mask, o_rs, o_cs;  // out = (q >> q_shift)*o_rs + (q & q_mask)*o_cs + ooff
+    // ---- every kernel: padding and activations
     int pad_mode, pre_act, post_act;
     float pre_slope, post_slope;
+    // ---- conv_taps_kernel, conv_x3_kernel, convw_kernel, convwg4s_kernel: pad-column masks of pitch maps
     int in_mask, out_mask;  // pitch-1 (e.g. 127) or 0: positions with (l & mask) == mask are structural zeros
+    // ---- conv_taps_kernel: interior tiles (conv_x3_kernel: tile_lo; convtw_kernel: tile_lo = its tile order; convw_kernel,
+    // convtw_kernel: tpw = tiles per workgroup / row blocks)
     int tile_lo, tile_hi;   // interior (FAST) tiles along L: [tile_lo, tile_hi)
-    int tpw;                // consecutive L-tiles walked by one FAST workgroup
+    int tpw;                // consecutive L-tiles walked by one workgroup (conv_taps_kernel: always 1)
     int x_guard;            // readable elements before every input row (vfx_tensor.guard)
-    // split-K (few workgroups, long K: the deep UNet levels at small batch): grid.z = B * ksplit, split ks reduces
+    // ---- conv_taps_kernel: split-K (few workgroups, long K: the deep UNet levels at small batch): grid.z = B * ksplit, split ks reduces
     // K-chunks [ks*cpp, (ks+1)*cpp) and writes raw partial sums to ws[ks][b][n][q]; splitk_reduce_kernel adds them
     // in fixed order and applies bias / residual / activation / pad-column zeroing
     int ksplit, cpp, ws_ls;
@@ -196,34 +204,30 @@ __device__ __forceinline__ void stage_load(StageState<MAXXV, MAXWV>& st, const C
     const float* __restrict__ wc = a.w + (long long)c0 * a.Cout;
 #pragma unroll
     for (int j = 0; j < MAXXV; ++j) {
-        if constexpr (FAST) {
-            st.xv[j] = *reinterpret_cast<const float4*>(xc + st.x_off[j]);
-        } else {
-            const int Lin = Lin_row;
-            const bool reflect = a.pad_mode == VFX_PAD_REFLECT;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int kc = st.x_kc[j];
-            if (c0 + kc < a.Cin) {
-                const float* row = xc + (long long)kc * xcs;
-                const int l = st.x_l[j];
-                if (l >= 0 && l + 3 < Lin) {
-                    v = *reinterpret_cast<const float4*>(row + l);
-                } else {
-                    float e[4];
+        const int Lin = Lin_row;
+        const bool reflect = a.pad_mode == VFX_PAD_REFLECT;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int kc = st.x_kc[j];
+        if (c0 + kc < a.Cin) {
+            const float* row = xc + (long long)kc * xcs;
+            const int l = st.x_l[j];
+            if (l >= 0 && l + 3 < Lin) {
+                v = *reinterpret_cast<const float4*>(row + l);
+            } else {
+                float e[4];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        int g = l + k;
-                        if (reflect) {
-                            if (g < 0) g = -g;
-                            if (g >= Lin) g = 2 * (Lin - 1) - g;
-                        }
-                        e[k] = (g >= 0 && g < Lin) ? row[g] : 0.f;
+                for (int k = 0; k < 4; ++k) {
+                    int g = l + k;
+                    if (reflect) {
+                        if (g < 0) g = -g;
+                        if (g >= Lin) g = 2 * (Lin - 1) - g;
                     }
-                    v = make_float4(e[0], e[1], e[2], e[3]);
+                    e[k] = (g >= 0 && g < Lin) ? row[g] : 0.f;
                 }
+                v = make_float4(e[0], e[1], e[2], e[3]);
             }
-            st.xv[j] = v;
         }
+        st.xv[j] = v;
     }
 #pragma unroll
     for (int j = 0; j < MAXWV; ++j) st.wv[j] = *reinterpret_cast<const float4*>(wc + st.w_off[j]);
@@ -623,7 +627,6 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
     const int cbase = SPLITK ? ks * a.cpp : 0;                      // first K-chunk of this split
     const int S = SPLITK ? min(a.cpp, nchunks - cbase) : nchunks;
     int ch1 = cbase + 1, ch2 = cbase + 2;  // chunk held in registers / chunk being loaded at the top of step s
-    constexpr int ti1 = 0, ti2 = 0;
     stage_load<FAST>(st, a, xb, xcs, cbase * KC, 0, xrsrc, wrsrc, Lin_row);
     // does any staged vector of this tile leave [0, Lin)?  (uniform; only possible with a guard band)
     bool range_mask = false;
@@ -651,14 +654,14 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
             float* nxs = smem + ((s + 1) & 1) * bufstride;
             if (plain) stage_write_plain<NTHR>(st, a, nxs, nxs + a.xs_floats, nxv, nwv, xtotal, wtotal, tid);
             else stage_write<FAST, NTHR>(st, a, ch1 * KC, nxs, nxs + a.xs_floats, aff, nxv, nwv, xtotal, wtotal, tid,
-                                         ti1 * BL, range_mask, Lin_row);
+                                         0, range_mask, Lin_row);
 #if VFX_ABL & 8
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
         }
         DBG_T(t1);
         if (s + 1 < S) {
-            if (s + 2 < S) stage_load<FAST>(st, a, xb, xcs, ch2 * KC, ti2 * BL, xrsrc, wrsrc, Lin_row);
+            if (s + 2 < S) stage_load<FAST>(st, a, xb, xcs, ch2 * KC, 0, xrsrc, wrsrc, Lin_row);
         }
 #endif
         DBG_T(t2);
@@ -737,7 +740,6 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
     }
 #endif
 }
-
 
 // --------------------------------------------------------------------------------------
 // bf16x3 instance: the same tap-GEMM with every fp32 operand split into two bf16 terms
@@ -1124,36 +1126,63 @@ static const ConvTables* device_tables(const ConvTables& tb) {
     return d;
 }
 
+// vfx_last_conv_tile() = BM * 100000 + BL * 100 + code.  The numbers are ABI (include/vfx_hip.h); conv_taps_kernel reports its
+// K-chunk depth (4 or 8) as the code, the convw_kernel families add their chunk depth / 8 (1, 2 or 4) to their base.
+enum TileCode {
+    TILE_X3 = 16,          // conv_x3_kernel
+    TILE_CONVH = 32,       // convh_kernel
+    TILE_CONVW = 50,       // 51 / 52 / 54: convw_kernel, chunk depth 8 / 16 / 32
+    TILE_CONVW_2D = 59,    // convw_kernel, 3x3 on a pitch map
+    TILE_FUSED = 60,       // 61 / 62 / 64: fused ResStack layer on convw_kernel
+    TILE_FUSED_F23 = 70,   // 7x: ... with the Winograd F(2,3) second half
+    TILE_WG4 = 80,         // convwg4_kernel (Winograd F(4,3))
+    TILE_WG4P = 81,        // convwg4p_kernel (persistent workgroups)
+    TILE_WG4X = 82,        // convwg4x_kernel (32 x 64 x 6 wave tile)
+    TILE_CONVTW = 83,      // convtw_kernel (transposed, Winograd F(3,2))
+    TILE_WG4S = 88,        // convwg4s_kernel (3x3, shared staging)
+    TILE_FUSED_F43 = 90,   // 9x: fused layer with the Winograd F(4,3) second half
+    TILE_RESBLK4 = 96,     // resblk4_kernel: fused layer, both halves F(4,3)
+    TILE_RESBLK4S = 97,    // resblk4s_kernel: the same on the strip tile
+};
 static thread_local int g_last_tile = 0;
 extern "C" int vfx_last_conv_tile(void) { return g_last_tile; }
+static inline void set_last_tile(int BM, int BL, int code) { g_last_tile = BM * 100000 + BL * 100 + code; }
+
+// ---- tap geometry of a phase
+struct TapSpan {
+    int mn, mx, span;   // smallest and largest tap offset, mx - mn
+};
+static TapSpan tap_span(const PhaseSpec& ph) {
+    int mn = ph.taps[0].off, mx = mn;
+    for (int t = 1; t < ph.ntaps; ++t) {
+        mn = ph.taps[t].off < mn ? ph.taps[t].off : mn;
+        mx = ph.taps[t].off > mx ? ph.taps[t].off : mx;
+    }
+    return {mn, mx, mx - mn};
+}
+
+// the 3x3 of a map of row pitch P: 9 taps (ky-1)*P + (kx-1), slab ky*3+kx
+static bool is_pitch_3x3(const PhaseSpec& ph, int P) {
+    if (ph.ntaps != 9) return false;
+    for (int t = 0; t < 9; ++t)
+        if (ph.taps[t].off != (t / 3 - 1) * P + (t % 3 - 1) || ph.taps[t].slab != t) return false;
+    return true;
+}
+
+// one phase whose outputs are its positions (out = q + 0), all of them inside the output row
+static bool plain_output_map(const ConvArgs& a, int nphase, int ooff) {
+    return nphase == 1 && a.q_shift == 31 && a.o_rs == 0 && a.o_cs == 1 && ooff == 0 && a.Lq <= a.Lout;
+}
+
+// The kernels that address one batch item through a raw buffer resource use 32-bit BYTE offsets (num_records 2^31 - 1: anything
+// beyond reads as zero): the bytes a launch spans from the item's base stay a megabyte below 2 GB.
+static bool offsets_fit31(long long bytes) { return bytes < (1ll << 31) - (1ll << 20); }
 
 static inline int floor4(int v) { return v >= 0 ? (v & ~3) : -(((-v) + 3) & ~3); }
 
 template <int BM, int BL, int WGM, int WGL, int KC, bool FAST, int NXV = 4, bool SPLITK = false>
 static int launch_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = conv_taps_kernel<BM, BL, WGM, WGL, KC, FAST, NXV, SPLITK>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    {
-        static const bool dump = VFX_DEV_ENV("VFX_DEBUG_ARGS") && atoi(VFX_DEV_ENV("VFX_DEBUG_ARGS")) != 0;  // development
-        if (dump) {
-            fprintf(stderr, "conv_taps<%d,%d,%d,%d,%d,%d,%d,%d> grid %u %u %u lds %zu args:", BM, BL, WGM, WGL, KC, (int)FAST,
-                    NXV, (int)SPLITK, grid.x, grid.y, grid.z, lds);
-            const unsigned* w = reinterpret_cast<const unsigned*>(&a);
-            for (size_t i = 0; i < sizeof(ConvArgs) / 4; ++i) fprintf(stderr, " %08x", w[i]);
-            fprintf(stderr, "\n");
-        }
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WGM * WGL), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<conv_taps_kernel<BM, BL, WGM, WGL, KC, FAST, NXV, SPLITK>>(grid, dim3(64 * WGM * WGL), lds, s, a);
 }
 
 // interior tiles go to the FAST instance, the (few) boundary tiles to the general one
@@ -1168,7 +1197,7 @@ static int launch_cfg(const ConvArgs& a, int ntiles, int gy, int gz, size_t lds,
         return rc;
     }
     if (nfast > 0) {
-        const dim3 grid((nfast + a.tpw - 1) / a.tpw, gy, gz);
+        const dim3 grid(nfast, gy, gz);
         if constexpr (WGM * WGL == 4) {
             rc = a.nxv <= 1   ? launch_one<BM, BL, WGM, WGL, KC, true, 1>(a, grid, lds, s)
                  : a.nxv == 2 ? launch_one<BM, BL, WGM, WGL, KC, true, 2>(a, grid, lds, s)
@@ -1183,61 +1212,70 @@ static int launch_cfg(const ConvArgs& a, int ntiles, int gy, int gz, size_t lds,
     return rc;
 }
 
-static int fill_segments(ConvArgs& a, ConvTables& tb, int nphase, const PhaseSpec* phs, int BL, int KC,
-                         bool exact = false) {
-    // decide halo vs per-tap segments per phase; compute LDS pitch and offsets
-    int segw = 0;
-    bool halo[VFX_MAXPH];
+// A phase stages its taps either as ONE segment with a halo (all taps read one tile of BL + span columns at shifted columns) or as
+// one BL-column segment per tap (large dilations): the halo form while it is no wider than the segments.
+static bool halo_fits(const PhaseSpec& ph, int BL) {
+    return (long long)BL + tap_span(ph).span + 3 <= (long long)ph.ntaps * (BL + 3);
+}
+
+// widest tap span of the phases; *all_segments: no phase stages a halo tile of BL columns
+static int max_tap_span(int nphase, const PhaseSpec* phs, int BL, bool* all_segments) {
+    int maxspan = 0;
+    *all_segments = true;
     for (int p = 0; p < nphase; ++p) {
-        int mn = phs[p].taps[0].off, mx = mn;
-        for (int t = 1; t < phs[p].ntaps; ++t) {
-            mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-            mx = phs[p].taps[t].off > mx ? phs[p].taps[t].off : mx;
+        const int span = tap_span(phs[p]).span;
+        maxspan = span > maxspan ? span : maxspan;
+        *all_segments &= !halo_fits(phs[p], BL);
+    }
+    return maxspan;
+}
+
+// The table of one phase: a halo segment from the smallest tap offset, or one segment per tap ``pitch`` LDS elements apart.
+// exact: unaligned origins (interior instance, buffer loads); otherwise origins are aligned down to a multiple of 4.
+static void fill_phase(PhaseTab& T, const PhaseSpec& ph, bool halo, bool exact, int pitch) {
+    T.ntaps = ph.ntaps;
+    T.ooff = ph.ooff;
+    T.nseg = halo ? 1 : ph.ntaps;
+    const int mn = tap_span(ph).mn;
+    for (int t = 0; t < ph.ntaps; ++t) {
+        const int from = halo ? mn : ph.taps[t].off;
+        const int org = exact ? from : floor4(from);
+        T.seg_org[halo ? 0 : t] = org;
+        T.tap_lds[t] = (halo ? 0 : t * pitch) + (ph.taps[t].off - org);
+        T.tap_w[t] = ph.taps[t].slab;
+    }
+}
+
+// the smallest and the largest segment origin of a table
+static TapSpan segment_range(const ConvTables& tb, int nphase) {
+    int lo = 0x7fffffff, hi = -0x7fffffff;
+    for (int p = 0; p < nphase; ++p)
+        for (int sg = 0; sg < tb.ph[p].nseg; ++sg) {
+            lo = tb.ph[p].seg_org[sg] < lo ? tb.ph[p].seg_org[sg] : lo;
+            hi = tb.ph[p].seg_org[sg] > hi ? tb.ph[p].seg_org[sg] : hi;
         }
-        const int span = mx - mn;
-        halo[p] = (long long)BL + span + 3 <= (long long)phs[p].ntaps * (BL + 3);
-        int need;
-        if (halo[p]) {
-            need = exact ? BL : (mn - floor4(mn)) + BL + span;
-        } else {
-            need = exact ? BL : BL + 3;
-        }
+    return {lo, hi, hi - lo};
+}
+
+static int max_segments(const ConvTables& tb, int nphase) {
+    int maxseg = 0;
+    for (int p = 0; p < nphase; ++p) maxseg = tb.ph[p].nseg > maxseg ? tb.ph[p].nseg : maxseg;
+    return maxseg;
+}
+
+// halo vs per-tap segments per phase, the LDS row pitch (a.segw) and the tables of a tile of BL columns in chunks of KC channels
+static void fill_segments(ConvArgs& a, ConvTables& tb, int nphase, const PhaseSpec* phs, int BL, int KC, bool exact = false) {
+    int segw = 0;
+    for (int p = 0; p < nphase; ++p) {
+        const TapSpan ts = tap_span(phs[p]);
+        int need = exact ? BL : (halo_fits(phs[p], BL) ? (ts.mn - floor4(ts.mn)) + BL + ts.span : BL + 3);
         need = (need + 3) & ~3;
         segw = need > segw ? need : segw;
     }
     a.segw = segw;
-    int xs = 0;
-    for (int p = 0; p < nphase; ++p) {
-        PhaseTab& T = tb.ph[p];
-        T.ntaps = phs[p].ntaps;
-        T.ooff = phs[p].ooff;
-        if (halo[p]) {
-            int mn = phs[p].taps[0].off;
-            for (int t = 1; t < phs[p].ntaps; ++t) mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-            const int org = exact ? mn : floor4(mn);  // exact: unaligned origin (interior instance, buffer loads)
-            T.nseg = 1;
-            T.seg_org[0] = org;
-            for (int t = 0; t < phs[p].ntaps; ++t) {
-                T.tap_lds[t] = phs[p].taps[t].off - org;
-                T.tap_w[t] = phs[p].taps[t].slab;
-            }
-        } else {
-            T.nseg = phs[p].ntaps;
-            for (int t = 0; t < phs[p].ntaps; ++t) {
-                const int org = exact ? phs[p].taps[t].off : floor4(phs[p].taps[t].off);
-                T.seg_org[t] = org;
-                T.tap_lds[t] = t * KC * segw + (phs[p].taps[t].off - org);
-                T.tap_w[t] = phs[p].taps[t].slab;
-            }
-        }
-        const int fl = T.nseg * KC * segw;
-        xs = fl > xs ? fl : xs;
-    }
-    a.xs_floats = xs;
-    return VFX_OK;
+    for (int p = 0; p < nphase; ++p) fill_phase(tb.ph[p], phs[p], halo_fits(phs[p], BL), exact, KC * segw);
+    a.xs_floats = max_segments(tb, nphase) * KC * segw;
 }
-
-
 
 // split-K workspace: one growing device buffer per stream (allocated during warm-up; a launch that fits reuses it)
 static float* splitk_workspace(hipStream_t s, size_t bytes) {
@@ -1264,10 +1302,6 @@ static float* splitk_workspace(hipStream_t s, size_t bytes) {
     return e.first;
 }
 
-// ---- bf16x3 launch path (opt-in per launch, vfx_act.math == VFX_MATH_BF16X3).  Returns VFX_ENOTSUP when the
-// geometry is outside what conv_x3_kernel covers; the caller then runs the fp32 kernel (the code is never returned
-// through the C ABI from here).
-
 #include "vfx_convw.inc"
 #include "vfx_convwg.inc"
 #include "vfx_convwg4p.inc"
@@ -1278,21 +1312,12 @@ static float* splitk_workspace(hipStream_t s, size_t bytes) {
 #include "vfx_resblk4s.inc"
 #include "vfx_convh.inc"
 
+// ---- bf16x3 launch path (opt-in per launch, vfx_act.math == VFX_MATH_BF16X3).  Returns VFX_ENOTSUP when the
+// geometry is outside what conv_x3_kernel covers; the caller then runs the fp32 kernel (the code is never returned
+// through the C ABI from here).
 template <int BM, int BL, int WGM, int WGL, int NT, int MODE, int ROWS = 1>
 static int launch_x3_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = conv_x3_kernel<BM, BL, WGM, WGL, NT, MODE, ROWS>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<conv_x3_kernel<BM, BL, WGM, WGL, NT, MODE, ROWS>>(grid, dim3(256), lds, s, a);
 }
 
 template <int BM, int BL, int WGM, int WGL>
@@ -1317,16 +1342,14 @@ static int try_launch_x3(ConvArgs a, const vfx_tensor* x, int nphase, const Phas
     if (!w3 || !vfx_aligned16(w3) || Cin % 32 != 0 || Cout % 32 != 0) return VFX_ENOTSUP;
     if (a.pad_mode == VFX_PAD_REFLECT || a.x_rows) return VFX_ENOTSUP;  // (no per-row lengths in the bf16x3 kernel)
     // (raw buffer resource, 32-bit byte offsets within one batch item: see launch_conv)
-    if (((long long)a.CinPad * x->cstride + Lin + 2 * x->guard) * 4 >= (1ll << 31) - (1ll << 20)) return VFX_ENOTSUP;
-    // 3x3 on a pitch map (9 taps (ky-1)*P + (kx-1), slab ky*3+kx) -> 3 kernel rows x the 3-tap dx case
+    if (!offsets_fit31(((long long)a.CinPad * x->cstride + Lin + 2 * x->guard) * 4)) return VFX_ENOTSUP;
+    // 3x3 on a pitch map (is_pitch_3x3) -> 3 kernel rows x the 3-tap dx case
     int rows = 1, P = 0;
     PhaseSpec row_spec;
     const PhaseSpec* phs = phs_in;
     if (nphase == 1 && phs_in[0].ntaps == 9) {
         P = phs_in[0].taps[3].off - phs_in[0].taps[0].off;
-        for (int t = 0; t < 9; ++t)
-            if (phs_in[0].taps[t].off != (t / 3 - 1) * P + (t % 3 - 1) || phs_in[0].taps[t].slab != t) return VFX_ENOTSUP;
-        if (P < 4) return VFX_ENOTSUP;
+        if (!is_pitch_3x3(phs_in[0], P) || P < 4) return VFX_ENOTSUP;
         rows = 3;
         row_spec.ntaps = 3;
         row_spec.ooff = phs_in[0].ooff;
@@ -1353,14 +1376,10 @@ static int try_launch_x3(ConvArgs a, const vfx_tensor* x, int nphase, const Phas
     int span = 0, seg_lo = 0x7fffffff, seg_hi = -0x7fffffff;
     for (int p = 0; p < nphase; ++p) {
         if (phs[p].ntaps != nt) return VFX_ENOTSUP;
-        int mn = phs[p].taps[0].off, mx = mn;
-        for (int t = 1; t < nt; ++t) {
-            mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-            mx = phs[p].taps[t].off > mx ? phs[p].taps[t].off : mx;
-        }
-        span = mx - mn > span ? mx - mn : span;
-        seg_lo = mn < seg_lo ? mn : seg_lo;
-        seg_hi = mx > seg_hi ? mx : seg_hi;
+        const TapSpan ts = tap_span(phs[p]);
+        span = ts.span > span ? ts.span : span;
+        seg_lo = ts.mn < seg_lo ? ts.mn : seg_lo;
+        seg_hi = ts.mx > seg_hi ? ts.mx : seg_hi;
     }
     // staging mode: 0 = halo inside the BL staged columns (tile of BL - span outputs, small spans),
     // 1 = BL + span columns (one more staging slot), 2 = one segment per tap (large dilations)
@@ -1380,19 +1399,7 @@ static int try_launch_x3(ConvArgs a, const vfx_tensor* x, int nphase, const Phas
     const int bl_eff = mode == 0 ? BL - span : BL;
     ConvTables tb;
     std::memset(&tb, 0, sizeof(tb));
-    for (int p = 0; p < nphase; ++p) {
-        PhaseTab& T = tb.ph[p];
-        T.ntaps = nt;
-        T.ooff = phs[p].ooff;
-        int mn = phs[p].taps[0].off;
-        for (int t = 1; t < nt; ++t) mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-        T.nseg = seg ? nt : 1;
-        for (int t = 0; t < nt; ++t) {
-            if (seg) { T.seg_org[t] = phs[p].taps[t].off; T.tap_lds[t] = t * segw; }
-            else { T.seg_org[0] = mn; T.tap_lds[t] = phs[p].taps[t].off - mn; }
-            T.tap_w[t] = phs[p].taps[t].slab;
-        }
-    }
+    for (int p = 0; p < nphase; ++p) fill_phase(tb.ph[p], phs[p], !seg, true, segw);   // (tables in POSITIONS, exact origins)
     // every tile must be interior with respect to the guard band (loads inside [-guard, Lin + guard))
     const int ntiles = (Lq + bl_eff - 1) / bl_eff;
     const long long g = a.x_guard;
@@ -1419,8 +1426,7 @@ static int try_launch_x3(ConvArgs a, const vfx_tensor* x, int nphase, const Phas
     if ((long long)ntiles * (nphase * Cout / BM) * B <= 96 && Cin * (rows == 3 && nt == 3 ? 9 : nt) >= 1024)
         return VFX_ENOTSUP;
     const dim3 grid(ntiles, nphase * Cout / BM, B);
-    g_last_tile = BM * 100000 + BL * 100 + 16;
-    (void)x;
+    set_last_tile(BM, BL, TILE_X3);
     if (BM == 128) return launch_x3_tile<128, 128, 2, 2>(a, nt, mode, rows, grid, lds, stream);
     if (BM == 32) {
         if (rows == 3 && nt == 3) return launch_x3_one<32, 256, 1, 4, 3, 0, 3>(a, grid, lds, stream);
@@ -1432,10 +1438,11 @@ static int try_launch_x3(ConvArgs a, const vfx_tensor* x, int nphase, const Phas
     return launch_x3_tile<64, 128, 1, 4>(a, nt, mode, rows, grid, lds, stream);
 }
 
-static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, const vfx_tensor* res,
-                       const vfx_tensor* y, int B, int Cin, int Cout, int Lin, int Lq, int Lout,
-                       int nphase, const PhaseSpec* phs, int q_shift, int q_mask, int o_rs, int o_cs,
-                       int pad_mode, const vfx_act* act, int in_mask, int out_mask, hipStream_t stream) {
+// ---- launch_conv, step 1: the checks of a call and its argument record (the fields every kernel of the chain shares)
+static int conv_args(ConvArgs& a, const vfx_tensor* x, const float* w, const float* bias, const vfx_tensor* res,
+                     const vfx_tensor* y, int B, int Cin, int Cout, int Lin, int Lq, int Lout,
+                     int nphase, const PhaseSpec* phs, int q_shift, int q_mask, int o_rs, int o_cs,
+                     int pad_mode, const vfx_act* act, int in_mask, int out_mask) {
     if (!x || !y || !w || !x->ptr || !y->ptr || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lq <= 0)
         return VFX_EINVAL;
     if (Cout % 32 != 0 || nphase < 1 || nphase > VFX_MAXPH) return VFX_EINVAL;
@@ -1444,7 +1451,6 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     if (pad_mode == VFX_PAD_REFLECT && Lin < 8) return VFX_EINVAL;
     if (B > 65535) return VFX_EINVAL;
 
-    ConvArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = (const float*)x->ptr;
     a.w = w;
@@ -1460,7 +1466,7 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     a.y_bs = y->bstride; a.y_cs = y->cstride; a.y_ls = y->lstride;
     if (res) { a.r_bs = res->bstride; a.r_cs = res->cstride; a.r_ls = res->lstride; }
     a.q_shift = q_shift; a.q_mask = q_mask; a.o_rs = o_rs; a.o_cs = o_cs;
-    a.res_init = res && nphase == 1 && q_shift == 31 && o_rs == 0 && o_cs == 1 && phs[0].ooff == 0 && Lq <= Lout &&
+    a.res_init = res && plain_output_map(a, nphase, phs[0].ooff) &&
                  (long long)Cout * res->cstride + (long long)Lq * res->lstride < (1ll << 31);
     a.pad_mode = pad_mode;
     a.pre_act = act ? act->pre_act : VFX_PRE_NONE;
@@ -1471,41 +1477,37 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     a.post_slope = act ? act->post_slope : 0.f;
     if (a.pre_act == VFX_PRE_AFFINE_LRELU && (!a.pre_scale || !a.pre_shift)) return VFX_EINVAL;
     a.in_mask = in_mask; a.out_mask = out_mask;
+    return VFX_OK;
+}
 
-    int maxnt = 0;
-    for (int p = 0; p < nphase; ++p) maxnt = phs[p].ntaps > maxnt ? phs[p].ntaps : maxnt;
-    if (maxnt < 1 || maxnt > VFX_MAXT) return VFX_EINVAL;
-    if (act && act->math == VFX_MATH_BF16X3) {
-        const int rc3 = try_launch_x3(a, x, nphase, phs, act->w_x3, stream);
-        if (rc3 != VFX_ENOTSUP) return rc3;
+// ---- step 2: the kernels that take a launch before conv_taps_kernel, in order.  VFX_ENOTSUP: none of them did.
+static int try_kernel_chain(const ConvArgs& a, const vfx_tensor* x, int nphase, const PhaseSpec* phs, const vfx_act* act,
+                            hipStream_t stream) {
+    if (!act) return VFX_ENOTSUP;
+    if (act->math == VFX_MATH_BF16X3) {
+        const int rc = try_launch_x3(a, x, nphase, phs, act->w_x3, stream);
+        if (rc != VFX_ENOTSUP) return rc;
     }
-    if (act && act->w_wino4) {
-        int rc4 = VFX_ENOTSUP;
-        if (nphase == 1 && phs[0].ntaps == 9 && in_mask > 0) {
-            const int P = in_mask + 1;
-            bool ok = true;
-            for (int t = 0; t < 9; ++t) ok &= phs[0].taps[t].off == (t / 3 - 1) * P + (t % 3 - 1) && phs[0].taps[t].slab == t;
-            if (ok) rc4 = try_launch_convwg4s_2d(a, x, P, act->w_wino4, stream);
-        } else {
-            rc4 = try_launch_convwg4(a, x, nphase, phs, act->w_wino4, stream);
-        }
-        if (rc4 != VFX_ENOTSUP) return rc4;
+    // nine taps on a pitch map go to the 2-D kernels, and only as that map's 3x3; everything else to the 1-D ones
+    const bool map9 = nphase == 1 && phs[0].ntaps == 9 && a.in_mask > 0;
+    const int P = a.in_mask + 1;
+    const bool offer = !map9 || is_pitch_3x3(phs[0], P);
+    if (act->w_wino4 && offer) {
+        const int rc = map9 ? try_launch_convwg4s_2d(a, x, P, act->w_wino4, stream)
+                            : try_launch_convwg4(a, x, nphase, phs, act->w_wino4, stream);
+        if (rc != VFX_ENOTSUP) return rc;
     }
-    if (act && act->w_direct) {
-        int rcw = VFX_ENOTSUP;
-        if (nphase == 1 && phs[0].ntaps == 9 && in_mask > 0) {
-            // 3x3 on a pitch map: taps (ky-1)*P + (kx-1), slab ky*3+kx
-            const int P = in_mask + 1;
-            bool ok = true;
-            for (int t = 0; t < 9; ++t) ok &= phs[0].taps[t].off == (t / 3 - 1) * P + (t % 3 - 1) && phs[0].taps[t].slab == t;
-            if (ok) rcw = try_launch_convw_2d(a, x, P, act->w_direct, stream);
-        } else {
-            rcw = try_launch_convw(a, x, nphase, phs, act->w_direct, stream);
-        }
-        if (rcw != VFX_ENOTSUP) return rcw;
+    if (act->w_direct && offer) {
+        const int rc = map9 ? try_launch_convw_2d(a, x, P, act->w_direct, stream)
+                            : try_launch_convw(a, x, nphase, phs, act->w_direct, stream);
+        if (rc != VFX_ENOTSUP) return rc;
     }
-    // tile choice: maximise (tile efficiency) x (tail efficiency along L) x (wave quantisation)
-    int best = -1;
+    return VFX_ENOTSUP;
+}
+
+// ---- step 3: the tile that maximises (tile efficiency) x (tail efficiency along L) x (wave quantisation); NULL: none divides Cout
+static const TileCfg* choose_tile(int B, int Cout, int Lq, int nphase) {
+    const TileCfg* best = nullptr;
     float best_score = -1.f;
     for (int i = 0; i < kNumTiles; ++i) {
         const TileCfg& t = kTiles[i];
@@ -1516,19 +1518,62 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
         const long long slots = 512;  // 2 workgroups per CU x 256 CUs
         const float quant = (float)nwg / (float)(((nwg + slots - 1) / slots) * slots);
         const float score = t.util * tail * quant;
-        if (score > best_score * 1.02f) { best_score = score; best = i; }
+        if (score > best_score * 1.02f) { best_score = score; best = &t; }
     }
-    if (best < 0) return VFX_EINVAL;
-    const TileCfg& tc = kTiles[best];
+    return best;
+}
 
-    // K-chunk depth: 8 channels per chunk unless the staged tiles would need more than 4 float4 per
-    // thread (activations) / the weight tile more than its slot budget -> 4 channels per chunk
-    // development switch: VFX_WAVES8=1 runs the two big tiles with 8 waves (wave tile 32x64)
-    static const bool waves8_env = VFX_DEV_ENV("VFX_WAVES8") && atoi(VFX_DEV_ENV("VFX_WAVES8")) != 0;
-    const bool waves8 = waves8_env && ((tc.BM == 128 && tc.BL == 128) || (tc.BM == 64 && tc.BL == 256));
-    const int nthr = waves8 ? 512 : 256;
+// what steps 4 and 5 decide beyond the fields of ConvArgs
+struct TapsPlan {
+    ConvTables tb;
+    int KC, ntiles;
+    size_t lds;
+    bool waves8;   // development: 8 waves per workgroup on the two big tiles
+};
+
+// ---- step 4a: K-chunk depth and tables.  From ``KC`` down to 4 channels per chunk until the staged activation tile needs no
+// more than 4 float4 per thread and the weight tile no more than its slot budget; 0: not even 4 fit.
+static int plan_chunk_depth(ConvArgs& a, ConvTables& tb, int nphase, const PhaseSpec* phs, const TileCfg& tc, int maxnt, int nthr,
+                            bool exact, int KC) {
+    for (;; KC = KC == 16 ? 8 : 4) {
+        std::memset(&tb, 0, sizeof(tb));
+        fill_segments(a, tb, nphase, phs, tc.BL, KC, exact);
+        const long long xvec = (long long)max_segments(tb, nphase) * KC * (a.segw / 4);
+        a.nxv = (int)((xvec + nthr - 1) / nthr);
+        const bool wfit = (long long)maxnt * KC * tc.BM <= (KC == 16 ? 6 : (KC == 8 ? 4 : 5)) * 4 * nthr;
+        if (xvec <= 4 * nthr && wfit) return KC;
+        if (KC == 4) return 0;
+    }
+}
+
+// ---- step 4b: interior tiles [tile_lo, tile_hi): all staged vectors of all phases inside the readable range, no channel tail
+static void plan_interior_tiles(ConvArgs& a, const ConvTables& tb, const vfx_tensor* x, int nphase, int ntiles, int KC) {
+    const TapSpan seg = segment_range(tb, nphase);
+    // loads are safe inside [-guard, Lin + guard); values outside [0, Lin) are masked in the kernel
+    const long long g = (x->guard > 0 && a.pad_mode != VFX_PAD_REFLECT) ? x->guard : 0;
+    const long long need_lo = -(long long)seg.mn - g;  // q0 >= need_lo
+    int tlo = need_lo > 0 ? (int)((need_lo + a.bl_step - 1) / a.bl_step) : 0;
+    const long long room = (long long)a.Lin + g - seg.mx - a.segw;
+    int thi = room >= 0 ? (int)(room / a.bl_step) + 1 : 0;
+    if (thi > ntiles) thi = ntiles;
+    if (tlo > thi || a.Cin % KC != 0) { tlo = 0; thi = 0; }
+    // the interior instance reads one batch item with 32-bit byte offsets (offsets_fit31): rows of a batch item spanning 2 GB
+    // or more (a 64-channel stage of > 3 minutes) run the general, pointer-addressed instance on every tile
+    if (!offsets_fit31(((long long)a.CinPad * x->cstride + a.Lin + 2 * g) * 4)) { tlo = 0; thi = 0; }
+    // ragged batches: a tile that is interior for the longest row holds the END of a shorter one, and only the
+    // general instance mirrors there (the interior one can only zero what lies outside the row)
+    if (a.x_rows && a.pad_mode == VFX_PAD_REFLECT) { tlo = 0; thi = 0; }
+    a.tile_lo = tlo;
+    a.tile_hi = thi;
+}
+
+// ---- step 4: chunk depth, exact or aligned layout, LDS size, tile count, interior tiles
+static int plan_layout(ConvArgs& a, TapsPlan& pl, const vfx_tensor* x, int nphase, const PhaseSpec* phs, const TileCfg& tc, int maxnt) {
+    const int Cin = a.Cin;
+    const int nthr = pl.waves8 ? 512 : 256;
     // development switch: VFX_KC16=1 lets 3-tap (or fewer) launches on the 128x128 tile use 16-channel chunks
     static const bool kc16_env = VFX_DEV_ENV("VFX_KC16") && atoi(VFX_DEV_ENV("VFX_KC16")) != 0;
+    const bool kc16 = kc16_env && maxnt <= 3 && tc.BM == 128 && tc.BL == 128 && !pl.waves8 && Cin % 16 == 0;
     // Exact-width halo tiles: when the taps of every phase span only a few positions (dilation <= 3, transposed
     // convolutions, k = 1) the halo is staged INSIDE the BL columns and a tile produces BL - span outputs.  The
     // activation tile then needs exactly one staging slot per thread (half the loads, conversions and LDS writes
@@ -1536,119 +1581,61 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     // instance on every tile (guard band), and no pad-column mask (its fast path assumes aligned vectors).
     // Launches whose phases all stage one segment per tap (wide dilations) get exact BL-wide segments the same
     // way (no alignment slack: 3 slots instead of 4), at no cost in columns.
-    int maxspan = 0;
-    bool all_segments = true;
-    for (int p = 0; p < nphase; ++p) {
-        int mn = phs[p].taps[0].off, mx = mn;
-        for (int t = 1; t < phs[p].ntaps; ++t) {
-            mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-            mx = phs[p].taps[t].off > mx ? phs[p].taps[t].off : mx;
-        }
-        maxspan = mx - mn > maxspan ? mx - mn : maxspan;
-        all_segments &= !((long long)tc.BL + (mx - mn) + 3 <= (long long)phs[p].ntaps * (tc.BL + 3));
-    }
+    bool all_segments;
+    const int maxspan = max_tap_span(nphase, phs, tc.BL, &all_segments);
     static const int exact_off = VFX_DEV_ENV("VFX_NO_EXACT") ? atoi(VFX_DEV_ENV("VFX_NO_EXACT")) : 0;  // development: 1 all, 2 segments
-    bool exact = exact_off != 1 && x->guard > 0 && pad_mode != VFX_PAD_REFLECT && in_mask == 0 && !waves8 &&
+    bool exact = exact_off != 1 && x->guard > 0 && a.pad_mode != VFX_PAD_REFLECT && a.in_mask == 0 && !pl.waves8 &&
                  ((maxspan > 0 && maxspan <= 8) || (all_segments && exact_off != 2));
-    ConvTables tb;
-    int KC, ntiles;
-    size_t lds;
-    for (;;) {
-        KC = (kc16_env && maxnt <= 3 && tc.BM == 128 && tc.BL == 128 && !waves8 && Cin % 16 == 0) ? 16 : 8;
-        for (;;) {
-            std::memset(&tb, 0, sizeof(tb));
-            int rc = fill_segments(a, tb, nphase, phs, tc.BL, KC, exact);
-            if (rc) return rc;
-            int maxseg = 0;
-            for (int p = 0; p < nphase; ++p) maxseg = tb.ph[p].nseg > maxseg ? tb.ph[p].nseg : maxseg;
-            const bool xfit = (long long)maxseg * KC * (a.segw / 4) <= 4 * nthr;
-            a.nxv = (int)(((long long)maxseg * KC * (a.segw / 4) + nthr - 1) / nthr);
-            const bool wfit = (long long)maxnt * KC * tc.BM <= (KC == 16 ? 6 : (KC == 8 ? 4 : 5)) * 4 * nthr;
-            if (xfit && wfit) break;
-            if (KC == 4) return VFX_ERANGE;
-            KC = KC == 16 ? 8 : 4;
-        }
-        a.ws_floats = maxnt * KC * tc.BM;
-        lds = (2ull * (a.xs_floats + a.ws_floats) + 2ull * a.CinPad) * sizeof(float);
-        {
-            // development knob: VFX_LDS_MIN_KB pads the request to limit workgroups per CU (occupancy studies)
-            static const long pad_kb = VFX_DEV_ENV("VFX_LDS_MIN_KB") ? atol(VFX_DEV_ENV("VFX_LDS_MIN_KB")) : 0;
-            if (pad_kb > 0 && lds < (size_t)pad_kb * 1024) lds = (size_t)pad_kb * 1024;
-        }
-        if (lds > 160 * 1024) return VFX_ERANGE;
-
-        // interior tiles: all staged vectors of all phases inside [0, Lin) and no channel tail
+    // the exact layout holds only when every tile is interior: a launch with boundary tiles is planned again, aligned
+    for (;; exact = false) {
+        pl.KC = plan_chunk_depth(a, pl.tb, nphase, phs, tc, maxnt, nthr, exact, kc16 ? 16 : 8);
+        if (!pl.KC) return VFX_ERANGE;
+        a.ws_floats = maxnt * pl.KC * tc.BM;
+        pl.lds = (2ull * (a.xs_floats + a.ws_floats) + 2ull * a.CinPad) * sizeof(float);
+        // development knob: VFX_LDS_MIN_KB pads the request to limit workgroups per CU (occupancy studies)
+        static const long pad_kb = VFX_DEV_ENV("VFX_LDS_MIN_KB") ? atol(VFX_DEV_ENV("VFX_LDS_MIN_KB")) : 0;
+        if (pad_kb > 0 && pl.lds < (size_t)pad_kb * 1024) pl.lds = (size_t)pad_kb * 1024;
+        if (pl.lds > 160 * 1024) return VFX_ERANGE;
         a.bl_step = (exact && !all_segments) ? tc.BL - maxspan : tc.BL;
-        ntiles = (Lq + a.bl_step - 1) / a.bl_step;
-        int seg_lo = 0x7fffffff, seg_hi = -0x7fffffff;
-        for (int p = 0; p < nphase; ++p)
-            for (int sg = 0; sg < tb.ph[p].nseg; ++sg) {
-                seg_lo = tb.ph[p].seg_org[sg] < seg_lo ? tb.ph[p].seg_org[sg] : seg_lo;
-                seg_hi = tb.ph[p].seg_org[sg] > seg_hi ? tb.ph[p].seg_org[sg] : seg_hi;
-            }
-        // loads are safe inside [-guard, Lin + guard); values outside [0, Lin) are masked in the kernel
-        const long long g = (x->guard > 0 && pad_mode != VFX_PAD_REFLECT) ? x->guard : 0;
-        const long long need_lo = -(long long)seg_lo - g;  // q0 >= need_lo
-        int tlo = need_lo > 0 ? (int)((need_lo + a.bl_step - 1) / a.bl_step) : 0;
-        const long long room = (long long)Lin + g - seg_hi - a.segw;
-        int thi = room >= 0 ? (int)(room / a.bl_step) + 1 : 0;
-        if (thi > ntiles) thi = ntiles;
-        if (tlo > thi || Cin % KC != 0) { tlo = 0; thi = 0; }
-        // the interior instance reads one batch item through a raw buffer resource with 32-bit byte offsets
-        // (num_records 2^31 - 1: anything beyond reads as zero): rows of a batch item spanning 2 GB or more (a
-        // 64-channel stage of > 3 minutes) run the general, pointer-addressed instance on every tile
-        if (((long long)a.CinPad * x->cstride + Lin + 2 * g) * 4 >= (1ll << 31) - (1ll << 20)) { tlo = 0; thi = 0; }
-        // ragged batches: a tile that is interior for the longest row holds the END of a shorter one, and only the
-        // general instance mirrors there (the interior one can only zero what lies outside the row)
-        if (a.x_rows && pad_mode == VFX_PAD_REFLECT) { tlo = 0; thi = 0; }
-        a.tile_lo = tlo;
-        a.tile_hi = thi;
-        if (exact && !(tlo == 0 && thi == ntiles)) { exact = false; continue; }  // boundary tiles: aligned layout
-        break;
+        pl.ntiles = (a.Lq + a.bl_step - 1) / a.bl_step;
+        plan_interior_tiles(a, pl.tb, x, nphase, pl.ntiles, pl.KC);
+        if (!exact || (a.tile_lo == 0 && a.tile_hi == pl.ntiles)) return VFX_OK;
     }
-    a.tab = device_tables(tb);
-    if (!a.tab) return VFX_EINVAL;
-    a.two_level = KC == 4 && Cin >= 256;
-    g_last_tile = tc.BM * 100000 + tc.BL * 100 + KC;
-    // split-K: a launch with few workgroups and a long K (the deep UNet levels at small batch: 48 workgroups x 864
-    // serial K-chunks) is cut along K so that the whole chip works on it; plain output maps only
+}
+
+// ---- step 5: split-K.  A launch with few workgroups and a long K (the deep UNet levels at small batch: 48 workgroups x 864
+// serial K-chunks) is cut along K so that the whole chip works on it; plain output maps only.
+static void plan_splitk(ConvArgs& a, const TapsPlan& pl, const TileCfg& tc, int nphase, int ooff, hipStream_t stream) {
+    static const bool splitk_off = VFX_DEV_ENV("VFX_NO_SPLITK") && atoi(VFX_DEV_ENV("VFX_NO_SPLITK")) != 0;  // development
     a.ksplit = 1;
-    {
-        static const bool splitk_off = VFX_DEV_ENV("VFX_NO_SPLITK") && atoi(VFX_DEV_ENV("VFX_NO_SPLITK")) != 0;  // development
-        const int nchunks = (Cin + KC - 1) / KC;
-        const long long nwg = (long long)ntiles * (nphase * Cout / tc.BM) * B;
-        const bool plain_map = nphase == 1 && q_shift == 31 && o_rs == 0 && o_cs == 1 && phs[0].ooff == 0 && Lq <= Lout;
-        if (!splitk_off && plain_map && nwg <= 192 && nchunks >= 32) {
-            int want = (int)(512 / nwg);
-            if (want > 8) want = 8;
-            if (want > nchunks / 16) want = nchunks / 16;
-            if (want >= 2 && (long long)B * want <= 65535) {
-                a.cpp = (nchunks + want - 1) / want;
-                a.ksplit = (nchunks + a.cpp - 1) / a.cpp;
-                a.ws_ls = Lq;
-                a.ws = splitk_workspace(stream, (size_t)a.ksplit * B * Cout * Lq * sizeof(float));
-                if (!a.ws) a.ksplit = 1;
-            }
-        }
-    }
-    {
-        // tiles per FAST workgroup: as many as keeps >= ~1024 workgroups in flight, at most 8
-        const long long nwg1 = (long long)(a.tile_hi - a.tile_lo) * (nphase * Cout / tc.BM) * B;
-        (void)nwg1;
-        a.tpw = 1;  // multi-tile workgroups measured slower (register pressure), see the kernel comment
-    }
-    const int gy = nphase * Cout / tc.BM;
-    const int gz = B * a.ksplit;
+    const int nchunks = (a.Cin + pl.KC - 1) / pl.KC;
+    const long long nwg = (long long)pl.ntiles * (nphase * a.Cout / tc.BM) * a.B;
+    if (splitk_off || !plain_output_map(a, nphase, ooff) || nwg > 192 || nchunks < 32) return;
+    int want = (int)(512 / nwg);
+    if (want > 8) want = 8;
+    if (want > nchunks / 16) want = nchunks / 16;
+    if (want < 2 || (long long)a.B * want > 65535) return;
+    a.cpp = (nchunks + want - 1) / want;
+    a.ksplit = (nchunks + a.cpp - 1) / a.cpp;
+    a.ws_ls = a.Lq;
+    a.ws = splitk_workspace(stream, (size_t)a.ksplit * a.B * a.Cout * a.Lq * sizeof(float));
+    if (!a.ws) a.ksplit = 1;
+}
+
+// ---- step 6: the instance table (tile x chunk depth; launch_cfg adds interior / boundary, slot count and split-K)
+static int launch_instance(const ConvArgs& a, const TapsPlan& pl, const TileCfg& tc, int gy, int gz, hipStream_t stream) {
+    const int KC = pl.KC, ntiles = pl.ntiles;
+    const size_t lds = pl.lds;
     int rc = VFX_EINVAL;
     if (KC == 16) rc = launch_cfg<128, 128, 2, 2, 16>(a, ntiles, gy, gz, lds, stream);
 #define VFX_CASE(BM_, BL_, WGM_, WGL_)                                                          \
     else if (tc.BM == BM_ && tc.BL == BL_)                                                      \
         rc = KC == 8 ? launch_cfg<BM_, BL_, WGM_, WGL_, 8>(a, ntiles, gy, gz, lds, stream)      \
                      : launch_cfg<BM_, BL_, WGM_, WGL_, 4>(a, ntiles, gy, gz, lds, stream);
-    else if (waves8 && tc.BM == 128 && tc.BL == 128)
+    else if (pl.waves8 && tc.BM == 128 && tc.BL == 128)
         rc = KC == 8 ? launch_cfg<128, 128, 4, 2, 8>(a, ntiles, gy, gz, lds, stream)
                      : launch_cfg<128, 128, 4, 2, 4>(a, ntiles, gy, gz, lds, stream);
-    else if (waves8 && tc.BM == 64 && tc.BL == 256)
+    else if (pl.waves8 && tc.BM == 64 && tc.BL == 256)
         rc = KC == 8 ? launch_cfg<64, 256, 2, 4, 8>(a, ntiles, gy, gz, lds, stream)
                      : launch_cfg<64, 256, 2, 4, 4>(a, ntiles, gy, gz, lds, stream);
     VFX_CASE(128, 128, 2, 2)
@@ -1658,6 +1645,39 @@ static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, c
     VFX_CASE(64, 64, 2, 2)
     VFX_CASE(32, 128, 1, 4)
 #undef VFX_CASE
+    return rc;
+}
+
+// Every convolution of the C ABI below: the argument record, the newer kernels in turn, then conv_taps_kernel.
+static int launch_conv(const vfx_tensor* x, const float* w, const float* bias, const vfx_tensor* res,
+                       const vfx_tensor* y, int B, int Cin, int Cout, int Lin, int Lq, int Lout,
+                       int nphase, const PhaseSpec* phs, int q_shift, int q_mask, int o_rs, int o_cs,
+                       int pad_mode, const vfx_act* act, int in_mask, int out_mask, hipStream_t stream) {
+    ConvArgs a;
+    int rc = conv_args(a, x, w, bias, res, y, B, Cin, Cout, Lin, Lq, Lout, nphase, phs, q_shift, q_mask, o_rs, o_cs, pad_mode, act,
+                       in_mask, out_mask);
+    if (rc != VFX_OK) return rc;
+    int maxnt = 0;
+    for (int p = 0; p < nphase; ++p) maxnt = phs[p].ntaps > maxnt ? phs[p].ntaps : maxnt;
+    if (maxnt < 1 || maxnt > VFX_MAXT) return VFX_EINVAL;
+    rc = try_kernel_chain(a, x, nphase, phs, act, stream);
+    if (rc != VFX_ENOTSUP) return rc;
+
+    const TileCfg* tc = choose_tile(B, Cout, Lq, nphase);
+    if (!tc) return VFX_EINVAL;
+    TapsPlan pl;
+    // development switch: VFX_WAVES8=1 runs the two big tiles with 8 waves (wave tile 32x64)
+    static const bool waves8_env = VFX_DEV_ENV("VFX_WAVES8") && atoi(VFX_DEV_ENV("VFX_WAVES8")) != 0;
+    pl.waves8 = waves8_env && ((tc->BM == 128 && tc->BL == 128) || (tc->BM == 64 && tc->BL == 256));
+    rc = plan_layout(a, pl, x, nphase, phs, *tc, maxnt);
+    if (rc != VFX_OK) return rc;
+    a.tab = device_tables(pl.tb);
+    if (!a.tab) return VFX_EINVAL;
+    a.two_level = pl.KC == 4 && Cin >= 256;
+    set_last_tile(tc->BM, tc->BL, pl.KC);
+    plan_splitk(a, pl, *tc, nphase, phs[0].ooff, stream);
+    a.tpw = 1;  // multi-tile workgroups measured slower (register pressure), see the kernel comment
+    rc = launch_instance(a, pl, *tc, nphase * Cout / tc->BM, B * a.ksplit, stream);
     if (rc != VFX_OK || a.ksplit == 1) return rc;
     const long long total = (long long)B * Cout * Lq;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);

@@ -237,6 +237,6 @@ extern "C" int vfx_conv1d_f16(const vfx_tensor* x, const void* w_f16, const floa
                      : (a.res ? convh_kernel<false, true> : convh_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk, 1, B), dim3(convh::NTHR), 0, (hipStream_t)stream, a);
     VFX_LAUNCHED();
-    g_last_tile = convh::BM * 100000 + convh::BL * 100 + 32;
+    set_last_tile(convh::BM, convh::BL, TILE_CONVH);
     return vfx_last_error();
 }

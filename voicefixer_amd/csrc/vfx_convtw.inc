@@ -296,9 +296,7 @@ __global__ __launch_bounds__(256, 2) void convtw_kernel(const ConvArgs a) {
 
 template <int WGM, int WGP>
 static int launch_convtw(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((convtw_kernel<WGM, WGP>), grid, dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<convtw_kernel<WGM, WGP>>(grid, dim3(256), lds, s, a);
 }
 
 // vfx_convtr1d_f32 on convtw_kernel: w32 = vfx_act.w_wino4 of this entry point (packing.pack_wino32_tr).  VFX_ENOTSUP = not this launch.
@@ -312,9 +310,9 @@ static int try_launch_convtw(const vfx_tensor* x, const float* w_packed, const f
     // the first whole one, assumes s <= 32)
     if (Cin < 32 || Cout <= 0 || Cin % 32 != 0 || Cout % 64 != 0 || B <= 0 || B > 65535 || Lin < 1 || stride < 1 || stride > 32) return VFX_ENOTSUP;
     if (x->lstride != 1 || y->lstride != 1 || (bias && !vfx_aligned16(bias))) return VFX_ENOTSUP;
-    const long long lim = (1ll << 31) - (1ll << 20);
-    if (((long long)Cin * x->cstride + Lin) * 4 >= lim || ((long long)Cout * y->cstride + (long long)stride * Lin) * 4 >= lim) return VFX_ENOTSUP;
-    if (4ll * stride * (Cin >> 3) * Cout * 32 >= lim || (long long)stride * stride * Cout >= (1ll << 32)) return VFX_ENOTSUP;   // (tw_rdiv's range)
+    if (!offsets_fit31(((long long)Cin * x->cstride + Lin) * 4) || !offsets_fit31(((long long)Cout * y->cstride + (long long)stride * Lin) * 4))
+        return VFX_ENOTSUP;
+    if (!offsets_fit31(4ll * stride * (Cin >> 3) * Cout * 32) || (long long)stride * stride * Cout >= (1ll << 32)) return VFX_ENOTSUP;   // (tw_rdiv's range)
     const bool wide = Cout % 128 == 0;
     const int BT = wide ? 32 : 64;
     const int ntriples = (Lin + 1 + 2) / 3;
@@ -343,6 +341,6 @@ static int try_launch_convtw(const vfx_tensor* x, const float* w_packed, const f
     a.xcd_chunk = nwg >= 64 ? (int)((nwg + 7) / 8) : 0;
     const dim3 grid(a.xcd_chunk > 0 ? (unsigned)(8 * a.xcd_chunk) : (unsigned)nwg, 1, B);
     const size_t lds = (wide ? 4ull * 32 * 48 : 2ull * 4 * 16 * BT) * sizeof(float);   // staging buffers 2 x 4 x 16 x BT floats; epilogue: 4 waves x 6 KB (more, where BT = 32)
-    g_last_tile = (wide ? 128 : 64) * 100000 + 3 * BT * 100 + 83;   // 83: convtw_kernel (transposed, Winograd F(3,2))
+    set_last_tile(wide ? 128 : 64, 3 * BT, TILE_CONVTW);
     return wide ? launch_convtw<4, 1>(a, grid, lds, stream) : launch_convtw<2, 2>(a, grid, lds, stream);
 }

@@ -930,19 +930,7 @@ __global__ __launch_bounds__(256, FUSED ? 2 : 3) void convw_kernel(const ConvArg
 // ---- host side ------------------------------------------------------------------------------------------------
 template <int BM, int BL, int WGM, int WGL, int NT, int NXV, int FUSED>
 static int launch_w_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = convw_kernel<BM, BL, WGM, WGL, NT, NXV, FUSED>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<convw_kernel<BM, BL, WGM, WGL, NT, NXV, FUSED>>(grid, dim3(256), lds, s, a);
 }
 
 template <int BM, int BL, int WGM, int WGL, int NT, int FUSED>
@@ -973,19 +961,11 @@ static int convw_setup(ConvArgs& a, const vfx_tensor* x, int nphase, const Phase
     // the kernel evaluates leaky ReLU as max(v, slope * v): other slopes stay on the first-generation kernel
     if ((a.pre_act == VFX_PRE_LRELU || a.pre_act == VFX_PRE_AFFINE_LRELU) && !(a.pre_slope >= 0.f && a.pre_slope <= 1.f))
         return VFX_ENOTSUP;
-    int maxspan = 0;
-    bool all_segments = true;
     const int nt = phs[0].ntaps;
-    for (int p = 0; p < nphase; ++p) {
+    for (int p = 1; p < nphase; ++p)
         if (phs[p].ntaps != nt) return VFX_ENOTSUP;
-        int mn = phs[p].taps[0].off, mx = mn;
-        for (int t = 1; t < nt; ++t) {
-            mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-            mx = phs[p].taps[t].off > mx ? phs[p].taps[t].off : mx;
-        }
-        maxspan = mx - mn > maxspan ? mx - mn : maxspan;
-        all_segments &= !((long long)BL + (mx - mn) + 3 <= (long long)nt * (BL + 3));
-    }
+    bool all_segments;
+    const int maxspan = max_tap_span(nphase, phs, BL, &all_segments);
     // unaligned ("exact") origins everywhere: every tile is interior and staged with buffer loads.  Small spans of
     // an unfused launch stage exactly BL columns and produce BL - span outputs; wide dilations stage BL columns per tap.
     const bool shrink = bl_out_fixed == 0 && maxspan > 0 && maxspan <= 8;
@@ -996,36 +976,16 @@ static int convw_setup(ConvArgs& a, const vfx_tensor* x, int nphase, const Phase
         if (kcx < 8) return VFX_ENOTSUP;
         if (Cin % kcx != 0) continue;
         std::memset(&tb, 0, sizeof(tb));
-        int rc = fill_segments(a, tb, nphase, phs, BL, kcx, exact_layout);
-        if (rc) return rc;
+        fill_segments(a, tb, nphase, phs, BL, kcx, exact_layout);
         if (!exact_layout) {
-            // halo tiles: fill_segments aligned the origin down to a multiple of 4; re-base on the exact minimum tap
-            // offset (buffer loads need no alignment) so that the staged width is BL + span rounded up to 4
-            for (int p = 0; p < nphase; ++p) {
-                PhaseTab& T = tb.ph[p];
-                if (T.nseg != 1) continue;
-                int mn = phs[p].taps[0].off;
-                for (int t = 1; t < nt; ++t) mn = phs[p].taps[t].off < mn ? phs[p].taps[t].off : mn;
-                T.seg_org[0] = mn;
-                for (int t = 0; t < nt; ++t) T.tap_lds[t] = phs[p].taps[t].off - mn;
-            }
+            // fill_segments aligned the origins down to a multiple of 4; buffer loads need no alignment: re-base every phase on
+            // its exact tap offsets, so that the staged width is BL + span rounded up to 4 (per-tap segments: BL rounded up)
             a.segw = (BL + maxspan + 3) & ~3;
             for (int p = 0; p < nphase; ++p)
                 if (tb.ph[p].nseg != 1) a.segw = a.segw > ((BL + 3) & ~3) ? a.segw : ((BL + 3) & ~3);
+            for (int p = 0; p < nphase; ++p) fill_phase(tb.ph[p], phs[p], tb.ph[p].nseg == 1, true, kcx * a.segw);
         }
-        int maxseg = 0;
-        for (int p = 0; p < nphase; ++p) maxseg = tb.ph[p].nseg > maxseg ? tb.ph[p].nseg : maxseg;
-        if (!exact_layout) {
-            // per-tap segment offsets depend on the row pitch: recompute for the re-based pitch
-            for (int p = 0; p < nphase; ++p) {
-                PhaseTab& T = tb.ph[p];
-                if (T.nseg == 1) continue;
-                for (int t = 0; t < nt; ++t) {
-                    T.seg_org[t] = phs[p].taps[t].off;
-                    T.tap_lds[t] = t * kcx * a.segw;
-                }
-            }
-        }
+        const int maxseg = max_segments(tb, nphase);
         a.xs_floats = maxseg * kcx * a.segw;
         a.nxv = (int)(((long long)maxseg * kcx * (a.segw / 4) + 255) / 256);
         if (a.nxv <= VFX_W_MAXNXV && 2ull * a.xs_floats * sizeof(float) <= VFX_W_LDS_BUDGET) break;
@@ -1034,15 +994,10 @@ static int convw_setup(ConvArgs& a, const vfx_tensor* x, int nphase, const Phase
     a.bl_step = bl_out_fixed ? bl_out_fixed : (shrink ? BL - maxspan : BL);
     const int ntiles = (Lq + a.bl_step - 1) / a.bl_step;
     // interior check: every staged vector inside [-guard, Lin + guard)
-    int seg_lo = 0x7fffffff, seg_hi = -0x7fffffff;
-    for (int p = 0; p < nphase; ++p)
-        for (int sg = 0; sg < tb.ph[p].nseg; ++sg) {
-            seg_lo = tb.ph[p].seg_org[sg] < seg_lo ? tb.ph[p].seg_org[sg] : seg_lo;
-            seg_hi = tb.ph[p].seg_org[sg] > seg_hi ? tb.ph[p].seg_org[sg] : seg_hi;
-        }
+    const TapSpan seg = segment_range(tb, nphase);
     const long long g = x->guard;
-    if (-(long long)seg_lo + halo_extra > g) return VFX_ENOTSUP;
-    if ((long long)(ntiles - 1) * a.bl_step - halo_extra + seg_hi + a.segw > (long long)Lin + g) return VFX_ENOTSUP;
+    if (-(long long)seg.mn + halo_extra > g) return VFX_ENOTSUP;
+    if ((long long)(ntiles - 1) * a.bl_step - halo_extra + seg.mx + a.segw > (long long)Lin + g) return VFX_ENOTSUP;
     // the kernel takes the staging layout from phase 0: every phase must stage the same segments / tap columns
     for (int p = 1; p < nphase; ++p) {
         if (tb.ph[p].nseg != tb.ph[0].nseg) return VFX_ENOTSUP;
@@ -1117,11 +1072,10 @@ static void convw_stagger(ConvArgs& a, long long nwg, size_t lds, int waves_per_
 
 // convw_kernel addresses every row of one batch item with 32-bit BYTE offsets from a per-item buffer base
 static bool convw_offsets_fit(const ConvArgs& a) {
-    const long long lim = (1ll << 31) - (1ll << 20);
     const long long xin = ((long long)a.CinPad * a.x_cs + a.Lin + 2ll * a.x_guard) * 4;
     const long long yout = ((long long)a.Cout * a.y_cs + (long long)a.Lout * (a.y_ls > 0 ? a.y_ls : 1)) * 4;
     const long long rin = a.res ? ((long long)a.Cout * a.r_cs + a.Lout) * 4 : 0;
-    return xin < lim && yout < lim && rin < lim;
+    return offsets_fit31(xin) && offsets_fit31(yout) && offsets_fit31(rin);
 }
 
 // unfused launch on convw_kernel; VFX_ENOTSUP -> the caller runs conv_taps_kernel
@@ -1155,7 +1109,7 @@ static int try_launch_convw(ConvArgs a, const vfx_tensor* x, int nphase, const P
         grid = dim3(grid.x * nphase, gy, a.B);
     }
     convw_stagger(a, ntiles * (long long)gy * a.B, lds, 3);
-    g_last_tile = BM * 100000 + BL * 100 + 50 + a.kcx / 8;  // 51 / 52 / 54: convw_kernel, chunk depth 8 / 16 / 32
+    set_last_tile(BM, BL, TILE_CONVW + a.kcx / 8);
     if (BM == 128) {
         return nt == 3 ? launch_w_nxv<128, 128, 2, 2, 3, false>(a, grid, lds, stream)
                        : launch_w_nxv<128, 128, 2, 2, 2, false>(a, grid, lds, stream);
@@ -1208,7 +1162,7 @@ static int try_launch_convw_2d(ConvArgs a, const vfx_tensor* x, int P, const flo
     if ((long long)(ntiles - 1) * BL + (P - 1) + a.segw > (long long)a.Lin + g) return VFX_ENOTSUP;
     const size_t lds = (2ull * a.xs_floats + 2ull * a.Cin) * sizeof(float) + 64;
     const dim3 grid(convw_grid_x(a, ntiles), gy, a.B);
-    g_last_tile = BM * 100000 + BL * 100 + 59;  // 59: convw_kernel, 3x3 on a pitch map
+    set_last_tile(BM, BL, TILE_CONVW_2D);
     if (BM == 128 && BL == 64) return launch_w_one<128, 64, 2, 2, 9, 4, false>(a, grid, lds, stream);
     if (BM == 128) return launch_w_nxv<128, 128, 2, 2, 9, false>(a, grid, lds, stream);
     if (BM == 64) return launch_w_nxv<64, 128, 1, 4, 9, false>(a, grid, lds, stream);
@@ -1238,8 +1192,7 @@ static int resblock_convw(const vfx_tensor* x, const vfx_tensor* y, const float*
         !vfx_aligned16(w2_direct))
         return VFX_EALIGN;
     if (x->ptr == y->ptr) return VFX_EINVAL;  // tiles read their neighbours' input columns: not an in-place update
-    if (((long long)C * x->cstride + L + 2 * x->guard) * 4 >= (1ll << 31) - (1ll << 20) ||
-        ((long long)C * y->cstride + L) * 4 >= (1ll << 31) - (1ll << 20))
+    if (!offsets_fit31(((long long)C * x->cstride + L + 2 * x->guard) * 4) || !offsets_fit31(((long long)C * y->cstride + L) * 4))
         return VFX_ERANGE;  // 32-bit byte offsets within one batch item
     ConvArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1293,20 +1246,20 @@ static int resblock_convw(const vfx_tensor* x, const vfx_tensor* y, const float*
     const dim3 grid(tpw == 1 ? convw_grid_x(a, ntiles) : (unsigned)((ntiles + tpw - 1) / tpw), 1, B);
     if (tpw != 1) { a.xcd_chunk = 0; a.ntiles_l = ntiles; }
     convw_stagger(a, (long long)grid.x * B, lds, (C == 64 && BL == 128) || (C == 128 && BL == 64) ? 3 : 2);
-    g_last_tile = C * 100000 + BL * 100 + 60 + a.kcx / 8;  // 61 / 62 / 64: fused ResStack layer
     hipStream_t s = (hipStream_t)stream;
     if (w2_wino4) {
-        g_last_tile += 30;  // 9x: fused layer with the Winograd F(4,3) second half
+        set_last_tile(C, BL, TILE_FUSED_F43 + a.kcx / 8);
         return launch_w_nxv<64, 256, 1, 4, 3, 3>(a, grid, lds, s);
     }
     if (w2_wino && C == 64 && BL == 256) {
-        g_last_tile += 10;  // 7x: fused layer with the Winograd second half
+        set_last_tile(C, BL, TILE_FUSED_F23 + a.kcx / 8);
         return launch_w_nxv<64, 256, 1, 4, 3, 2>(a, grid, lds, s);
     }
     if (w2_wino && C == 128 && BL == 128) {
-        g_last_tile += 10;
+        set_last_tile(C, BL, TILE_FUSED_F23 + a.kcx / 8);
         return launch_w_nxv<128, 128, 2, 2, 3, 2>(a, grid, lds, s);
     }
+    set_last_tile(C, BL, TILE_FUSED + a.kcx / 8);
     if (C == 64) {
         return BL == 256 ? launch_w_nxv<64, 256, 1, 4, 3, 1>(a, grid, lds, s)
                          : launch_w_nxv<64, 128, 1, 4, 3, 1>(a, grid, lds, s);

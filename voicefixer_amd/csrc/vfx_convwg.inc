@@ -657,19 +657,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
 
 template <int WGM, int WGP, bool D1 = false, int XD = 2, bool PRE = true, int SPEC = 0>
 static int launch_wg4_xd(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = convwg4_kernel<WGM, WGP, D1, XD, PRE, SPEC>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<convwg4_kernel<WGM, WGP, D1, XD, PRE, SPEC>>(grid, dim3(256), lds, s, a);
 }
 
 template <int WGM, int WGP, bool D1 = false>
@@ -716,18 +704,15 @@ static int try_launch_convwg4(ConvArgs a, const vfx_tensor* x, int nphase, const
     // leaky ReLU is evaluated as max(v, slope * v): slopes outside [0, 1] take the direct kernels
     if (a.pre_act == VFX_PRE_LRELU && !(a.pre_slope >= 0.f && a.pre_slope <= 1.f)) return VFX_ENOTSUP;
     if (a.post_act == VFX_POST_LRELU && !(a.post_slope >= 0.f && a.post_slope <= 1.f)) return VFX_ENOTSUP;
-    if (a.q_shift != 31 || a.o_rs != 0 || a.o_cs != 1 || a.y_ls != 1 || a.Lq != a.Lin || a.Lq > a.Lout) return VFX_ENOTSUP;
+    if (!plain_output_map(a, nphase, phs[0].ooff) || a.y_ls != 1 || a.Lq != a.Lin) return VFX_ENOTSUP;
     if (a.res && a.r_ls != 1) return VFX_ENOTSUP;
     if (a.Cin % 32 != 0 || a.Cout % 64 != 0 || a.Cin != a.CinPad) return VFX_ENOTSUP;
     static const bool square = VFX_DEV_ENV("VFX_WINO4_SQUARE") && atoi(VFX_DEV_ENV("VFX_WINO4_SQUARE")) != 0;   // development: 64 x 64 tiles everywhere
     const bool wide = a.Cout % 128 == 0 && !square;
-    {
-        const long long lim = (1ll << 31) - (1ll << 20);
-        if (((long long)a.Cin * a.x_cs + a.Lin) * 4 >= lim || ((long long)a.Cout * a.y_cs + a.Lout) * 4 >= lim ||
-            (a.res && ((long long)a.Cout * a.r_cs + a.Lout) * 4 >= lim))
-            return VFX_ENOTSUP;
-        if (6ll * (a.CinPad >> 3) * a.Cout * 32 >= lim) return VFX_ENOTSUP;
-    }
+    if (!offsets_fit31(((long long)a.Cin * a.x_cs + a.Lin) * 4) || !offsets_fit31(((long long)a.Cout * a.y_cs + a.Lout) * 4) ||
+        (a.res && !offsets_fit31(((long long)a.Cout * a.r_cs + a.Lout) * 4)))
+        return VFX_ENOTSUP;
+    if (!offsets_fit31(6ll * (a.CinPad >> 3) * a.Cout * 32)) return VFX_ENOTSUP;   // (the transformed weights)
     const long long nquads = ((long long)a.Lin + 4 * d - 1) / (4 * d) * d;
     const int BQ = wide ? 32 : 64;
     const int ntiles = (int)((nquads + BQ - 1) / BQ);
@@ -748,7 +733,7 @@ static int try_launch_convwg4(ConvArgs a, const vfx_tensor* x, int nphase, const
         lds += (size_t)atoi(VFX_DEV_ENV("VFX_WG4_LDS_PAD_KB")) * 1024;
     dim3 grid(convw_grid_x(a, ntiles), gy, a.B);
     convwg_fold_blocks(a, grid, gy);
-    g_last_tile = (wide ? 128 : 64) * 100000 + 4 * BQ * 100 + 80;   // 80: convwg4_kernel (Winograd F(4,3))
+    set_last_tile(wide ? 128 : 64, 4 * BQ, TILE_WG4);
     // dilation 1 (the residual-carrying second convolution of a ResStack layer): quads as aligned 16-byte vectors
     static const bool d1_off = VFX_DEV_ENV("VFX_WINO4_D1") && atoi(VFX_DEV_ENV("VFX_WINO4_D1")) == 0;   // development
     const bool vec_ok = ((a.x_cs | a.x_bs | a.y_cs | a.y_bs) & 3) == 0 && vfx_aligned16(a.x) && vfx_aligned16(a.y) &&
@@ -759,7 +744,7 @@ static int try_launch_convwg4(ConvArgs a, const vfx_tensor* x, int nphase, const
     if (wide && wg4x && (wg4x != 2 || d1vec || a.Cout == 128)) {
         const int rc = try_launch_convwg4x(a, nquads, d1vec, stream);
         if (rc != VFX_ENOTSUP) {
-            if (rc == VFX_OK) g_last_tile = 128 * 100000 + 256 * 100 + 82;   // 82: convwg4x_kernel (32 x 64 x 6 wave tile)
+            if (rc == VFX_OK) set_last_tile(128, 256, TILE_WG4X);
             return rc;
         }
     }
@@ -767,7 +752,7 @@ static int try_launch_convwg4(ConvArgs a, const vfx_tensor* x, int nphase, const
         // the two launches of a ResStack layer, when long enough: persistent workgroups, pipeline across tiles (vfx_convwg4p.inc)
         const int rc = try_launch_convwg4p(a, ntiles, gy, wide, d1vec, stream);
         if (rc != VFX_ENOTSUP) {
-            if (rc == VFX_OK) g_last_tile = (wide ? 128 : 64) * 100000 + 4 * BQ * 100 + 81;   // 81: convwg4p_kernel
+            if (rc == VFX_OK) set_last_tile(wide ? 128 : 64, 4 * BQ, TILE_WG4P);
             return rc;
         }
     }

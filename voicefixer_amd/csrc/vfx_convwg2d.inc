@@ -374,19 +374,7 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void convwg4s_kernel(const ConvAr
 
 template <int WGM, int WGP, int KC, bool AFF, bool TWO>
 static int launch_wg4s_aff(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;   // bit d: the attribute is set on device d (one process may drive several)
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = convwg4s_kernel<WGM, WGP, KC, AFF, TWO>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<convwg4s_kernel<WGM, WGP, KC, AFF, TWO>>(grid, dim3(256), lds, s, a);
 }
 
 template <int WGM, int WGP, int KC>
@@ -410,19 +398,16 @@ static int try_launch_convwg4s_2d(ConvArgs a, const vfx_tensor* x, int P, const 
     if (a.pre_act != VFX_PRE_NONE && a.pre_act != VFX_PRE_AFFINE_LRELU) return VFX_ENOTSUP;
     if (a.pre_act == VFX_PRE_AFFINE_LRELU && !(a.pre_slope >= 0.f && a.pre_slope <= 1.f)) return VFX_ENOTSUP;   // lrelu = max(v, slope v)
     if (a.post_act == VFX_POST_LRELU && !(a.post_slope >= 0.f && a.post_slope <= 1.f)) return VFX_ENOTSUP;
-    if (a.q_shift != 31 || a.o_rs != 0 || a.o_cs != 1 || a.y_ls != 1 || a.Lq != a.Lin || a.Lq > a.Lout) return VFX_ENOTSUP;
+    if (!plain_output_map(a, 1, 0) || a.y_ls != 1 || a.Lq != a.Lin) return VFX_ENOTSUP;   // (one phase at offset 0: the caller's 3x3)
     if (a.res && a.r_ls != 1) return VFX_ENOTSUP;
     if (a.Cout % 32 != 0 || a.Cin != a.CinPad) return VFX_ENOTSUP;
     const bool narrow = a.Cout % 64 != 0;         // 32 channels x 128 quads, 8-channel chunks (UNet level 0)
     const int BQ = narrow ? 128 : 64, kc = narrow ? 8 : 16;
     if (a.Cin % (2 * kc) != 0 || P > BQ) return VFX_ENOTSUP;
-    {
-        const long long lim = (1ll << 31) - (1ll << 20);
-        if (((long long)a.Cin * a.x_cs + a.Lin) * 4 >= lim || ((long long)a.Cout * a.y_cs + a.Lout) * 4 >= lim ||
-            (a.res && ((long long)a.Cout * a.r_cs + a.Lout) * 4 >= lim))
-            return VFX_ENOTSUP;
-        if (18ll * (a.CinPad >> 3) * a.Cout * 32 >= lim) return VFX_ENOTSUP;
-    }
+    if (!offsets_fit31(((long long)a.Cin * a.x_cs + a.Lin) * 4) || !offsets_fit31(((long long)a.Cout * a.y_cs + a.Lout) * 4) ||
+        (a.res && !offsets_fit31(((long long)a.Cout * a.r_cs + a.Lout) * 4)))
+        return VFX_ENOTSUP;
+    if (!offsets_fit31(18ll * (a.CinPad >> 3) * a.Cout * 32)) return VFX_ENOTSUP;   // (the transformed weights)
     const int d = P;
     const long long nquads = ((long long)a.Lin + 4 * d - 1) / (4 * d) * d;
     const int ntiles = (int)((nquads + BQ - 1) / BQ);
@@ -437,6 +422,6 @@ static int try_launch_convwg4s_2d(ConvArgs a, const vfx_tensor* x, int P, const 
     const size_t lds = (2ull * 6 * kc * (BQ + 2) + 2ull * a.Cin) * sizeof(float);
     dim3 grid(convw_grid_x(a, ntiles), gy, a.B);
     convwg_fold_blocks(a, grid, gy);
-    g_last_tile = (narrow ? 32 : 64) * 100000 + (4 * BQ % 1000) * 100 + 88;   // 88: convwg4s_kernel (3x3, shared staging)
+    set_last_tile(narrow ? 32 : 64, 4 * BQ % 1000, TILE_WG4S);
     return narrow ? launch_wg4s_one<1, 4, 8>(a, grid, lds, stream) : launch_wg4s_one<2, 2, 16>(a, grid, lds, stream);
 }

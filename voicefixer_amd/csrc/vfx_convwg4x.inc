@@ -434,19 +434,7 @@ __global__ __launch_bounds__(256, 1) void convwg4x_kernel(const ConvArgs a) {
 
 template <bool D1, bool PRE, int SPEC>
 static int launch_wg4x(const ConvArgs& a, int nwg, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    auto kern = convwg4x_kernel<D1, PRE, SPEC>;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    return vfx_launch<convwg4x_kernel<D1, PRE, SPEC>>(dim3(nwg), dim3(256), lds, s, a);
 }
 
 // The re-blocked persistent form of a wide (Cout % 128 == 0) convwg4_kernel launch; `a`, d1vec as try_launch_convwg4 prepared them, the tile

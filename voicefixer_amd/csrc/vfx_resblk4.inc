@@ -469,7 +469,7 @@ static bool resblk4_args_ok(const vfx_tensor* x, const vfx_tensor* y, const vfx_
              y->lstride == 1 && ((x->cstride | x->bstride | y->cstride | y->bstride) & 3) == 0 &&
              (!bias1 || vfx_aligned16(bias1)) && (!bias2 || vfx_aligned16(bias2)) && slope >= 0.f && slope <= 1.f &&
              !(post_act == VFX_POST_LRELU && !(post_slope >= 0.f && post_slope <= 1.f)) &&
-             ((long long)C * x->cstride + L) * 4 < (1ll << 31) - (1ll << 20) && ((long long)C * y->cstride + L) * 4 < (1ll << 31) - (1ll << 20);
+             offsets_fit31(((long long)C * x->cstride + L) * 4) && offsets_fit31(((long long)C * y->cstride + L) * 4);
     }
     return ok;
 }
@@ -516,19 +516,8 @@ static int resblk4_launch(const vfx_tensor* x, const vfx_tensor* y, const vfx_re
     const int ntiles = (L + a.bl_step - 1) / a.bl_step;
     const size_t lds = (size_t)C * a.yp * sizeof(float);   // 66 560 bytes (the staging buffers, 49 152, alias it)
     const dim3 grid(convw_grid_x(a, ntiles), 1, B);
-    static unsigned long long attr_set = 0;
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(resblk4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    g_last_tile = C * 100000 + 256 * 100 + 96;    // 96: fused ResStack layer, both halves Winograd F(4,3)
-    hipLaunchKernelGGL(resblk4_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    set_last_tile(C, 256, TILE_RESBLK4);
+    return vfx_launch<resblk4_kernel>(grid, dim3(256), lds, (hipStream_t)stream, a);
 }
 
 // vfx_resblock_f32 (include/vfx_hip.h): one ResStack layer, fused.  With both F(4,3) transforms offered, C = 64, a dilation

@@ -45,17 +45,6 @@ extern "C" int vfx_resblock_wino4_f32(const vfx_tensor* x, const vfx_tensor* y, 
     if (ntiles * G >= (1 << 20)) return VFX_ENOTSUP;   // fast_div's range
     const size_t lds = (size_t)C * a.yp * sizeof(float);   // 66 560 bytes (the staging buffers, 49 152, alias it)
     const dim3 grid(convw_grid_x(a, (int)ntiles), 1, B);
-    static unsigned long long attr_set = 0;
-    int attr_dev = 0;
-    if (hipGetDevice(&attr_dev) != hipSuccess) attr_dev = 0;
-    if (!((attr_set >> (attr_dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(resblk4s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set |= 1ull << (attr_dev & 63);
-    }
-    g_last_tile = C * 100000 + 256 * 100 + 97;    // 97: fused ResStack layer on the strip tile
-    hipLaunchKernelGGL(resblk4s_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
-    VFX_LAUNCHED();
-    return vfx_last_error();
+    set_last_tile(C, 256, TILE_RESBLK4S);
+    return vfx_launch<resblk4s_kernel>(grid, dim3(256), lds, (hipStream_t)stream, a);
 }

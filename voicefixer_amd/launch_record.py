@@ -10,7 +10,7 @@ from . import ops, _lib
 NAMES = ("conv1d", "resblock", "resblock_wino4", "convtr1d", "conv2d", "convtr2d_3x3s2")
 PAD_NAMES = {_lib.PAD_ZERO: "zero", _lib.PAD_REFLECT: "reflect"}
 FAMILIES = {51: "convw", 52: "convw", 54: "convw", 59: "convw 3x3", 61: "fused", 62: "fused", 64: "fused", 71: "fused+F23",
-            72: "fused+F23", 74: "fused+F23", 91: "fused+F43", 92: "fused+F43", 94: "fused+F43", 96: "fused F43+F43",
+            72: "fused+F23", 74: "fused+F23", 91: "fused+F43", 92: "fused+F43", 94: "fused+F43", 96: "fused F43+F43", 97: "fused F43+F43 strip",
             80: "convwg4", 81: "convwg4p", 82: "convwg4x", 83: "convtw", 88: "convwg4s", 16: "x3", 32: "convh"}
 
 
