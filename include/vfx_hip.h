@@ -507,6 +507,38 @@ int vfx_loudness_report_groups_f32(const float* x, int64_t x_stride, const int32
                                    const double* mpow, int S, int hop, int lookback, const float* bank, int J, int R, int c,
                                    double* report, void* ws, size_t ws_bytes, vfx_stream_t stream);
 
+/* ---- look-ahead peak limiter behind the loudness measurement ------------------------------------------------- */
+
+/* Bytes of the WHOLE workspace of vfx_loudness_limit_f32 (0 on bad arguments): the workspace of vfx_loudness_groups_f32 and, behind
+ * it, 4 bytes per sample of the batch (the required gain) and a few values per row and per tile of 1024 samples. */
+size_t vfx_loudness_limit_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J);
+
+/* Loudness normalisation with a look-ahead limiter in place of the static ceiling: the arguments of vfx_loudness_groups_f32
+ * (G = 0 with NULL group_start and weight: every row is its own programme), then H, the look-ahead in samples (1..4096),
+ * true_peak (1: the ceiling is a true-peak one; 0: a sample-peak one, nothing is oversampled, bank / J / R / c are checked but
+ * not used) and result, device float64[G or B][8].  Per programme, with L, P, TP as vfx_loudness_groups_f32 measures them (the
+ * same bits; TP = P when true_peak = 0 or R = 1), gL = 10^((target - L)/20) (1 when L = -inf) and Cl = 10^(ceiling_db/20):
+ *   bound = Cl / TP < gL.  Not bound: out = (float)gL * x, the bits of vfx_loudness_groups_f32.
+ *   bound: e[n] = max(|x[n]|, the R interpolated values in (n - 1, n]) (those behind the last sample go to n - 1), the
+ *   maximum over the programme's rows;  c[n] = min(1, Cl / (gL e[n]));  m[n] = min c[j], |j - n| <= H inside the row;
+ *   g[n] = 1 - sum_{|k| <= H} w[k] (1 - m[clamp(n + k)]),  w[k] = (1 + cos(pi k / (H + 1))) / (2 H + 2), summed in fp32 in
+ *   ascending k;  v = ((float)gL * g[n]) * x;  TPv = the true peak of v (its sample peak when nothing is oversampled);
+ *   t = min(1, Cl / TPv);  out = (float)t * v.
+ * result = {L, gL, P, TP, bound (0 / 1), min g, t, TPv * t}; not bound: {L, gL, P, TP, 0, 1, 1, (float)gL * TP}.
+ * out may be x itself (the same pointer and stride); any other overlap of the two batches is VFX_EINVAL.  A row gives the
+ * same bits alone and in any batch.  Launches: those of vfx_loudness_groups_f32 measuring only, then 6 at R > 1 (row
+ * parameters, envelope, limit, true peak of the limited rows, fold, trim) or 5 (R = 1 or true_peak = 0) -- the same number
+ * whatever B and the lengths; no host synchronisation.  ws: >= vfx_loudness_limit_workspace_bytes(B, n_max, hop, S, R, J)
+ * bytes (with R = 1 where true_peak = 0, if the smaller size is wanted), 16-byte aligned.
+ * VFX_EINVAL on bad arguments (nothing launched): everything vfx_loudness_groups_f32 rejects (apart from G = 0 with both
+ * pointers NULL), G or one pointer without the others, H outside [1, 4096], true_peak not 0 or 1, a NaN target, NULL out,
+ * overlapping x and out, ws too small. */
+int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                           const int32_t* group_start, const double* weight, int G, const double* coef, const double* mpow,
+                           int S, int hop, int lookback, double target, double ceiling_db, const float* bank, int J, int R,
+                           int c, float* out, int64_t out_stride, int H, int true_peak, double* result, void* ws,
+                           size_t ws_bytes, vfx_stream_t stream);
+
 /* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
 
 /* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into

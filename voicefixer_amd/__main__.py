@@ -26,6 +26,9 @@ Differences, all deliberate:
     limited by the sample-peak ceiling ``--peak-ceiling DBFS`` (default -1); file and folder mode, every ``--mode``;
     ``--true-peak`` with it: the ceiling is read as dBTP and the TRUE peak, measured between the samples, limits the gain
     (alone it is an argument error; forwarded to every ``--gpus`` rank with the rest of the command line);
+    ``--limiter`` with it: where the target would push a file past the ceiling, a look-ahead peak limiter
+    (``--limiter-lookahead-ms MS``, 0.1..10, default 3) dips the gain around the peaks instead of lowering the whole file,
+    so a file with one click still reaches the target (both are an argument error without ``--loudness``);
   * ``--channels {mix,first,all}`` (extension; file and folder mode, forwarded to every ``--gpus`` rank): what becomes of an
     input with several channels -- ``mix`` (default): their average, as the reference's ``librosa.load``; ``first``: the first
     channel; ``all``: every channel is restored and the output has the input's channel count; ``--loudness`` is then ONE
@@ -80,14 +83,16 @@ def mode_outfile(outfile, mode, append_mode):
 
 
 def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
-              resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None):
+              resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None, limiter=False,
+              limiter_lookahead_ms=3.0):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
     start = time.time()
     voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, output_sample_rate=output_sample_rate,
                        resample_on_device=resample_on_device, loudness=loudness, peak_ceiling=peak_ceiling, true_peak=true_peak,
-                       channels=channels)
+                       channels=channels,
+                       **({"limiter": True, "limiter_lookahead_ms": limiter_lookahead_ms} if limiter else {}))
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 
@@ -98,6 +103,12 @@ class _Parser(argparse.ArgumentParser):
         ns = super().parse_args(args, namespace)
         if ns.true_peak and ns.loudness is None:
             self.error("--true-peak needs --loudness: it turns the ceiling of the loudness normalisation into a true-peak one")
+        if ns.limiter and ns.loudness is None:
+            self.error("--limiter needs --loudness: it replaces the static ceiling of the loudness normalisation")
+        if ns.limiter_lookahead_ms is not None and not ns.limiter:
+            self.error("--limiter-lookahead-ms needs --limiter (and --loudness)")
+        if ns.limiter_lookahead_ms is None:
+            ns.limiter_lookahead_ms = 3.0
         return ns
 
 
@@ -144,6 +155,11 @@ def build_parser():
     parser.add_argument("--true-peak", default=False, action="store_true",
                         help="(extension) with --loudness: read --peak-ceiling as dBTP and limit the gain by the TRUE peak, measured "
                              "on the device between the samples (EBU R 128's ceiling)")
+    parser.add_argument("--limiter", default=False, action="store_true",
+                        help="(extension) with --loudness: a look-ahead peak limiter in place of the static ceiling -- the gain "
+                             "dips around the peaks only, so a file with a click or plosive still reaches the target")
+    parser.add_argument("--limiter-lookahead-ms", type=_lookahead_ms, default=None, metavar="MS",
+                        help="(extension) with --limiter: its look-ahead in ms, in [0.1, 10] (default 3)")
     parser.add_argument("--channels", choices=["mix", "first", "all"], default=None,
                         help="(extension) inputs of several channels: mix (default): restore their average; first: restore the "
                              "first channel; all: restore every channel and write the input's channel count (with --loudness: "
@@ -170,6 +186,14 @@ def _dbfs(text):
     from . import loudness
     try:
         return loudness.check_ceiling(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _lookahead_ms(text):
+    from . import loudness
+    try:
+        return loudness.check_limiter(True, float(text))[1]
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -279,7 +303,8 @@ def main(argv=None):
         for m in modes:
             writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
                       output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device,
-                      loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak, channels=args.channels)
+                      loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak, channels=args.channels,
+                      limiter=args.limiter, limiter_lookahead_ms=args.limiter_lookahead_ms)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -296,7 +321,9 @@ def main(argv=None):
                                           seed=args.seed, output_sample_rate=args.output_sample_rate,
                                           resample_on_device=args.resample_on_device, loudness=args.loudness,
                                           peak_ceiling=args.peak_ceiling, **({"true_peak": True} if args.true_peak else {}),
-                                          **({"channels": args.channels} if args.channels is not None else {}))
+                                          **({"channels": args.channels} if args.channels is not None else {}),
+                                          **({"limiter": True, "limiter_lookahead_ms": args.limiter_lookahead_ms}
+                                             if args.limiter else {}))
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

@@ -272,6 +272,35 @@ def apply_loudness_groups(full, lens, groups, rate, target, peak_ceiling=-1.0, t
     return out, res
 
 
+def apply_limiter(full, lens, rate, target, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, groups=None,
+                  channel_weights=None):
+    """``apply_loudness`` / ``apply_loudness_groups`` with the look-ahead peak limiter in place of the static ceiling
+    (ops.loudness_limit; loudness.py): rows that the target would push past the ceiling get a gain curve that looks
+    ``lookahead_ms`` ahead, one curve per programme of ``groups`` adjacent channels.  Returns (rows, device float64 (G or B, 8)
+    of {L before, gL, sample peak, true peak, bound, min g, trim, peak after})."""
+    from . import loudness, ops
+    target, peak_ceiling = loudness.check_target(target), loudness.check_ceiling(peak_ceiling)
+    true_peak = loudness.check_true_peak(true_peak)
+    if target is None:
+        raise ValueError("limiter=True needs a loudness target")
+    loudness.limiter_window(rate, lookahead_ms)
+    x = full if full.stride(-1) == 1 else full.contiguous()
+    out = torch.empty_like(x)
+    if groups is not None:
+        weights = None if channel_weights is None else [w for g in groups for w in loudness.channel_weights(g, channel_weights)]
+        res = ops.loudness_limit(x, [int(n) for n in lens], rate, target, peak_ceiling, true_peak, lookahead_ms, out=out,
+                                 groups=groups, weights=weights)
+    else:
+        n_rows = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(x.device, non_blocking=True)
+        res = ops.loudness_limit(x, n_rows, rate, target, peak_ceiling, true_peak, lookahead_ms, out=out)
+    return out, res
+
+
+def _check_limiter(limiter, lookahead_ms):
+    from . import loudness
+    return loudness.check_limiter(limiter, lookahead_ms)[0]
+
+
 def _check_channels(channels):
     from . import loudness
     return loudness.check_channels(channels)
@@ -282,14 +311,20 @@ class _Output:
     and channel weights, and mode 2's seed.  Built ONCE per public call from its keywords -- the checks are made here, before
     anything touches the device -- and handed down as it is.  ``kwargs()`` is the one place that knows which keywords a
     ``restore_batches`` call is given, ``finish()`` the one tail of the device stage."""
-    __slots__ = ("rate_out", "loudness", "peak_ceiling", "true_peak", "channel_weights", "seed")
+    __slots__ = ("rate_out", "loudness", "peak_ceiling", "true_peak", "channel_weights", "seed", "limiter",
+                 "limiter_lookahead_ms")
 
     def __init__(self, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None,
-                 mode=0, seed=None):
+                 mode=0, seed=None, limiter=False, limiter_lookahead_ms=3.0):
         from . import loudness as ld
         self.rate_out = _output_rate(output_sample_rate)
         self.true_peak = ld.check_true_peak(true_peak)
         self.loudness, self.peak_ceiling = ld.check_target(loudness), ld.check_ceiling(peak_ceiling)
+        self.limiter, self.limiter_lookahead_ms = ld.check_limiter(limiter, limiter_lookahead_ms)
+        if self.limiter:
+            if self.loudness is None:
+                raise ValueError("limiter=True needs a loudness target (loudness=...)")
+            ld.limiter_window(self.rate_out, self.limiter_lookahead_ms)
         if channel_weights is not None:
             if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
                     or not 1 <= len(channel_weights) <= ld.MAX_CHANNELS:
@@ -316,6 +351,8 @@ class _Output:
                 kw.update(true_peak=True)
             if self.channel_weights is not None:
                 kw["channel_weights"] = self.channel_weights
+            if self.limiter:
+                kw.update(limiter=True, limiter_lookahead_ms=self.limiter_lookahead_ms)
         return kw
 
     def finish(self, full, lens, groups=None):
@@ -325,7 +362,10 @@ class _Output:
         if self.rate_out != 44100:
             full, lens = convert_output(full, lens, self.rate_out)
         res = None
-        if self.loudness is not None and groups is not None:
+        if self.limiter:
+            full, res = apply_limiter(full, lens, self.rate_out, self.loudness, self.peak_ceiling, self.true_peak,
+                                      self.limiter_lookahead_ms, groups, self.channel_weights)
+        elif self.loudness is not None and groups is not None:
             full, res = apply_loudness_groups(full, lens, groups, self.rate_out, self.loudness, self.peak_ceiling,
                                               self.true_peak, self.channel_weights)
         elif self.loudness is not None:
@@ -701,7 +741,7 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
                       output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
-                      channel_weights=None):
+                      channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
         ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
@@ -716,6 +756,11 @@ class VoiceFixer(nn.Module):
         ``peak_ceiling`` (dBFS in [-20, 0]): one fp32 gain for the file (``apply_loudness``).  None (default): unchanged.
         ``true_peak=True`` (extension): ``peak_ceiling`` is read as dBTP, the gain is limited by the file's TRUE peak at the
         output rate (measured on the device between the samples: loudness.py, EBU R 128's ceiling).
+        ``limiter=True`` (extension; needs ``loudness``): where the target would push the file past ``peak_ceiling``, a
+        look-ahead peak limiter takes the place of the one static gain (``apply_limiter``; loudness.py): the gain dips
+        around the peaks only, ``limiter_lookahead_ms`` (0.1..10, default 3) ahead of them, and the rest of the file reaches
+        the target.  The ceiling is a true-peak one with ``true_peak=True``, else a sample-peak one; with ``channels="all"``
+        the gain curve is one per file.  A file the ceiling does not bind is written exactly as without the limiter.
         ``channels="all"`` (extension): ``wav_10k`` is (C, N), 1 <= C <= 8, and (C, N') comes back: the model is mono, so
         every channel goes through the path as ``restore_inmem(wav_10k[c])`` does -- the same segment cuts, mode-1 cut, seed,
         rate conversions and peak rule per channel -- with the same segment of all channels in ONE batch; ``loudness`` is
@@ -725,7 +770,8 @@ class VoiceFixer(nn.Module):
         as one.  None (default): a 2-D input raises ValueError (it used to be misread as one long row)."""
         self._check_mode(mode, seed)
         rate_in = _check_rate(sample_rate)
-        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
+                      limiter_lookahead_ms)
         wav, multi = _as_programme(wav_10k, _check_channels(channels), "restore_inmem")     # (C, n); C = 1 unless channels="all"
         C = wav.shape[0]
         job.check_channel_counts([C])
@@ -867,7 +913,8 @@ class VoiceFixer(nn.Module):
 
     @torch.no_grad()
     def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
-                        loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None):
+                        loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None, limiter=False,
+                        limiter_lookahead_ms=3.0):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -885,7 +932,8 @@ class VoiceFixer(nn.Module):
         ``loudness`` / ``peak_ceiling``: every row is normalised on the device (restore_inmem) before it crosses, and the
         generator yields ``(tag, out_host, lens_out, loud_host)``, ``loud_host`` a pinned float64 (B, 3) of {LUFS before,
         gain, sample peak} per row, copied with the batch.  ``true_peak=True``: the ceiling is a true-peak one (restore_inmem)
-        and ``loud_host`` is (B, 4): {LUFS before, gain, sample peak, true peak}.
+        and ``loud_host`` is (B, 4): {LUFS before, gain, sample peak, true peak}.  ``limiter=True`` (restore_inmem): ``loud_host``
+        is (B, 8): {LUFS before, gL, sample peak, true peak, bound, min g, trim, peak after} (loudness.py).
         Multichannel files: an item may carry a 6th field, ``groups`` (the 5th may then be None): one channel count (1..8) per
         tag; the channels of a file are adjacent rows of one length and rate, ``tag`` has one entry per FILE.  Every row goes
         through the path on its own; ``loudness`` is then ONE linked gain per file (``apply_loudness_groups``, weights
@@ -895,7 +943,8 @@ class VoiceFixer(nn.Module):
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
-        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
+                      limiter_lookahead_ms)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -956,7 +1005,7 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
                       sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False,
-                      channels=None, channel_weights=None):
+                      channels=None, channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -972,15 +1021,16 @@ class VoiceFixer(nn.Module):
         every file is restored as ``restore_inmem(mode=2, seed=seed)`` restores it.
         ``sample_rate`` (extension): the rate of the inputs, one int or a list with one rate per wav; rows are staged at
         their own rates and converted on the device (one launch per distinct rate pair and batch), the batches are
-        planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``, ``true_peak``: as
-        ``restore_inmem`` (each file is measured on its own row, whatever else its batch holds).
+        planned by the converted lengths.  ``output_sample_rate``, ``loudness``, ``peak_ceiling``, ``true_peak``,
+        ``limiter``, ``limiter_lookahead_ms``: as ``restore_inmem`` (each file is measured on its own row, whatever else its batch holds).
         ``channels="all"`` (extension): items may be (N,) or (C, N), results are (C, N').  The channels of a file are adjacent
         rows of one batch: the planning is by file, a file weighs C rows (ValueError when ``batch_size`` is smaller than the
         largest C), and ``loudness`` is one linked gain per file (``restore_inmem``; ``channel_weights`` then applies to
         every file and all must have that many channels).  "mix" / "first": (C, N) items are averaged / cut to their first
         channel first.  None (default): as before."""
         self._check_mode(mode, seed)
-        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
+                      limiter_lookahead_ms)
         multi = _check_channels(channels) == "all"
         progs = [_as_programme(w, channels, "restore_batch")[0] for w in wavs]     # (C_i, N_i); C_i = 1 unless channels="all"
         rates = _row_rates(sample_rate, len(progs))
@@ -1025,7 +1075,7 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_stream(self, wav, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=8, mode=0,
                        your_vocoder_func=None, on_chunk=None, sample_rate=44100, output_sample_rate=None, loudness=None,
-                       peak_ceiling=-1.0, true_peak=False):
+                       peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0):
         """Long-form restoration with overlap-add (BASELINE config 5; NOT in the reference, whose 30 s segments
         are hard-cut -- ``restore_inmem`` keeps that behaviour): chunks of ``chunk_seconds`` every
         ``chunk_seconds - overlap_seconds``, each restored independently (equal-length chunks are batched),
@@ -1039,11 +1089,12 @@ class VoiceFixer(nn.Module):
         ``sample_rate`` (extension): the rate of ``wav``; another rate than 44.1 kHz is converted once, up front, on the
         device, and the chunks are cut from the converted waveform.  ``output_sample_rate`` other than 44.1 kHz raises
         NotImplementedError: the ``on_chunk`` stretches would need the converter's filter state across chunk boundaries; so
-        does ``loudness``, and ``true_peak=True`` with it: the stretches leave before a whole-file measurement exists."""
+        does ``loudness``, and ``true_peak=True`` or ``limiter=True`` with it: the stretches leave before a whole-file measurement
+        exists."""
         _check_stream_mode(mode, "restore_stream")
         rate_in = _check_rate(sample_rate)
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak)
-        if job.loudness is not None or job.true_peak:
+        if job.loudness is not None or job.true_peak or _check_limiter(limiter, limiter_lookahead_ms):
             raise NotImplementedError("restore_stream: loudness normalisation is not built -- the on_chunk stretches leave before "
                                       "the whole file has been measured; use restore_inmem or restore_folder")
         if job.rate_out != 44100:
@@ -1091,14 +1142,18 @@ class VoiceFixer(nn.Module):
         return out[:, :n_out]
 
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
-                    sample_rate=44100, output_sample_rate=None):
+                    sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
         returns for the concatenated blocks (converted to 44.1 kHz as a whole) with the same ``chunk_seconds``,
         ``overlap_seconds``, ``batch_size`` and ``mode`` -- bit for bit at ``batch_size=1`` -- converted as a whole to the
         output rate.  Modes 0 and 1; ``mode=2`` raises NotImplementedError.  The arguments are checked here, before the
-        device is touched."""
+        device is touched.  ``limiter=True`` raises NotImplementedError, as ``restore_stream`` does: a session
+        never sees the whole file."""
+        if _check_limiter(limiter, limiter_lookahead_ms):
+            raise NotImplementedError("open_stream: the limiter is not built -- it follows a whole-file loudness measurement; use "
+                                      "restore_inmem or restore_folder")
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
                               output_sample_rate)
 
@@ -1161,7 +1216,8 @@ class VoiceFixer(nn.Module):
     def restore_folder(self, infolder, outfolder, mode=0, batch_size=32, io_threads=None, your_vocoder_func=None,
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
                        skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False, loudness=None,
-                       peak_ceiling=-1.0, true_peak=False, channels=None, channel_weights=None):
+                       peak_ceiling=-1.0, true_peak=False, channels=None, channel_weights=None, limiter=False,
+                       limiter_lookahead_ms=3.0):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -1199,7 +1255,9 @@ class VoiceFixer(nn.Module):
         ``loudness`` / ``peak_ceiling``: every output is normalised on the device (restore_inmem) before it is written;
         ``stats["loudness"]`` lists ``(output name, LUFS before, gain in dB)`` of the files written.  ``true_peak=True``:
         the ceiling is a true-peak one (restore_inmem) and ``stats["true_peak"]`` lists ``(output name, dBTP before, dBTP
-        after)``.
+        after)``.  ``limiter=True`` (restore_inmem): ``stats["limiter"]`` lists ``(output name, largest gain reduction in
+        dB, trim in dB, peak after in dB)`` per output -- ``(name, 0.0, 0.0, peak after)`` for a file the ceiling did not bind --
+        and the gain in ``stats["loudness"]`` is gL times the trim.
         ``channels`` (extension): None or "mix": files of several channels are averaged to one (the reference's
         ``librosa.load``); "first": their first channel is restored; "all": EVERY channel is restored and the output is
         written with the input's channel count (1..8; mixed counts in one folder are fine).  The count comes from the header
@@ -1213,7 +1271,8 @@ class VoiceFixer(nn.Module):
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
-        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
+                      limiter_lookahead_ms)
         rate_out = job.rate_out
         channels = _check_channels(channels)
         multi = channels == "all"
@@ -1325,6 +1384,7 @@ class VoiceFixer(nn.Module):
         written, skipped, done = [], [], []
         loud_rows = {}         # index -> (LUFS before, gain in dB)
         tp_rows = {}           # index -> (dBTP before, dBTP after)
+        lim_rows = {}          # index -> (largest gain reduction in dB, trim in dB, peak after in dB)
         with ThreadPoolExecutor(max_workers=io_threads) as pool:
             scanned = list(pool.map(scan, range(len(files))))
             # every rank must deal from the SAME list: inside an initialised process group of this world size the scans are
@@ -1443,6 +1503,13 @@ class VoiceFixer(nn.Module):
                     if extra:
                         lv = extra[0].numpy()
                         for r, i in enumerate(idx):
+                            if lv.shape[1] == 8:              # the limiter's record (loudness.py)
+                                db = [20.0 * float(np.log10(v)) if v > 0 else -float("inf") for v in lv[r, [1, 3, 5, 6, 7]]]
+                                loud_rows[i] = (float(lv[r, 0]), db[0] + db[3])
+                                lim_rows[i] = (db[2], db[3], db[4])
+                                if job.true_peak:
+                                    tp_rows[i] = (db[1], db[4])
+                                continue
                             loud_rows[i] = (float(lv[r, 0]), 20.0 * float(np.log10(lv[r, 1])))
                             if lv.shape[1] == 4:
                                 before = 20.0 * float(np.log10(lv[r, 3])) if lv[r, 3] > 0 else -float("inf")
@@ -1472,6 +1539,8 @@ class VoiceFixer(nn.Module):
                          loudness=sorted((names[i],) + loud_rows[i] for i in done if i in loud_rows))
             if job.true_peak and job.loudness is not None:
                 stats["true_peak"] = sorted((names[i],) + tp_rows[i] for i in done if i in tp_rows)
+            if job.limiter:
+                stats["limiter"] = sorted((names[i],) + lim_rows[i] for i in done if i in lim_rows)
         return sorted(written)
 
     @staticmethod
@@ -1480,14 +1549,16 @@ class VoiceFixer(nn.Module):
 
     def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
                 resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
-                channel_weights=None):
+                channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
         """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
         rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
         resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device);
-        ``loudness`` / ``peak_ceiling`` / ``true_peak``: as ``restore_inmem``.  ``channels`` (extension): None or "mix": a file
+        ``loudness`` / ``peak_ceiling`` / ``true_peak`` / ``limiter`` / ``limiter_lookahead_ms``: as ``restore_inmem``.
+        ``channels`` (extension): None or "mix": a file
         of several channels is averaged to one (the reference's ``librosa.load``); "first": its first channel; "all": every
         channel is restored (``restore_inmem(channels="all")``) and the output has the input's channel count."""
-        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights)
+        job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, limiter=limiter,
+                      limiter_lookahead_ms=limiter_lookahead_ms)
         channels = _check_channels(channels)
 
         per_channel = channels in ("first", "all")
@@ -1499,6 +1570,8 @@ class VoiceFixer(nn.Module):
         else:
             x, sr = self._load_wav(input, sample_rate=44100), 44100
         kw = {"channels": "all", "channel_weights": channel_weights} if channels == "all" else {}
+        if job.limiter:
+            kw.update(limiter=True, limiter_lookahead_ms=job.limiter_lookahead_ms)
         out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
                                         your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
                                         output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,

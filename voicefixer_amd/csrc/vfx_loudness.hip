@@ -295,21 +295,16 @@ __device__ __forceinline__ long long tp_tiles(long long n, int R, int c, long lo
     return n > 0 ? (((long long)c + (long long)R * n - 1) / R - Kal) / TP_TILE + 1 : 0;
 }
 
+// Stage the bank and the tile from K0 of the row xr (n samples) into tp_lds, then form both chains of the R * TP_KPL outputs
+// of this lane: output (K0 + TP_KPL * l + k) * R + p is aa[p][k] + ab[p][k].  Shared by lk_truepeak_kernel and the limiter's
+// lk_env_kernel, so the envelope and the partials are the same bits.
 template <int R, bool VEC>
-__global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restrict__ x, long long x_stride,
-                                                           const int* __restrict__ n_rows, long long n_max,
-                                                           const float* __restrict__ bank, int J, int Jp, float* part,
-                                                           lk_tp t) {
-    extern __shared__ float4 tp_lds[];
+__device__ __forceinline__ void tp_tile_sums(const float* __restrict__ xr, long long n, const float* __restrict__ bank, int J,
+                                             int Jp, long long K0, float4* tp_lds, float (&aa)[R][TP_KPL],
+                                             float (&ab)[R][TP_KPL]) {
     float* xs = reinterpret_cast<float*>(tp_lds);         // [TP_TILE + Jp]
     float* bk = xs + TP_TILE + Jp;                        // [R][Jp]
-    const int r = blockIdx.y, l = threadIdx.x;
-    long long n = n_rows[r];
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    if ((long long)blockIdx.x >= tp_tiles(n, R, t.c, t.Kal)) return;         // (uniform over the workgroup)
-    const long long t_end = (long long)t.c + (long long)R * n;
-    const long long K0 = t.Kal + (long long)blockIdx.x * TP_TILE;
-    const float* xr = x + (long long)r * x_stride;
+    const int l = threadIdx.x;
     for (int i = l; i < R * Jp; i += TP_T) {
         const int p = i / Jp, ii = i - p * Jp - (Jp - J);
         bk[i] = ii >= 0 ? bank[p * J + ii] : 0.f;
@@ -332,7 +327,6 @@ __global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restri
     const float4* xs4 = tp_lds;
     const float4* bk4 = reinterpret_cast<const float4*>(bk);
     const int nb = Jp / 4;
-    float aa[R][TP_KPL], ab[R][TP_KPL];
 #pragma unroll
     for (int p = 0; p < R; ++p)
 #pragma unroll
@@ -355,6 +349,23 @@ __global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restri
         }
         a = d;
     }
+}
+
+template <int R, bool VEC>
+__global__ __launch_bounds__(TP_T) void lk_truepeak_kernel(const float* __restrict__ x, long long x_stride,
+                                                           const int* __restrict__ n_rows, long long n_max,
+                                                           const float* __restrict__ bank, int J, int Jp, float* part,
+                                                           lk_tp t) {
+    extern __shared__ float4 tp_lds[];
+    float* xs = reinterpret_cast<float*>(tp_lds);         // [TP_TILE + Jp]
+    const int r = blockIdx.y, l = threadIdx.x;
+    long long n = n_rows[r];
+    n = n < 0 ? 0 : (n > n_max ? n_max : n);
+    if ((long long)blockIdx.x >= tp_tiles(n, R, t.c, t.Kal)) return;         // (uniform over the workgroup)
+    const long long t_end = (long long)t.c + (long long)R * n;
+    const long long K0 = t.Kal + (long long)blockIdx.x * TP_TILE;
+    float aa[R][TP_KPL], ab[R][TP_KPL];
+    tp_tile_sums<R, VEC>(x + (long long)r * x_stride, n, bank, J, Jp, K0, tp_lds, aa, ab);
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < TP_KPL; ++k)
@@ -693,12 +704,15 @@ static void lk_ext_layout(int B, long long n_max, int hop, bool report, size_t* 
     }
 }
 
-// mode 0: vfx_loudness_rows_f32 ({L, g, P});  1: with the true peak ({L, g, P, TP});  2: the report (measure only).
-// G > 0 (modes 1 and 2): the rows form G programmes (group_start, weight: lk_grp), result / report have G rows.
+#include "vfx_limit.inc"
+
+// mode 0: vfx_loudness_rows_f32 ({L, g, P});  1: with the true peak ({L, g, P, TP});  2: the report (measure only);
+// 3: the look-ahead limiter (vfx_loudness_limit_f32: the measurement of mode 1, then lk_limit_run; result has 8 columns).
+// G > 0 (modes 1, 2 and 3): the rows form G programmes (group_start, weight: lk_grp), result / report have G rows.
 static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max, const double* coef,
                   const double* mpow, int S, int hop, int lookback, double target, double ceiling_db, const float* bank, int J,
                   int R, int c, float* out, int64_t out_stride, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream,
-                  int G = 0, const int32_t* group_start = nullptr, const double* weight = nullptr) {
+                  int G = 0, const int32_t* group_start = nullptr, const double* weight = nullptr, int H = 0) {
     if (!x || !n_rows || !coef || !mpow || !result || !ws || B <= 0 || B > 65535 || n_max < 0 || n_max > INT32_MAX)
         return VFX_EINVAL;
     const bool grouped = G != 0 || group_start || weight;
@@ -717,7 +731,13 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
     lk_layout(B, n_max, hop, S, &need, &w, (char*)ws);
     if (mode != 0) lk_ext_layout(B, n_max, hop, mode == 2, &more, &e, (char*)ws + need);
     const size_t rowres_bytes = grouped && mode == 1 ? lk_round((size_t)B * 4 * sizeof(double)) : 0;
-    if (ws_bytes < need + more + rowres_bytes || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
+    size_t lim_bytes = 0;
+    lk_lim lm = {};
+    if (mode == 3) {
+        if (H < 1 || H > LM_HMAX || std::isnan(target) || !lk_lim_alias_ok(x, x_stride, out, out_stride, B, n_max)) return VFX_EINVAL;
+        lk_lim_layout(B, n_max, &lim_bytes, &lm, (char*)ws + need + more);
+    }
+    if (ws_bytes < need + more + rowres_bytes + lim_bytes || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
     const lk_grp grp = {(const int*)group_start, weight, rowres_bytes ? (double*)((char*)ws + need + more) : nullptr, B};
     const lk_coef k = {(float)coef[0], (float)coef[1], (float)coef[2], (float)coef[3], (float)coef[4],
                        (float)coef[5], (float)coef[6], (float)coef[7], (float)coef[8], (float)coef[9]};
@@ -752,9 +772,11 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
     if (mode == 0) hipLaunchKernelGGL((lk_gate_kernel<3, false>), dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
                                       (long long)n_max, S, hop, target, ceiling_db, result, w, t, grp);
     else if (!grouped) hipLaunchKernelGGL((lk_gate_kernel<4, false>), dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
-                                          (long long)n_max, S, hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t, grp);
+                                          (long long)n_max, S, hop, target, ceiling_db,
+                                          mode == 2 ? e.res4 : (mode == 3 ? lm.res4 : result), w, t, grp);
     else hipLaunchKernelGGL((lk_gate_kernel<4, true>), dim3((unsigned)G), dim3(LK_T), 0, s, (const int*)n_rows,
-                            (long long)n_max, S, hop, target, ceiling_db, mode == 2 ? e.res4 : result, w, t, grp);
+                            (long long)n_max, S, hop, target, ceiling_db, mode == 2 ? e.res4 : (mode == 3 ? lm.res4 : result), w, t,
+                            grp);
     VFX_LAUNCHED();
     if (mode == 2) {
         if (!grouped) hipLaunchKernelGGL(lk_report_kernel<false>, dim3((unsigned)B), dim3(LK_T), 0, s, (const int*)n_rows,
@@ -763,6 +785,9 @@ static int lk_run(int mode, const float* x, int64_t x_stride, const int32_t* n_r
                                 (long long)n_max, S, hop, (const double*)e.res4, result, e.qs, e.st, e.nqmax, w, grp);
         VFX_LAUNCHED();
     }
+    if (mode == 3)
+        return lk_limit_run(x, x_stride, n_rows, B, n_max, target, ceiling_db, bank, J, H, out, out_stride, result, s, t, grp,
+                            grouped ? G : 0, lm);
     if (apply) {
         long long nbx = (n_max / 4 + LK_T - 1) / LK_T;
         nbx = nbx < 1 ? 1 : (nbx > 2048 ? 2048 : nbx);
@@ -851,4 +876,27 @@ extern "C" int vfx_loudness_report_groups_f32(const float* x, int64_t x_stride, 
     if (G < 1 || !group_start || !weight) return VFX_EINVAL;
     return lk_run(2, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, NAN, -1.0, bank, J, R, c, nullptr, 0, report,
                   ws, ws_bytes, stream, G, group_start, weight);
+}
+
+/* ---- look-ahead peak limiter (kernels: vfx_limit.inc) -------------------------------------------------------- */
+
+extern "C" size_t vfx_loudness_limit_workspace_bytes(int B, int64_t n_max, int hop, int S, int R, int J) {
+    if (B <= 0 || n_max < 0 || n_max > INT32_MAX || hop <= 0 || S <= 0 || J < 1 || J > TP_JMAX || (R != 1 && R != 2 && R != 4))
+        return 0;
+    size_t total = 0, more = 0, lim = 0;
+    lk_layout(B, n_max, hop, S, &total, nullptr, nullptr);
+    lk_ext_layout(B, n_max, hop, false, &more, nullptr, nullptr);
+    lk_lim_layout(B, n_max, &lim, nullptr, nullptr);
+    return total + more + lim;
+}
+
+extern "C" int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                                      const int32_t* group_start, const double* weight, int G, const double* coef,
+                                      const double* mpow, int S, int hop, int lookback, double target, double ceiling_db,
+                                      const float* bank, int J, int R, int c, float* out, int64_t out_stride, int H,
+                                      int true_peak, double* result, void* ws, size_t ws_bytes, vfx_stream_t stream) {
+    if (G < 0 || (true_peak != 0 && true_peak != 1)) return VFX_EINVAL;
+    if (!true_peak) R = 1;                                // (the sample-peak limiter: nothing is oversampled)
+    return lk_run(3, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, target, ceiling_db, bank, J, R, c, out,
+                  out_stride, result, ws, ws_bytes, stream, G, group_start, weight, H);
 }

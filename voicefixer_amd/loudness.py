@@ -45,6 +45,27 @@ sample peak and TP_c the true peak of channel c as defined above:
 ``channel_weights(C)`` are the weights of BS.1770-4 Table 4 in the WAVE / FLAC channel order (L R C LFE Ls Rs ...: the
 surrounds weigh 1.41, the LFE 0).  Two identical channels therefore read 10 log10 2 = 3.0103 LU above the same signal as
 one channel: that is the recommendation's sum over channels, not an error.
+
+Look-ahead peak limiter (``limiter=True`` with a loudness target; ``vfx_loudness_limit_f32``).  Per row of N
+samples at fs, or per programme of linked channels, after the measurement above has produced L, P and TP:
+
+  1. gL = 10^((T - L)/20) (1 when L = -inf), Cl = 10^(peak_ceiling/20).  The row is BOUND iff gL TP > Cl (TP is the sample
+     peak P with ``true_peak=False``); a row that is not bound is written as float32(gL) x, exactly as without the limiter.
+  2. Peak envelope: e[n] = |x[n]| with ``true_peak=False`` or at R = 1; otherwise, with y[m] the interpolation above
+     (m in [0, R N), bank centre c), e[n] = max(|x[n]|, max{|y[m]| : n(m) = n}), n(m) = min((m + c mod R) // R, N - 1).  For both
+     banks c mod R = R - 1 (c = 375 at R = 4, 187 at R = 2), so sample n collects the interpolated values at times in
+     (n - 1, n].  For a programme e[n] is the maximum over its channels.
+  3. Required gain: c[n] = min(1, Cl / (gL e[n])), 1 when e[n] = 0.
+  4. Look-ahead: H = round(fs lookahead_ms / 1000), lookahead_ms in [0.1, 10] (default 3.0), H in [1, 4096];
+     m[n] = min{c[j] : |j - n| <= H, 0 <= j < N}.
+  5. Smoothing: w[k] = (1 + cos(pi k / (H + 1))) / (2 H + 2) for |k| <= H (all positive, summing to exactly 1);
+     g[n] = 1 - sum_{|k| <= H} w[k] (1 - m[clamp(n + k, 0, N - 1)]).  The deficit form gives g[n] = 1 EXACTLY wherever the
+     window holds only ones; every m in the window of n covers n, so g[n] <= c[n].
+  6. Limited row: v[n] = gL g[n] x[n].
+  7. Trim: the interpolated peak of a gain-modulated row is not bounded exactly by step 5.  TPv is the true peak of v by the
+     same definition (the sample peak in the sample-peak mode, where t = 1 always); t = min(1, Cl / TPv); the output is t v.
+  8. Result record per row or programme, device float64: {L, gL, P, TP, bound (0/1), min_n g[n], t, TPv t}; a row that is
+     not bound records {L, gL, P, TP, 0, 1, 1, float32(gL) TP}.
 """
 import math
 
@@ -59,6 +80,8 @@ NPOW = 16                     # M^(2^i), i < NPOW (LK_NPOW)
 TARGET_RANGE = (-70.0, 0.0)   # LUFS, [lo, hi)
 CEILING_RANGE = (-20.0, 0.0)  # dBFS, [lo, hi]
 MAX_CHANNELS = 8
+LOOKAHEAD_MS_RANGE = (0.1, 10.0)   # ms, [lo, hi]
+LOOKAHEAD_MAX = 4096               # samples (LM_HMAX of the kernel)
 _SURROUND = 1.41              # BS.1770-4 Table 4 (Ls, Rs)
 _TABLE4 = {1: [1.0], 2: [1.0, 1.0], 3: [1.0, 1.0, 1.0], 4: [1.0, 1.0, _SURROUND, _SURROUND],
            5: [1.0, 1.0, 1.0, _SURROUND, _SURROUND], 6: [1.0, 1.0, 1.0, 0.0, _SURROUND, _SURROUND],
@@ -224,3 +247,25 @@ def check_channels(channels, allow_none=True):
     if not isinstance(channels, str) or channels not in CHANNEL_MODES:
         raise ValueError("channels must be 'mix', 'first' or 'all' (got %r)" % (channels,))
     return channels
+
+
+def check_limiter(limiter, lookahead_ms=3.0):
+    """(limiter, lookahead_ms): ``limiter`` is a bool, ``lookahead_ms`` a number in [0.1, 10]."""
+    if not isinstance(limiter, (bool, np.bool_)):
+        raise ValueError("limiter must be True or False (got %r)" % (limiter,))
+    v = _number(lookahead_ms, "limiter_lookahead_ms")
+    if not LOOKAHEAD_MS_RANGE[0] <= v <= LOOKAHEAD_MS_RANGE[1]:
+        raise ValueError("limiter_lookahead_ms must be in [0.1, 10] ms (got %r)" % (lookahead_ms,))
+    return bool(limiter), v
+
+
+def limiter_window(fs, ms=3.0):
+    """(H, w) of the limiter at ``fs`` Hz: H = round(fs ms / 1000) in [1, 4096] (ValueError otherwise) and the smoothing
+    weights w[k], k = -H..H, float64[2 H + 1]: (1 + cos(pi k / (H + 1))) / (2 H + 2)."""
+    fs = _check_rate(fs)
+    ms = check_limiter(True, ms)[1]
+    H = int(math.floor(fs * ms / 1000.0 + 0.5))
+    if not 1 <= H <= LOOKAHEAD_MAX:
+        raise ValueError("limiter: a look-ahead of %r ms at %d Hz is %d samples, outside [1, %d]" % (ms, fs, H, LOOKAHEAD_MAX))
+    k = np.arange(-H, H + 1, dtype=np.float64)
+    return H, (1.0 + np.cos(np.pi * k / (H + 1))) / (2.0 * H + 2.0)

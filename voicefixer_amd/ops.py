@@ -721,6 +721,49 @@ def loudness_groups(x, n_rows, groups, fs, target=None, peak_ceiling=-1.0, out=N
     return res
 
 
+def loudness_limit(x, n_rows, rate, target, ceiling_db=-1.0, true_peak=True, lookahead_ms=3.0, out=None, groups=None,
+                   weights=None):
+    """Loudness normalisation with the look-ahead peak limiter in place of the static ceiling (vfx_loudness_limit_f32;
+    loudness.py): the rows of x (B, >= max n) at ``rate`` Hz are brought to ``target`` LUFS, and where that
+    would pass the ceiling (dBTP with ``true_peak``, else dBFS) a gain curve that looks ``lookahead_ms`` ahead holds the peaks
+    under it.  ``groups`` = [C_0, C_1, ...]: programmes of adjacent channels as in loudness_groups (``n_rows`` then a list or
+    a device tensor as there, one gain curve per programme); None: one programme per row, ``n_rows`` a device int32 (B,).
+    Writes ``out`` (default: in place) up to every row's own length and returns a device float64 (G or B, 8) of {L, gL, P,
+    TP, bound, min g, t, peak after}.  No synchronisation; the launch count depends on neither B nor the lengths."""
+    from . import loudness
+    _need_cuda(x, out)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    target = loudness.check_target(target)
+    if target is None:
+        raise ValueError("loudness_limit: the limiter needs a loudness target")
+    ceiling_db = loudness.check_ceiling(ceiling_db)
+    true_peak = loudness.check_true_peak(true_peak)
+    H = loudness.limiter_window(rate, lookahead_ms)[0]
+    start = wt = None
+    G = 0
+    if groups is not None:
+        n_rows, start, wt, G = _loudness_groups_plan(x, n_rows, groups, weights)
+    _need_cuda(n_rows)
+    assert n_rows.dtype == torch.int32 and n_rows.numel() == x.shape[0]
+    p, mpow, coef, (bank, J, R, c) = _loudness_plan(x, rate)
+    if not true_peak:
+        bank, J, R, c = mpow, 1, 1, 0                      # (R = 1: the bank is never read, must not be null)
+    if out is None:
+        out = x
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == x.shape[0]
+    assert out.shape[1] >= x.shape[1]
+    B, n_max = x.shape
+    h = _lib.lib()
+    nb = h.vfx_loudness_limit_workspace_bytes(B, n_max, p["hop"], p["S"], R, J)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=x.device)
+    res = torch.empty((G if G else B, 8), dtype=torch.float64, device=x.device)
+    check(h.vfx_loudness_limit_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, _ptr(start), _ptr(wt), G,
+                                   coef, _ptr(mpow), p["S"], p["hop"], p["lookback"], target, ceiling_db, _ptr(bank), J, R, c,
+                                   _ptr(out), out.stride(0) if B > 1 else out.shape[1], H, 1 if true_peak else 0, _ptr(res),
+                                   _ptr(ws), nb, _stream()), "vfx_loudness_limit_f32")
+    return res
+
+
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):
     """Loudness report of programmes of several channels (vfx_loudness_report_groups_f32; arguments as loudness_groups): a
     device float64 (G, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample
