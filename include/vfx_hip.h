@@ -1,6 +1,8 @@
 /*
  * vfx_hip.h -- C ABI of libvfx_hip.so, the MI355X (gfx950) kernel library behind
- * voicefixer_amd.VoiceFixer.restore()/restore_inmem() and Vocoder.forward()/oracle().
+ * voicefixer_amd.VoiceFixer.restore()/restore_inmem() and Vocoder.forward()/oracle(), and of the stages between the restored
+ * waveform and the file: rate conversion, loudness / true peak / limiter, and the word-length reduction to 16- or 24-bit PCM
+ * (vfx_quantize_rows_f32), which -- when asked for -- takes the place of the reference's truncating int16 cast on the host.
  *
  * The reference (haoheliu/voicefixer) has no FFI: its hot path is a chain of stock torch
  * operators.  Each entry point below replaces the torch operator calls named in its
@@ -539,7 +541,31 @@ int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const int32_t* n_ro
                            int c, float* out, int64_t out_stride, int H, int true_peak, double* result, void* ws,
                            size_t ws_bytes, vfx_stream_t stream);
 
-/* ---- train-mode restorer (the reference's mode 2: restorer/model.py:69-99 and modules.py in .train()) --------------- */
+/* ---- word-length reduction: 16- / 24-bit PCM with seeded dither (voicefixer_amd/wordlength.py) ----------------- */
+
+/* The last stage of the output chain (the reference's save_wave truncates to int16 on the host, voicefixer/tools/wav.py:27-34;
+ * this is the opt-in replacement): row r of x ([B][x_stride] float32, n_rows device int32[B], each clamped to [0, n_max])
+ * becomes PCM of `bits` in {16, 24} bits.  With n = n0[r] + i the ABSOLUTE index of sample i in its file (n0: device int64[B],
+ * each >= 0; NULL: all 0), c = chan[r] its channel (device int32[B], 0..7; NULL: all 0) and
+ *   k_t(n) = (word n % 4 of Philox4x32-10(counter = ((n / 4) & 0xffffffff, (n / 4) >> 32, c, t), key = (seed & 0xffffffff,
+ *            seed >> 32))) >> 8,   t in {0, 1},
+ *   dither 0 (none): d = 0;   1 (tpdf): d = (k_0(n) - k_1(n)) * 2^-24;   2 (hp): d = (k_0(n) - k_0(n - 1)) * 2^-24, d(0) as tpdf,
+ *   v = (double)x * 2^(bits-1) + d  (one float64 rounding);  NaN -> 0;
+ *   q = clamp(rint(v), -2^(bits-1), 2^(bits-1) - 1)          (round half to even; saturates, never wraps),
+ * the integers of voicefixer_amd/wordlength.py, bit for bit, whatever the batch, the alignment or the split of a row into calls.
+ * out: int16 rows at bits == 16, int32 rows at 24, [B][out_stride] (strides in elements); the first n_rows[r] samples of every
+ * row are written and nothing else.  result: device int32[B][2] = {clipped, peak}, overwritten: clipped counts the samples the
+ * clamp changed or whose x was NaN, peak = max |q|.  Grid (tiles of 1024 samples, B), capped at about 2048 workgroups (a
+ * workgroup then walks further tiles of its row); four consecutive samples per thread (one 16-byte load and one 8- / 16-byte store
+ * when x, out and both strides allow it), float64 arithmetic, per-row counts by a wave reduction and at most one vector atomic of
+ * each kind per workgroup.  One kernel behind one clear of result on the stream; no host synchronisation.
+ * VFX_EINVAL, nothing launched: a NULL x, n_rows, out or result, B < 0 or > 65535, n_max < 0, bits not 16 or 24, dither not in
+ * 0..2, x_stride or out_stride < n_max.  B == 0 or n_max == 0: VFX_OK, nothing launched. */
+int vfx_quantize_rows_f32(const float* x, int64_t x_stride, const int32_t* n_rows, int B, int64_t n_max,
+                          const int64_t* n0, const int32_t* chan, int bits, int dither, uint64_t seed, void* out,
+                          int64_t out_stride, int32_t* result, vfx_stream_t stream);
+
+/* ---- train-mode restorer (the reference's mode 2:restorer/model.py:69-99 and modules.py in .train()) --------------- */
 
 /* BatchNorm batch statistics: per (batch row b, BN channel g) the mean and BIASED variance of a region of x, turned into
  * the affine of torch's train-mode batch_norm: scale[b*G+g] = gamma[g]/sqrt(var+eps), shift[b*G+g] = beta[g] - mean*scale.

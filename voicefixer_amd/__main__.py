@@ -33,6 +33,11 @@ Differences, all deliberate:
     input with several channels -- ``mix`` (default): their average, as the reference's ``librosa.load``; ``first``: the first
     channel; ``all``: every channel is restored and the output has the input's channel count; ``--loudness`` is then ONE
     linked gain per file (BS.1770-4's weighted sum over the channels), which keeps their balance;
+  * ``--bit-depth {16,24}`` (extension; file and folder mode, forwarded to every ``--gpus`` rank): the outputs are reduced to
+    that word length ON THE DEVICE -- rounded to nearest, saturating, with the dither ``--dither {none,tpdf,hp}`` (default
+    tpdf) drawn from ``--dither-seed N`` (default 0) -- cross to the host as PCM and are written at that depth; without it the
+    outputs are 16-bit, truncated on the host as the reference's ``save_wave`` does (``--dither`` / ``--dither-seed`` alone are
+    an argument error);
   * output formats are WAV and FLAC (``audio_io.FORMATS``) instead of whatever libsndfile offers;
   * folder mode isolates faults per FILE: an unreadable / truncated / too short input or a row the device refuses costs that
     file only -- it is listed on stderr with its reason, every other file is written, the exit status is 2 (all ranks of a
@@ -84,7 +89,7 @@ def mode_outfile(outfile, mode, append_mode):
 
 def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=False, seed=None, output_sample_rate=None,
               resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None, limiter=False,
-              limiter_lookahead_ms=3.0):
+              limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf", dither_seed=0):
     outfile = mode_outfile(outfile, mode, append_mode)
     if verbose:
         print("Processing {}, mode={}".format(infile, mode))
@@ -92,7 +97,8 @@ def writefile(voicefixer, infile, outfile, mode, append_mode, cuda, verbose=Fals
     voicefixer.restore(input=infile, output=outfile, cuda=cuda, mode=int(mode), seed=seed, output_sample_rate=output_sample_rate,
                        resample_on_device=resample_on_device, loudness=loudness, peak_ceiling=peak_ceiling, true_peak=true_peak,
                        channels=channels,
-                       **({"limiter": True, "limiter_lookahead_ms": limiter_lookahead_ms} if limiter else {}))
+                       **({"limiter": True, "limiter_lookahead_ms": limiter_lookahead_ms} if limiter else {}),
+                       **({"bit_depth": bit_depth, "dither": dither, "dither_seed": dither_seed} if bit_depth is not None else {}))
     print("Restoration took {} s".format(round(time.time() - start, 1)))
 
 
@@ -109,6 +115,14 @@ class _Parser(argparse.ArgumentParser):
             self.error("--limiter-lookahead-ms needs --limiter (and --loudness)")
         if ns.limiter_lookahead_ms is None:
             ns.limiter_lookahead_ms = 3.0
+        if ns.dither is not None and ns.bit_depth is None:
+            self.error("--dither needs --bit-depth: it is the dither of the word-length reduction")
+        if ns.dither_seed is not None and ns.bit_depth is None:
+            self.error("--dither-seed needs --bit-depth (and a --dither other than none)")
+        if ns.dither is None:
+            ns.dither = "tpdf"
+        if ns.dither_seed is None:
+            ns.dither_seed = 0
         return ns
 
 
@@ -164,6 +178,14 @@ def build_parser():
                         help="(extension) inputs of several channels: mix (default): restore their average; first: restore the "
                              "first channel; all: restore every channel and write the input's channel count (with --loudness: "
                              "one linked gain per file)")
+    parser.add_argument("--bit-depth", type=int, choices=[16, 24], default=None,
+                        help="(extension) reduce the outputs to this word length on the device (rounded, saturating, dithered) and "
+                             "write them at that depth; default: 16-bit, truncated on the host as the reference does")
+    parser.add_argument("--dither", choices=["none", "tpdf", "hp"], default=None,
+                        help="(extension) with --bit-depth: tpdf (default): white triangular dither of +-1 LSB; hp: the same "
+                             "amplitude, high-passed; none: plain rounding")
+    parser.add_argument("--dither-seed", type=_seed, default=None, metavar="N",
+                        help="(extension) with --bit-depth: seed of the dither, an int in [0, 2**64) (default 0)")
     return parser
 
 
@@ -304,7 +326,8 @@ def main(argv=None):
             writefile(voicefixer, args.infile, args.outfile, m, append, cuda, verbose=not args.silent, seed=args.seed,
                       output_sample_rate=args.output_sample_rate, resample_on_device=args.resample_on_device,
                       loudness=args.loudness, peak_ceiling=args.peak_ceiling, true_peak=args.true_peak, channels=args.channels,
-                      limiter=args.limiter, limiter_lookahead_ms=args.limiter_lookahead_ms)
+                      limiter=args.limiter, limiter_lookahead_ms=args.limiter_lookahead_ms, bit_depth=args.bit_depth,
+                      dither=args.dither, dither_seed=args.dither_seed)
     n_failed = 0
     if process_folder:
         n_files = len([f for f in os.listdir(args.infolder) if os.path.splitext(os.path.basename(f))[-1] == ".wav"])
@@ -323,7 +346,9 @@ def main(argv=None):
                                           peak_ceiling=args.peak_ceiling, **({"true_peak": True} if args.true_peak else {}),
                                           **({"channels": args.channels} if args.channels is not None else {}),
                                           **({"limiter": True, "limiter_lookahead_ms": args.limiter_lookahead_ms}
-                                             if args.limiter else {}))
+                                             if args.limiter else {}),
+                                          **({"bit_depth": args.bit_depth, "dither": args.dither, "dither_seed": args.dither_seed}
+                                             if args.bit_depth is not None else {}))
             except Exception as e:    # noqa: BLE001 -- per-file faults never get here (restore_folder isolates them); whatever does
                 # must not leave the other ranks waiting in the collectives below: this rank reports itself and goes on to them
                 import traceback

@@ -308,15 +308,18 @@ def _check_channels(channels):
 
 class _Output:
     """What happens to restored rows before they leave the device: the output rate, the loudness target with its ceiling
-    and channel weights, and mode 2's seed.  Built ONCE per public call from its keywords -- the checks are made here, before
-    anything touches the device -- and handed down as it is.  ``kwargs()`` is the one place that knows which keywords a
-    ``restore_batches`` call is given, ``finish()`` the one tail of the device stage."""
+    and channel weights, mode 2's seed, and the word length they leave at.  Built ONCE per public call from its keywords -- the
+    checks are made here, before anything touches the device -- and handed down as it is.  ``kwargs()`` is the one place that
+    knows which keywords a ``restore_batches`` call is given, ``finish()`` the one tail of the float device stage and
+    ``quantize()``, after it, the reduction to ``bit_depth``-bit PCM (None, the default: float32 rows leave, as ever)."""
     __slots__ = ("rate_out", "loudness", "peak_ceiling", "true_peak", "channel_weights", "seed", "limiter",
-                 "limiter_lookahead_ms")
+                 "limiter_lookahead_ms", "bit_depth", "dither", "dither_seed")
 
     def __init__(self, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None,
-                 mode=0, seed=None, limiter=False, limiter_lookahead_ms=3.0):
-        from . import loudness as ld
+                 mode=0, seed=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf", dither_seed=0):
+        from . import dropout, loudness as ld, wordlength
+        self.bit_depth = wordlength.check_bit_depth(bit_depth, allow_none=True)
+        self.dither, self.dither_seed = wordlength.check_dither(dither), dropout.check_seed(dither_seed)
         self.rate_out = _output_rate(output_sample_rate)
         self.true_peak = ld.check_true_peak(true_peak)
         self.loudness, self.peak_ceiling = ld.check_target(loudness), ld.check_ceiling(peak_ceiling)
@@ -353,6 +356,8 @@ class _Output:
                 kw["channel_weights"] = self.channel_weights
             if self.limiter:
                 kw.update(limiter=True, limiter_lookahead_ms=self.limiter_lookahead_ms)
+        if self.bit_depth is not None:
+            kw.update(bit_depth=self.bit_depth, dither=self.dither, dither_seed=self.dither_seed)
         return kw
 
     def finish(self, full, lens, groups=None):
@@ -371,6 +376,36 @@ class _Output:
         elif self.loudness is not None:
             full, res = apply_loudness(full, lens, self.rate_out, self.loudness, self.peak_ceiling, self.true_peak)
         return full, lens, res
+
+    def quantize(self, full, lens, groups=None, n0=None):
+        """The rows ``finish()`` returned -> (PCM rows, device int32 (B, 2) of {clipped samples, max |q|}): int16 rows at
+        ``bit_depth`` 16, int32 rows at 24, quantised on the device with the job's dither (ops.quantize_rows; wordlength.py).  A
+        row's channel is its index within its file of ``groups`` adjacent rows (0 without groups); ``n0`` (one int, or one per
+        row; default 0) is the absolute index of the rows' first sample in their file -- a streaming session passes its position."""
+        from . import ops, wordlength
+        if self.bit_depth is None:
+            raise ValueError("_Output.quantize: the job has no bit_depth")
+        x = full if full.stride(-1) == 1 else full.contiguous()
+        B, dev = x.shape[0], x.device
+        if len(lens) != B:
+            raise ValueError("_Output.quantize: %d lengths for %d rows" % (len(lens), B))
+        n_rows = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev, non_blocking=True)
+        chan = None
+        if groups is not None:
+            chans = [c for g in groups for c in range(int(g))]
+            if len(chans) != B or max(chans, default=0) >= wordlength.MAX_CHANNELS:
+                raise ValueError("_Output.quantize: groups %r do not describe %d rows of 1..8 channels" % (list(groups), B))
+            if any(chans):
+                chan = torch.tensor(chans, dtype=torch.int32).to(dev, non_blocking=True)
+        start = None
+        if n0 is not None:
+            first = [wordlength.check_position(n0)] * B if isinstance(n0, (int, np.integer)) else \
+                [wordlength.check_position(v) for v in n0]
+            if len(first) != B:
+                raise ValueError("_Output.quantize: %d positions for %d rows" % (len(first), B))
+            if any(first):
+                start = torch.tensor(first, dtype=torch.int64).to(dev, non_blocking=True)
+        return ops.quantize_rows(x, n_rows, self.bit_depth, self.dither, self.dither_seed, start, chan)
 
 
 class _Batch:
@@ -543,6 +578,39 @@ def measure_loudness(wav, sample_rate=44100, channel_weights=None):
                     lambda x, n_rows: ops.loudness_rows(x, n_rows, sample_rate),
                     lambda x, lens, counts, weights: ops.loudness_groups(x, lens, counts, sample_rate, weights=weights),
                     lambda v: float(v[0]))
+
+
+def quantize(wav, bit_depth=16, dither="tpdf", dither_seed=0):
+    """Word-length reduction of a float array (N,) -- or of every array of a list, in one device call -- to ``bit_depth``-bit
+    PCM (16: int16, 24: int32) on the device: rounded to nearest, saturating, with the seeded dither ``dither`` ("tpdf",
+    "hp" or "none"; wordlength.py has the definition, ``wordlength.quantize_ref`` gives the same integers).  A (C, N) array is
+    a file of C channels (1..8): channel c draws the dither of channel c.  Every array starts at sample 0.  Lists may mix (N,)
+    and (C, N) arrays; what comes back has the shapes that went in."""
+    from . import wordlength
+    job = _Output(bit_depth=wordlength.check_bit_depth(bit_depth), dither=dither, dither_seed=dither_seed)
+    single = not isinstance(wav, (list, tuple))
+    items = [np.asarray(w, dtype=np.float32) for w in ([wav] if single else wav)]
+    for w in items:
+        if w.ndim not in (1, 2) or (w.ndim == 2 and not 1 <= w.shape[0] <= wordlength.MAX_CHANNELS):
+            raise ValueError("a waveform is (N,) or (channels, N) with 1..8 channels (got shape %r)" % (w.shape,))
+    if not items:
+        return []
+    rows = [w[None] if w.ndim == 1 else w for w in items]
+    groups = [w.shape[0] for w in rows]
+    lens = [w.shape[1] for w in rows for _ in range(w.shape[0])]
+    host = np.zeros((len(lens), max(max(lens), 1)), np.float32)
+    r = 0
+    for w in rows:
+        host[r:r + w.shape[0], :w.shape[1]] = w
+        r += w.shape[0]
+    pcm, _ = job.quantize(torch.from_numpy(host).to(_device()), lens, groups)
+    pcm = pcm.cpu().numpy()
+    out, r = [], 0
+    for w, v in zip(items, rows):
+        q = pcm[r:r + v.shape[0], :v.shape[1]].copy()
+        out.append(q[0] if w.ndim == 1 else q)
+        r += v.shape[0]
+    return out[0] if single else out
 
 
 class Vocoder(nn.Module):
@@ -741,7 +809,8 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_inmem(self, wav_10k, cuda=False, mode=0, your_vocoder_func=None, seed=None, sample_rate=44100,
                       output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
-                      channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
+                      channel_weights=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf",
+                      dither_seed=0):
         """wav_10k: float32 numpy (N,) at 44.1 kHz -> float32 numpy (1, N).
         30 s hard-cut segments, no overlap, concatenated (voicefixer/base.py:117-138).
         ``sample_rate`` (extension): the rate of ``wav_10k``; any other rate than 44.1 kHz is converted ON THE DEVICE
@@ -767,11 +836,16 @@ class VoiceFixer(nn.Module):
         then ONE linked gain for the file (BS.1770-4's sum over the channels weighted by ``channel_weights``, default
         loudness.channel_weights(C); the largest peak over the channels: ``apply_loudness_groups``), which keeps the
         balance between the channels.  "mix" / "first": a (C, N) input is averaged / cut to its first channel and restored
-        as one.  None (default): a 2-D input raises ValueError (it used to be misread as one long row)."""
+        as one.  None (default): a 2-D input raises ValueError (it used to be misread as one long row).
+        ``bit_depth`` (extension; 16 or 24): the finished output -- after every stage above -- is reduced ON THE DEVICE to PCM of
+        that word length and comes back as int16 / int32 of the same shape: rounded to nearest, saturating, with the dither
+        ``dither`` ("tpdf", the default: white triangular dither of +-1 LSB; "hp": the same amplitude, high-passed; "none") drawn
+        from ``dither_seed`` (an int in [0, 2**64)) as a function of the sample's index and channel (wordlength.py), so a call
+        can be repeated.  None (default): float32 comes back, and ``audio_io.save_wave`` truncates it as the reference does."""
         self._check_mode(mode, seed)
         rate_in = _check_rate(sample_rate)
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
-                      limiter_lookahead_ms)
+                      limiter_lookahead_ms, bit_depth, dither, dither_seed)
         wav, multi = _as_programme(wav_10k, _check_channels(channels), "restore_inmem")     # (C, n); C = 1 unless channels="all"
         C = wav.shape[0]
         job.check_channel_counts([C])
@@ -817,6 +891,8 @@ class VoiceFixer(nn.Module):
                 res.append(self._restore_segments(pipe, seg, b - a, mode, your_vocoder_func, seed, [len(full)] * C))
             out = torch.cat(res, -1)
             out, ms, _ = job.finish(out, [out.shape[-1]] * C, [C] if multi else None)
+            if job.bit_depth is not None:
+                out, _ = job.quantize(out, ms, [C] if multi else None)
             return out[:, :ms[0]].cpu().numpy()  # (synchronises)
 
         return pipe.run_checked(run)   # (device error flags are read here; a missed GRU hand-off re-runs the call)
@@ -848,8 +924,8 @@ class VoiceFixer(nn.Module):
     def _issue_batch(self, pipe, stream, batch, mode, your_vocoder_func, job):
         """Queue ONE batch (a ``_Batch``) on ``stream``: H2D of its pinned staging tensor, (rate conversion of rows at other rates
         than 44.1 kHz,) the launch sequence, the tail ``job`` (an ``_Output``) asks for -- (conversion to the output rate,)
-        (loudness normalisation) -- D2H of the result and of the loudness results into pinned tensors, an event.  Nothing here
-        waits for the device."""
+        (loudness normalisation,) (word-length reduction) -- D2H of the result (float32, or PCM with ``bit_depth``) and of the
+        loudness and word-length results into pinned tensors, an event.  Nothing here waits for the device."""
         from . import ops
         kind, host, lens, rates, seed = batch.kind, batch.host, batch.lens, batch.rates, job.seed
         if rates is not None and all(r == 44100 for r in rates):
@@ -905,16 +981,21 @@ class VoiceFixer(nn.Module):
             if res is not None:
                 loud_host = torch.empty(tuple(res.shape), dtype=torch.float64, pin_memory=True)
                 loud_host.copy_(res, non_blocking=True)
-            out_host = torch.empty(tuple(full.shape), dtype=torch.float32, pin_memory=True)
+            word_host = None
+            if job.bit_depth is not None:
+                full, qres = job.quantize(full, lens_out, batch.groups)
+                word_host = torch.empty(tuple(qres.shape), dtype=torch.int32, pin_memory=True)
+                word_host.copy_(qres, non_blocking=True)
+            out_host = torch.empty(tuple(full.shape), dtype=full.dtype, pin_memory=True)
             out_host.copy_(full, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
-        return [batch, out_host, lens_out, ev, loud_host]
+        return [batch, out_host, lens_out, ev, loud_host, word_host]
 
     @torch.no_grad()
     def restore_batches(self, batches, your_vocoder_func=None, streams=2, mode=0, seed=None, output_sample_rate=None,
                         loudness=None, peak_ceiling=-1.0, true_peak=False, channel_weights=None, limiter=False,
-                        limiter_lookahead_ms=3.0):
+                        limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf", dither_seed=0):
         """The device stage of folder inference as a GENERATOR: ``batches`` yields ``(tag, kind, host, lens)`` --
         ``host`` a pinned float32 (B, >= max(lens)) staging tensor whose row r holds ``lens[r]`` samples, ``kind``
         "ragged" (one launch sequence with per-row lengths, Pipeline.restore_rows) or "samples" (equal lengths: files
@@ -938,13 +1019,17 @@ class VoiceFixer(nn.Module):
         tag; the channels of a file are adjacent rows of one length and rate, ``tag`` has one entry per FILE.  Every row goes
         through the path on its own; ``loudness`` is then ONE linked gain per file (``apply_loudness_groups``, weights
         ``channel_weights`` or loudness.channel_weights) and ``loud_host`` has one row per file: (G, 4).
+        ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): every row is reduced to PCM on the device before it crosses --
+        ``out_host`` is then a pinned int16 (16) or int32 (24) tensor, half the bytes at 16 bits -- and the generator yields one
+        more field, LAST (behind ``loud_host`` when that is there): a pinned int32 (B, 2) of {clipped samples, max |q|} per row.
+        Every row starts at sample 0 of its file; its channel is its index within its file (``groups``).
         The two-CU GRU's error flag is read when a batch's result crosses to the host; a missed hand-off drains the
         batches in flight and re-issues them on the one-workgroup GRU kernel (Pipeline.run_checked's rule)."""
         from collections import deque
         from .engine import DeviceFlagRaised
         self._check_mode(mode, seed)
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
-                      limiter_lookahead_ms)
+                      limiter_lookahead_ms, bit_depth, dither, dither_seed)
         pipe = self._get_pipe()
         pool = self._streams(streams)
         main = torch.cuda.current_stream(pipe.device)
@@ -980,7 +1065,8 @@ class VoiceFixer(nn.Module):
                         pipe.check()
                     rec = inflight[0]
                 inflight.popleft()
-                return (rec[0].tag, rec[1], rec[2]) + ((rec[4],) if job.loudness is not None else ())
+                return (rec[0].tag, rec[1], rec[2]) + ((rec[4],) if job.loudness is not None else ()) + \
+                    ((rec[5],) if job.bit_depth is not None else ())
 
             for item in batches:
                 inflight.append(self._issue_batch(pipe, pool[nb % len(pool)], _Batch.parse(item), mode, your_vocoder_func, job))
@@ -1005,7 +1091,8 @@ class VoiceFixer(nn.Module):
     @torch.no_grad()
     def restore_batch(self, wavs, your_vocoder_func=None, batch_size=32, streams=2, ragged_ratio=0.5, mode=0, seed=None,
                       sample_rate=44100, output_sample_rate=None, loudness=None, peak_ceiling=-1.0, true_peak=False,
-                      channels=None, channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
+                      channels=None, channel_weights=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
+                      dither="tpdf", dither_seed=0):
         """Batched folder inference (not in the reference, which loops files at B=1,
         voicefixer/__main__.py:187-212): list of float32 numpy (N_i,) -> list of (1, N_i)  (mode 1: (1, 512*(N_i//512))
         per 30 s segment, as ``restore_inmem`` returns it).
@@ -1027,10 +1114,12 @@ class VoiceFixer(nn.Module):
         rows of one batch: the planning is by file, a file weighs C rows (ValueError when ``batch_size`` is smaller than the
         largest C), and ``loudness`` is one linked gain per file (``restore_inmem``; ``channel_weights`` then applies to
         every file and all must have that many channels).  "mix" / "first": (C, N) items are averaged / cut to their first
-        channel first.  None (default): as before."""
+        channel first.  None (default): as before.
+        ``bit_depth`` / ``dither`` / ``dither_seed``: as ``restore_inmem`` -- the results are int16 / int32 PCM of the same shapes,
+        each file quantised as that call quantises it, whatever else its batch holds."""
         self._check_mode(mode, seed)
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
-                      limiter_lookahead_ms)
+                      limiter_lookahead_ms, bit_depth, dither, dither_seed)
         multi = _check_channels(channels) == "all"
         progs = [_as_programme(w, channels, "restore_batch")[0] for w in wavs]     # (C_i, N_i); C_i = 1 unless channels="all"
         rates = _row_rates(sample_rate, len(progs))
@@ -1142,7 +1231,8 @@ class VoiceFixer(nn.Module):
         return out[:, :n_out]
 
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
-                    sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0):
+                    sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
+                    dither="tpdf", dither_seed=0):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
@@ -1150,12 +1240,14 @@ class VoiceFixer(nn.Module):
         ``overlap_seconds``, ``batch_size`` and ``mode`` -- bit for bit at ``batch_size=1`` -- converted as a whole to the
         output rate.  Modes 0 and 1; ``mode=2`` raises NotImplementedError.  The arguments are checked here, before the
         device is touched.  ``limiter=True`` raises NotImplementedError, as ``restore_stream`` does: a session
-        never sees the whole file."""
+        never sees the whole file.  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
+        on the device, each from the session's position on, so that all of them, concatenated, are the whole output quantised
+        once; ``push`` and ``finish`` then return int16 / int32 arrays."""
         if _check_limiter(limiter, limiter_lookahead_ms):
             raise NotImplementedError("open_stream: the limiter is not built -- it follows a whole-file loudness measurement; use "
                                       "restore_inmem or restore_folder")
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
-                              output_sample_rate)
+                              output_sample_rate, bit_depth, dither, dither_seed)
 
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
@@ -1217,7 +1309,7 @@ class VoiceFixer(nn.Module):
                        name_suffix="", extensions=(".wav",), rank=None, world=None, streams=2, ahead=3, stats=None,
                        skip_existing=False, seed=None, output_sample_rate=None, resample_on_device=False, loudness=None,
                        peak_ceiling=-1.0, true_peak=False, channels=None, channel_weights=None, limiter=False,
-                       limiter_lookahead_ms=3.0):
+                       limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf", dither_seed=0):
         """Folder inference (the reference's CLI loop, voicefixer/__main__.py:176-212: every ``*.wav`` of
         ``infolder`` -> same file name in ``outfolder``), batched, pipelined and -- with ``world`` > 1 -- sharded over
         one process per GPU (BASELINE configs[2] and [3]).
@@ -1264,6 +1356,11 @@ class VoiceFixer(nn.Module):
         at scan time; the channels of a file are adjacent rows of one batch (a file weighs C rows in the planning and C * n
         in the deal over ranks; a file with more channels than ``batch_size`` fails alone), ``loudness`` is one linked gain
         per file (``restore_inmem``) and ``stats["loudness"]`` / ``stats["true_peak"]`` keep one entry per file.
+        ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the outputs are reduced to 16- or 24-bit PCM on the device,
+        cross to the host as PCM and are written at that depth (``audio_io.save_pcm``: WAV or FLAC) -- the encode workers no
+        longer convert anything; ``stats["word_length"]`` lists ``(output name, bits, clipped samples, peak after in dBFS)`` per
+        output (a file of several channels: the sum of its rows' clipped counts, the largest of their peaks).  None (default):
+        float32 rows cross and ``audio_io.save_wave`` truncates them to 16 bits, as the reference does.
         Returns the list of file names THIS rank wrote."""
         import threading
         import time
@@ -1272,7 +1369,7 @@ class VoiceFixer(nn.Module):
         from . import dist as vdist, flac
         self._check_mode(mode, seed)
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, mode, seed, limiter,
-                      limiter_lookahead_ms)
+                      limiter_lookahead_ms, bit_depth, dither, dither_seed)
         rate_out = job.rate_out
         channels = _check_channels(channels)
         multi = channels == "all"
@@ -1369,7 +1466,9 @@ class VoiceFixer(nn.Module):
             final = os.path.join(outfolder, names[i])
             part = os.path.join(outfolder, ".part-%d-%s" % (os.getpid(), names[i]))   # (same extension: save_wave picks the container from it)
             try:
-                if multi:
+                if job.bit_depth is not None:      # (row is PCM already: straight into the container)
+                    audio_io.save_pcm(row, part, rate_out, job.bit_depth, channels_first=True)
+                elif multi:
                     audio_io.save_wave(row, part, rate_out, channels_first=True)
                 else:
                     audio_io.save_wave(row, part, rate_out)
@@ -1385,6 +1484,7 @@ class VoiceFixer(nn.Module):
         loud_rows = {}         # index -> (LUFS before, gain in dB)
         tp_rows = {}           # index -> (dBTP before, dBTP after)
         lim_rows = {}          # index -> (largest gain reduction in dB, trim in dB, peak after in dB)
+        word_rows = {}         # index -> (bits, clipped samples, peak after in dBFS)
         with ThreadPoolExecutor(max_workers=io_threads) as pool:
             scanned = list(pool.map(scan, range(len(files))))
             # every rank must deal from the SAME list: inside an initialised process group of this world size the scans are
@@ -1500,7 +1600,14 @@ class VoiceFixer(nn.Module):
                 for idx, out_host, lens_out, *extra in self._restore_batches_isolated(decoded(), dev_failed, your_vocoder_func,
                                                                                        streams, mode, **job.kwargs()):
                     ov = out_host.numpy()
-                    if extra:
+                    if job.bit_depth is not None:      # (the last field: {clipped, max |q|} per ROW)
+                        from . import wordlength
+                        qv, row0 = extra[-1].numpy(), rows_of(idx)
+                        for r, i in enumerate(idx):
+                            rows = qv[row0[r]:row0[r + 1]]
+                            word_rows[i] = (job.bit_depth, int(rows[:, 0].sum()),
+                                            wordlength.peak_db(int(rows[:, 1].max()), job.bit_depth))
+                    if job.loudness is not None:
                         lv = extra[0].numpy()
                         for r, i in enumerate(idx):
                             if lv.shape[1] == 8:              # the limiter's record (loudness.py)
@@ -1541,6 +1648,8 @@ class VoiceFixer(nn.Module):
                 stats["true_peak"] = sorted((names[i],) + tp_rows[i] for i in done if i in tp_rows)
             if job.limiter:
                 stats["limiter"] = sorted((names[i],) + lim_rows[i] for i in done if i in lim_rows)
+            if job.bit_depth is not None:
+                stats["word_length"] = sorted((names[i],) + word_rows[i] for i in done if i in word_rows)
         return sorted(written)
 
     @staticmethod
@@ -1549,16 +1658,18 @@ class VoiceFixer(nn.Module):
 
     def restore(self, input, output, cuda=False, mode=0, your_vocoder_func=None, seed=None, output_sample_rate=None,
                 resample_on_device=False, loudness=None, peak_ceiling=-1.0, true_peak=False, channels=None,
-                channel_weights=None, limiter=False, limiter_lookahead_ms=3.0):
+                channel_weights=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None, dither="tpdf", dither_seed=0):
         """File -> file (voicefixer/base.py:140-146).  ``resample_on_device`` (extension): the input is decoded at its own
         rate and converted on the device (``restore_inmem(sample_rate=...)``; ratios the device does not take are still
         resampled on the host); ``output_sample_rate``: the file is written at that rate (converted on the device);
         ``loudness`` / ``peak_ceiling`` / ``true_peak`` / ``limiter`` / ``limiter_lookahead_ms``: as ``restore_inmem``.
         ``channels`` (extension): None or "mix": a file
         of several channels is averaged to one (the reference's ``librosa.load``); "first": its first channel; "all": every
-        channel is restored (``restore_inmem(channels="all")``) and the output has the input's channel count."""
+        channel is restored (``restore_inmem(channels="all")``) and the output has the input's channel count.
+        ``bit_depth`` / ``dither`` / ``dither_seed``: as ``restore_inmem``; the file is written at that depth
+        (``audio_io.save_pcm``).  None (default): 16 bits, truncated by ``audio_io.save_wave`` as the reference does."""
         job = _Output(output_sample_rate, loudness, peak_ceiling, true_peak, channel_weights, limiter=limiter,
-                      limiter_lookahead_ms=limiter_lookahead_ms)
+                      limiter_lookahead_ms=limiter_lookahead_ms, bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)
         channels = _check_channels(channels)
 
         per_channel = channels in ("first", "all")
@@ -1572,11 +1683,16 @@ class VoiceFixer(nn.Module):
         kw = {"channels": "all", "channel_weights": channel_weights} if channels == "all" else {}
         if job.limiter:
             kw.update(limiter=True, limiter_lookahead_ms=job.limiter_lookahead_ms)
+        if job.bit_depth is not None:
+            kw.update(bit_depth=job.bit_depth, dither=job.dither, dither_seed=job.dither_seed)
         out_np_wav = self.restore_inmem(np.ascontiguousarray(x, dtype=np.float32), cuda=cuda, mode=mode,
                                         your_vocoder_func=your_vocoder_func, seed=seed, sample_rate=sr,
                                         output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
                                         true_peak=true_peak, **kw)
         # (channels_first: what came back is (C, N') whatever its sizes; for one channel this is what the default does)
+        if job.bit_depth is not None:
+            audio_io.save_pcm(out_np_wav, output, job.rate_out, job.bit_depth, channels_first=True)
+            return
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=job.rate_out, channels_first=True)
 
 
@@ -1639,12 +1755,15 @@ class RestoreSession:
     stretches, which therefore never visit the host).  Held between calls: the 44.1 kHz samples from the next chunk's
     start on, one overlap, two filter windows -- O(chunk + the largest block), whatever has been pushed.  A chunk is
     settled once more than chunk + min_tail samples (1024; mode 1: 1535) beyond its start are known at 44.1 kHz: the
-    session's latency.  Loudness normalisation and a true-peak ceiling need the whole file and are not offered here.
+    session's latency.  Loudness normalisation and a true-peak ceiling need the whole file and are not offered here; the
+    word-length reduction (``bit_depth``) is: its dither is a function of a sample's position, not of the file.
     A context manager; leaving it without ``finish`` discards what is pending."""
 
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
-                 sample_rate=44100, output_sample_rate=None):
+                 sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0):
         _check_stream_mode(mode, "open_stream")
+        self._word = _Output(bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)     # (checks the three)
+        self._dtype = {None: np.float32, 16: np.int16, 24: np.int32}[self._word.bit_depth]
         self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
         for r in (self._rate_in, self._rate_out):
             if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
@@ -1686,7 +1805,7 @@ class RestoreSession:
         if block.ndim != 1:
             raise ValueError("push: a block is a 1-D array of samples (got shape %r)" % (block.shape,))
         if block.shape[0] == 0:
-            return np.zeros((1, 0), np.float32)
+            return np.zeros((1, 0), self._dtype)
         pipe = self._vf._get_pipe()
         x = torch.from_numpy(np.ascontiguousarray(block)).to(pipe.device)
         self._n_in += block.shape[0]
@@ -1748,13 +1867,17 @@ class RestoreSession:
         return out
 
     def _deliver(self, pipe, stretches, at_end):
-        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs."""
+        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs and, with a
+        ``bit_depth``, through the word-length reduction: sample k of what is delivered has the absolute index position + k."""
         if self._conv_out is not None:
             stretches = [self._conv_out.feed(y) for y in stretches if y.numel()]
             if at_end:
                 stretches.append(self._conv_out.finish(pipe.device))
         if not stretches:
-            return np.zeros((1, 0), np.float32)
-        y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches)).cpu().numpy()[None]
+            return np.zeros((1, 0), self._dtype)
+        y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches))[None]
+        if self._word.bit_depth is not None and y.shape[1] > 0:
+            y, _ = self._word.quantize(y, [y.shape[1]], None, self.position)
+        y = y.cpu().numpy().astype(self._dtype, copy=False)
         self.position += y.shape[1]
         return y

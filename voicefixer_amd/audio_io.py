@@ -54,6 +54,65 @@ def save_wave(frames, fname, sample_rate=SR, channels_first=False):
     wavfile.write(fname, sample_rate, pcm if pcm.shape[1] > 1 else pcm[:, 0])
 
 
+def _write_wav24(fname, pcm, sample_rate):
+    """int (N, channels) inside the signed 24-bit range -> RIFF/WAVE with packed 3-byte little-endian samples: a plain PCM
+    ``fmt `` chunk for one or two channels, WAVE_FORMAT_EXTENSIBLE (sub-format PCM, no speaker positions assigned) for more."""
+    n, nch = pcm.shape
+    raw = np.ascontiguousarray(pcm, dtype="<i4").view(np.uint8).reshape(n, nch, 4)[:, :, :3].tobytes()
+    align = 3 * nch
+    if nch <= 2:
+        fmt = struct.pack("<HHIIHH", 1, nch, sample_rate, sample_rate * align, align, 24)
+    else:
+        pcm_guid = b"\x01\x00\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"
+        fmt = struct.pack("<HHIIHHHHI", 0xFFFE, nch, sample_rate, sample_rate * align, align, 24, 22, 24, 0) + pcm_guid
+    pad = b"\x00" * (len(raw) & 1)
+    if 4 + 8 + len(fmt) + 8 + len(raw) + len(pad) > 0xFFFFFFFF:
+        raise RuntimeError("too long for a RIFF/WAVE file (4 GB): %s" % fname)
+    with open(fname, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 4 + 8 + len(fmt) + 8 + len(raw) + len(pad)) + b"WAVE")
+        f.write(b"fmt " + struct.pack("<I", len(fmt)) + fmt)
+        f.write(b"data" + struct.pack("<I", len(raw)))
+        f.write(raw)
+        f.write(pad)
+
+
+def save_pcm(pcm, fname, sample_rate, bit_depth, channels_first=False):
+    """Integer PCM (what the restore calls return with ``bit_depth=``: int16 at 16 bits, int32 at 24) -> WAV or FLAC of that
+    depth by extension, sample for sample: nothing is scaled, rounded or truncated here (``save_wave`` is the float path and
+    stays the reference's).  Shapes as ``save_wave``: (N,), (1, N), (2, N), or with ``channels_first`` (channels, N), 1..8
+    channels.  Values outside the signed ``bit_depth``-bit range raise ValueError."""
+    from . import wordlength
+    bit_depth = wordlength.check_bit_depth(bit_depth)
+    pcm = np.asarray(pcm)
+    if pcm.dtype.kind != "i":
+        raise ValueError("save_pcm takes integer PCM (got %s); float waveforms go through save_wave" % pcm.dtype)
+    if channels_first:
+        if pcm.ndim != 2 or not 1 <= pcm.shape[0] <= 8:
+            raise ValueError("save_pcm: channels_first takes (channels, N) with 1..8 channels (got shape %r)" % (pcm.shape,))
+        pcm = pcm.T
+    elif pcm.ndim == 1:
+        pcm = pcm[..., None]
+    elif pcm.ndim == 2 and pcm.shape[0] < pcm.shape[1] and pcm.shape[0] <= 2:
+        pcm = pcm.T
+    if pcm.ndim != 2:
+        raise ValueError("save_pcm: PCM is (N,) or two-dimensional (got shape %r)" % (pcm.shape,))
+    if pcm.size and (pcm.min() < -(1 << (bit_depth - 1)) or pcm.max() > (1 << (bit_depth - 1)) - 1):
+        raise ValueError("save_pcm: samples outside the signed %d-bit range" % bit_depth)
+    low = str(fname).lower()
+    if low.endswith(".flac"):
+        from . import flac
+        flac.write(fname, pcm, sample_rate, bit_depth)
+        return
+    if not low.endswith(".wav"):
+        raise RuntimeError("output format not supported offline (WAV and FLAC are): %s" % fname)
+    if bit_depth == 16:
+        from scipy.io import wavfile
+        pcm = pcm.astype(np.int16)
+        wavfile.write(fname, sample_rate, pcm if pcm.shape[1] > 1 else pcm[:, 0])
+        return
+    _write_wav24(fname, pcm, int(sample_rate))
+
+
 def _riff_info(path, channels=False):
     """(sample_rate, frames, frames the header promises) of a RIFF/WAVE file from its ``fmt `` and ``data`` chunk headers alone
     -- any bit depth (scipy's memory-mapped read refuses 24-bit PCM, a very common studio format).  ``channels``: the channel

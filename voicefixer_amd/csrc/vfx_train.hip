@@ -10,6 +10,7 @@
 // Every kernel here is memory-bound; the scale / shift products are kept as scalar FMAs (Makefile: check_no_pk_fma
 // covers this object too).
 #include "vfx_common.h"
+#include "vfx_philox.h"      // philox4x32_10
 
 namespace {
 
@@ -188,20 +189,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         for (int i = 0; i < 4; ++i)
             if (l0 + i < valid) yp[i] = e[i];
     }
-}
-
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = M0 * ctr.x, hi0 = __umulhi(M0, ctr.x);
-        const uint32_t lo1 = M1 * ctr.z, hi1 = __umulhi(M1, ctr.z);
-        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-        key.x += W0;
-        key.y += W1;
-    }
-    return ctr;
 }
 
 // grid (ceil(T / 256), C / 4, B): thread (t, c4) draws philox((t * C + 4 c4) / 4, seg_b, layer, 0) once and masks the

@@ -532,6 +532,33 @@ def xfade(tail, head, fade, out):
     check(_lib.lib().vfx_xfade_f32(_ptr(tail), _ptr(head), _ptr(fade), n, _ptr(out), _stream()), "vfx_xfade_f32")
 
 
+def quantize_rows(x, n_rows, bit_depth, dither, seed, n0=None, chan=None, out=None):
+    """Word-length reduction on the device (vfx_quantize_rows_f32; wordlength.py is the specification): row r of x (B, >= max
+    n) holds n_rows[r] float samples (device int32 (B,)) and becomes ``bit_depth``-bit PCM -- int16 rows at 16, int32 rows at 24
+    -- with the dither ``dither`` ("none", "tpdf", "hp") of ``seed``.  ``n0`` (device int64 (B,), default 0): the absolute index
+    of every row's first sample in its file; ``chan`` (device int32 (B,), default 0): its channel (0..7).  Returns (out, result):
+    ``out`` (default: a new (B, width of x) tensor) is written up to every row's own length and nowhere else, ``result`` is a device
+    int32 (B, 2) of {clipped samples, max |q|}.  One kernel behind one clear of ``result``, no synchronisation."""
+    from . import dropout, wordlength
+    _need_cuda(x, n_rows, n0, chan, out)
+    bits, kind, seed = wordlength.check_bit_depth(bit_depth), wordlength.check_dither(dither), dropout.check_seed(seed)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == n_rows.numel()
+    assert n_rows.dtype == torch.int32 and n_rows.is_contiguous()
+    B, n_max = x.shape
+    assert n0 is None or (n0.dtype == torch.int64 and n0.is_contiguous() and n0.numel() == B)
+    assert chan is None or (chan.dtype == torch.int32 and chan.is_contiguous() and chan.numel() == B)
+    dtype = torch.int16 if bits == 16 else torch.int32
+    if out is None:
+        out = torch.empty((B, n_max), dtype=dtype, device=x.device)
+    assert out.dtype == dtype and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == B and out.shape[1] >= n_max
+    res = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+    check(_lib.lib().vfx_quantize_rows_f32(_ptr(x), x.stride(0) if B > 1 else n_max, _ptr(n_rows), B, n_max, _ptr(n0), _ptr(chan),
+                                           bits, wordlength.DITHERS.index(kind), seed, _ptr(out),
+                                           out.stride(0) if B > 1 else out.shape[1], _ptr(res), _stream()),
+          "vfx_quantize_rows_f32")
+    return out, res
+
+
 _LOUDNESS_MPOW = {}
 
 
