@@ -10,7 +10,9 @@ pin these statements against the oracle and the torch operators on the CPU, test
 tests/test_conv_taps_gpu.py hold the kernels to them.  Ragged batches are given as a list of per-row lengths; every function
 returns float64 CPU tensors.  The last sections are the yardsticks of tests/test_convwg4s_gpu.py and tests/test_convtw_gpu.py:
 the 3x3 convolution as a plain fp32 Winograd F(4,3) (conv2d_f43_f32) with the per-quad error figure, and the transposed 1-D
-convolution as a plain fp32 Winograd F(3,2) (convtr1d_f32_f32) -- the two functions here that return float32.
+convolution as a plain fp32 Winograd F(3,2) (convtr1d_f32_f32) -- functions that return float32.  tests/test_resblk4_gpu.py
+holds the fused C = 64 ResStack layer to ``resblock`` and measures its bound on ``resblock_f43_f32`` (two
+``conv1d_f43_f32``: the dilated 1-D convolution as a plain fp32 F(4,3)).
 """
 import torch
 
@@ -449,6 +451,79 @@ def convtr1d_f32_f32(x, w, bias=None, stride=2, lengths=None):
     if bias is not None:
         y = y + bias.to(f32).reshape(1, -1, 1)
     return y.contiguous()
+
+
+# --------------------------------------------------------------------------------------
+# one ResStack layer, and the dilated 1-D convolution as Winograd F(4,3) in fp32 (the yardstick of resblk4_kernel / resblk4s_kernel)
+# --------------------------------------------------------------------------------------
+def resblock(x, w1, b1, w2, b2, dilation, slope=0.01, post=POST_NONE, post_slope=0.0, lengths=None, magnitude=False):
+    """vfx_resblock_f32 / vfx_resblock_wino4_f32: post(x + b2 + conv_k3_d1(lrelu(b1 + conv_k3_dil(lrelu(x))))), both
+    convolutions zero-padded at the row's own ends, as two conv1d.  x (B, C, L), w1 / w2 (C, C, 3) -> (B, C, L) float64.
+    `magnitude=True`: M = |x| + |b2| + sum |w2| mag1 with mag1 = sum |w1| |lrelu(x)| + |b1| the first convolution's own
+    magnitude (zero outside the row): the first-order size of what one relative rounding error per partial sum of
+    either convolution can do to an output (|lrelu(v)| <= |v|, and the leaky ReLU's slope is at most 1)."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: resblock(xb, w1, b1, w2, b2, dilation, slope, post, post_slope, None, magnitude),
+                        x, None, lengths, lambda n: n)
+    mid = conv1d(x, w1, b1, None, dilation, pre=PRE_LRELU, pre_slope=slope, magnitude=magnitude)
+    if magnitude:
+        return conv1d(mid, w2, b2, x, 1, magnitude=True)
+    return conv1d(mid, w2, b2, x, 1, pre=PRE_LRELU, pre_slope=slope, post=post, post_slope=post_slope)
+
+
+def _f43_weights_1d(w, dtype):
+    """U = G w along the taps, formed in float64 and rounded once to `dtype` (as packing.pack_wino4 does):
+    w (Cout, Cin, 3) -> (6 planes, Cout, Cin)."""
+    g0, g1, g2 = (w[:, :, t].to(torch.float64) for t in range(3))
+    return torch.stack([g0 / 4, -(g0 + g1 + g2) / 6, -(g0 - g1 + g2) / 6, g0 / 24 + g1 / 12 + g2 / 6,
+                        g0 / 24 - g1 / 12 + g2 / 6, g2]).to(dtype)
+
+
+def conv1d_f43_f32(x, w, bias=None, res=None, dilation=1, pre=PRE_NONE, pre_slope=0.0, post=POST_NONE, post_slope=0.0,
+                   lengths=None, dtype=torch.float32):
+    """conv1d (k = 3, zero padding) computed in `dtype` as dilated Winograd F(4,3) with the standard matrices (the header of
+    voicefixer_amd/csrc/vfx_convwg.inc writes them out): a quad is four outputs a dilation apart, positions
+    4d blk + i d + r (i = 0 .. 3); its six inputs are d_j = pre(x)[4d blk + r + (j - 1) d]; V = B^T d, six planes
+    m_p = sum_c U_p V_p (one chain over the channels), y = A^T m, then bias, residual and the post-activation.  Every
+    operation is separately rounded.  The reference yardstick, not a model of a kernel.  x (B, Cin, L), w (Cout, Cin, 3)
+    -> (B, Cout, L) of `dtype` (NaN past a row's own end when `lengths` is given)."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: conv1d_f43_f32(xb, w, bias, rb, dilation, pre, pre_slope, post, post_slope, None,
+                                                      dtype).double(), x, res, lengths, lambda n: n).to(dtype)
+    assert w.shape[2] == 3 and pre in (PRE_NONE, PRE_LRELU)
+    B, Cin, L = x.shape
+    dl = dilation
+    xa = x.to(dtype)
+    if pre == PRE_LRELU:
+        xa = torch.where(xa > 0, xa, xa * torch.tensor(float(pre_slope), dtype=dtype))
+    nblk = (L + 4 * dl - 1) // (4 * dl)
+    xp = torch.zeros((B, Cin, (4 * nblk + 2) * dl), dtype=dtype)
+    xp[:, :, dl:dl + L] = xa
+    d = xp.reshape(B, Cin, 4 * nblk + 2, dl).unfold(2, 6, 4)        # (B, Cin, nblk, d, 6): positions 4d blk + r + (j - 1) d
+    d0, d1, d2, d3, d4, d5 = (d[..., j] for j in range(6))
+    V = [4 * d0 - 5 * d2 + d4, -4 * d1 - 4 * d2 + d3 + d4, 4 * d1 - 4 * d2 - d3 + d4,
+         -2 * d1 - d2 + 2 * d3 + d4, 2 * d1 - d2 - 2 * d3 + d4, 4 * d1 - 5 * d3 + d5]
+    U = _f43_weights_1d(w, dtype)
+    m = [torch.einsum("nc,bckr->bnkr", U[p], V[p]) for p in range(6)]
+    y = torch.stack([m[0] + m[1] + m[2] + m[3] + m[4], m[1] - m[2] + 2 * (m[3] - m[4]), m[1] + m[2] + 4 * (m[3] + m[4]),
+                     m[1] - m[2] + 8 * (m[3] - m[4]) + m[5]], dim=3)           # (B, Cout, nblk, 4, d)
+    y = y.reshape(B, w.shape[0], 4 * nblk * dl)[:, :, :L]
+    if bias is not None:
+        y = y + bias.to(dtype).reshape(1, -1, 1)
+    if res is not None:
+        y = y + res.to(dtype)
+    return conv_post(y, post, post_slope).contiguous()
+
+
+def resblock_f43_f32(x, w1, b1, w2, b2, dilation, slope=0.01, post=POST_NONE, post_slope=0.0, lengths=None,
+                     dtype=torch.float32):
+    """resblock as two conv1d_f43_f32: the dilated half, its result rounded to `dtype` (and, every row being taken alone,
+    absent outside the row: the second half's zero padding), then the dilation-1 half with x as the residual."""
+    if lengths is not None:
+        return _by_rows(lambda xb, rb: resblock_f43_f32(xb, w1, b1, w2, b2, dilation, slope, post, post_slope, None,
+                                                        dtype).double(), x, None, lengths, lambda n: n).to(dtype)
+    mid = conv1d_f43_f32(x, w1, b1, None, dilation, PRE_LRELU, slope, dtype=dtype)
+    return conv1d_f43_f32(mid, w2, b2, x, 1, PRE_LRELU, slope, post, post_slope, dtype=dtype)
 
 
 def quad_figure(got, ref, mag, lipschitz=1.0):

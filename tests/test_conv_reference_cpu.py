@@ -386,3 +386,128 @@ def test_convtr1d_f32_f32_zero_weights_return_the_bias(s):
         for b, n in enumerate(lengths or [Lin] * B):
             assert torch.equal(got[b, :, :n * s], bias.reshape(-1, 1).expand(Cout, n * s))
             assert torch.isnan(got[b, :, n * s:]).all()
+
+
+# --------------------------------------------------------------------------------------
+# one ResStack layer: the float64 statement and the fp32 F(4,3) statements (the yardstick of tests/test_resblk4_gpu.py)
+# --------------------------------------------------------------------------------------
+RB_DILATIONS = [1, 3, 27, 81]
+
+
+def _rb_operands(C, B, L, seed, bias=True):
+    x = _rand((B, C, L), seed)
+    w1, w2 = _rand((C, C, 3), seed + 1, (3 * C) ** -0.5), _rand((C, C, 3), seed + 2, (3 * C) ** -0.5)
+    b1, b2 = (_rand((C,), seed + 3, 0.3), _rand((C,), seed + 4, 0.3)) if bias else (None, None)
+    return x, w1, b1, w2, b2
+
+
+def _rb_lengths(d):
+    return [1, 5, 4 * d + 3]
+
+
+def _rb_torch(x, w1, b1, w2, b2, d, slope, post, post_slope, dtype):
+    """The layer as torch's own operators in `dtype`, one row."""
+    c = lambda t: None if t is None else t.to(dtype)
+    mid = F.conv1d(F.leaky_relu(c(x), slope), c(w1), c(b1), dilation=d, padding=d)
+    y = c(x) + F.conv1d(F.leaky_relu(mid, slope), c(w2), c(b2), padding=1)
+    return _post32(y, post, post_slope)
+
+
+@pytest.mark.parametrize("post", [ref64.POST_NONE, ref64.POST_LRELU, ref64.POST_LRELU_SNAKE])
+@pytest.mark.parametrize("d", RB_DILATIONS)
+def test_resblock_statement_equals_torch_in_float64(d, post):
+    """resblock against a float64 F.conv1d composition to 1e-12 of M, at L = 1, 5 and 4d + 3, plain and ragged (every row
+    alone); M is what conv1d(mag1, w2, b2, res=x, magnitude=True) returns and bounds the linear part."""
+    C, B = 12, 3
+    lens = _rb_lengths(d)
+    for bias in (True, False):
+        for L in lens:
+            x, w1, b1, w2, b2 = _rb_operands(C, B, L, 500 + d + L, bias)
+            got = ref64.resblock(x, w1, b1, w2, b2, d, 0.01, post, 0.2)
+            M = ref64.resblock(x, w1, b1, w2, b2, d, 0.01, magnitude=True)
+            want = _rb_torch(x, w1, b1, w2, b2, d, 0.01, post, 0.2, torch.float64)
+            assert got.dtype == torch.float64 and got.shape == want.shape == M.shape
+            assert ((got - want).abs() <= 1e-12 * M).all()
+            mag1 = ref64.conv1d(x, w1, b1, None, d, pre=ref64.PRE_LRELU, pre_slope=0.01, magnitude=True)
+            assert torch.equal(M, ref64.conv1d(mag1, w2, b2, x, 1, magnitude=True))
+            lin = ref64.resblock(x, w1, b1, w2, b2, d, 0.01)
+            assert (M >= lin.abs() - 1e-12).all()
+        Lmax = max(lens)
+        x, w1, b1, w2, b2 = _rb_operands(C, B, Lmax, 600 + d, bias)
+        for mag in (False, True):
+            rag = ref64.resblock(x, w1, b1, w2, b2, d, 0.01, post, 0.2, lengths=lens, magnitude=mag)
+            for b, n in enumerate(lens):
+                alone = ref64.resblock(x[b:b + 1, :, :n], w1, b1, w2, b2, d, 0.01, post, 0.2, magnitude=mag)
+                assert torch.equal(rag[b:b + 1, :, :n], alone) and torch.isnan(rag[b, :, n:]).all()
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["plain", "ragged"])
+@pytest.mark.parametrize("d", RB_DILATIONS)
+def test_f43_statements_are_the_layer_in_float64(d, ragged):
+    """Run with dtype = float64 (U = G w then unrounded), conv1d_f43_f32 meets conv1d and resblock_f43_f32 meets resblock
+    to 1e-12 of the magnitude: the statement is algebraically the layer -- quads, taps, matrices, padding at the row's own
+    ends, bias and residual after the output transform."""
+    C, B = 10, 3
+    lens = _rb_lengths(d)
+    for L in ([max(lens)] if ragged else lens):
+        x, w1, b1, w2, b2 = _rb_operands(C, B, L, 700 + d + L)
+        kw = dict(lengths=lens) if ragged else {}
+        ok = None
+        for post in (ref64.POST_NONE, ref64.POST_LRELU_SNAKE):
+            got = ref64.resblock_f43_f32(x, w1, b1, w2, b2, d, 0.01, post, 0.2, dtype=torch.float64, **kw)
+            ref = ref64.resblock(x, w1, b1, w2, b2, d, 0.01, post, 0.2, **kw)
+            M = ref64.resblock(x, w1, b1, w2, b2, d, 0.01, magnitude=True, **kw)
+            ok = ~torch.isnan(ref)
+            assert got.dtype == torch.float64 and torch.equal(torch.isnan(got), ~ok) and bool(ok.any())
+            assert ((got - ref).abs()[ok] <= 1e-12 * ref64.post_lipschitz(post) * M[ok]).all()
+        # one convolution alone, with a residual and no pre-activation
+        res = _rand((B, C, L), 9)
+        got = ref64.conv1d_f43_f32(x, w1, b1, res, d, dtype=torch.float64, **kw)
+        ref = ref64.conv1d(x, w1, b1, res, d, **kw)
+        mag = ref64.conv1d(x, w1, b1, res, d, magnitude=True, **kw)
+        assert ((got - ref).abs()[ok] <= 1e-12 * mag[ok]).all()
+
+
+@pytest.mark.parametrize("gains", ["unit", "heavy"])
+@pytest.mark.parametrize("d", RB_DILATIONS)
+def test_resblock_f43_f32_figure_next_to_torchs_direct_operator(d, gains):
+    """At fp32 and C = 64 the statement's figure |. - ref| / (M + |ref|) is printed next to that of torch's direct fp32
+    operators; with `heavy` both convolutions carry log-normal output gains and unit-scale biases, as tests/test_resblk4_gpu.py
+    draws them.  The statement returns float32, NaN exactly past a row's own end, and is held to what an fp32 evaluation
+    can be expected to reach at all: 64 x 2^-23 of M (a wrong tap or constant is off by the order of M)."""
+    C, B, L = 64, 3, 4 * d + 3
+    lens = [L, 1, 5]
+    x, w1, b1, w2, b2 = _rb_operands(C, B, L, 800 + d)
+    if gains == "heavy":
+        g = torch.Generator().manual_seed(900 + d)
+        w1 = w1 * torch.exp(1.5 * torch.randn(C, generator=g) - 2.25).reshape(-1, 1, 1)
+        w2 = w2 * torch.exp(1.5 * torch.randn(C, generator=g) - 2.25).reshape(-1, 1, 1)
+        b1, b2 = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    got = ref64.resblock_f43_f32(x, w1, b1, w2, b2, d, lengths=lens)
+    ref = ref64.resblock(x, w1, b1, w2, b2, d, lengths=lens)
+    M = ref64.resblock(x, w1, b1, w2, b2, d, lengths=lens, magnitude=True)
+    assert got.dtype == torch.float32 and torch.equal(torch.isnan(got), torch.isnan(ref))
+    direct = torch.full(ref.shape, float("nan"))
+    for b, n in enumerate(lens):
+        direct[b:b + 1, :, :n] = _rb_torch(x[b:b + 1, :, :n], w1, b1, w2, b2, d, 0.01, ref64.POST_NONE, 0.0, torch.float32)
+    fs, fd = ref64.conv_error(got, ref, M), ref64.conv_error(direct, ref, M)
+    print("F43RB d%d %s: statement max %.3e rms %.3e, torch direct max %.3e rms %.3e" % (d, gains, fs[0], _rms(fs), fd[0], _rms(fd)))
+    assert fs[2] == fd[2] == C * sum(lens)
+    assert fs[0] <= 64 * ULP and fd[0] <= 64 * ULP
+
+
+def test_f43_weights_1d_are_the_packed_ones():
+    """U = G w of the statement holds bit for bit the values packing.pack_wino4 hands the kernels, once its blob
+    [6 planes][Cin / 8][Cout][8] is un-permuted (packing.pack_direct: position e of a group of 8 input channels is
+    channel (0, 2, 4, 6, 1, 3, 5, 7)[e])."""
+    from voicefixer_amd import packing
+    C = 16
+    w = _rand((C, C, 3), 41, 0.1)
+    U = ref64._f43_weights_1d(w, torch.float32)                            # (6, Cout, Cin)
+    blob = packing.pack_wino4(packing.pack_conv1d(w))                      # [6][Cin / 8][Cout][8]
+    assert blob.shape == (6, C // 8, C, 8)
+    lane_ci = torch.tensor([0, 2, 4, 6, 1, 3, 5, 7])
+    un = torch.empty_like(U)
+    for grp in range(C // 8):
+        un[:, :, grp * 8 + lane_ci] = blob[:, grp]
+    assert torch.equal(un, U)

@@ -25,7 +25,8 @@ def _describe(name, a):
     y, res, act = a.get("y"), a.get("res"), a.get("act")
     d = {"op": name, "B": x.shape[0]}
     if name in ("resblock", "resblock_wino4"):
-        d.update(cin=x.shape[1], cout=x.shape[1], L=a["L"], k=3, step=a["dilation"], pad="zero")
+        d.update(cin=x.shape[1], cout=x.shape[1], L=a["L"], k=3, step=a["dilation"], pad="zero", slope=a["slope"],
+                 post_slope=a["post_slope"], bias_pair=(a["b1"] is not None, a["b2"] is not None))
     else:
         d.update(cin=x.shape[1] if a.get("cin") is None else a["cin"], cout=w.shape[2])
     if name == "conv1d":
@@ -92,6 +93,11 @@ class LaunchRecorder:
     def tw(self):
         """The records that ran on convtw_kernel (code 83: the Winograd F(3,2) transposed convolution of the UpsampleNet)."""
         return [r for r in self.records if r["code"] == 83]
+
+    def rb4(self):
+        """The records that ran on resblk4_kernel / resblk4s_kernel (codes 96 / 97: one whole C = 64 ResStack layer, both
+        halves Winograd F(4,3), on the block tile / the strip tile)."""
+        return [r for r in self.records if r["code"] in (96, 97)]
 
 
 def split_k(rec):
