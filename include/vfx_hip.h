@@ -541,6 +541,35 @@ int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const int32_t* n_ro
                            int c, float* out, int64_t out_stride, int H, int true_peak, double* result, void* ws,
                            size_t ws_bytes, vfx_stream_t stream);
 
+/* ---- fixed-gain look-ahead limiter of a streaming session: the span form ------------------------------------- */
+
+/* Bytes of the workspace of vfx_limit_span_f32 for spans of up to n_span outputs at look-ahead H (0 on bad arguments: n_span < 0
+ * or > 2^30, H outside [1, 4096]): 4 bytes per output and per sample of the 4 H around the span, a few values per tile of 1024. */
+size_t vfx_limit_span_workspace_bytes(int64_t n_span, int H);
+
+/* Outputs [m0, m1) of the fixed-gain limiter F over ONE row of n_total samples (INT64_MAX: the row's end is not known yet) from
+ * the window xw[k] = x[g0 + k], k < wlen; out[n - m0] receives output n.  F is the bound branch of vfx_loudness_limit_f32 with
+ * a GIVEN gain and without the trim: gL = gain (linear, finite, > 0), Cl = 10^(ceiling_db/20), thr = (float)(Cl / gL),
+ *   e[n] = max(|x[n]|, the R interpolated values in (n - 1, n]) (R = 1: |x[n]|; those behind the last sample go to n_total - 1,
+ *   once n_total is known);  c[n] = e[n] > thr ? thr / e[n] : 1;  m[n] = min c[j], |j - n| <= H inside the row;
+ *   g[n] = min(c[n], 1 - sum_{|k| <= H} w[k] (1 - m[clamp(n + k, 0, n_total - 1)])), fp32, ascending k (the exact sum never
+ *   exceeds c[n]; the minimum takes the chain's rounding out, so that |out[n]| <= Cl to two roundings);  out = x * ((float)gL * g[n]).
+ * Every value is a function of global positions, clipped and clamped against [0, n_total), never against the window: output n
+ * has the bits the single span [0, n_total) writes for it, whatever the split, the window or g0.  While the end is unknown,
+ * outputs below n_known - 2 H - Fw are final (n_known: the samples seen so far).  The window must cover
+ *   [max(0, m0 - 2 H - Bk), min(n_total - 1, m1 - 1 + 2 H + Fw)],   Fw = c / R, Bk = J - 1 - c / R  (both 0 at R = 1),
+ * and nothing outside the window is read.  bank / J / c: the R-phase interpolator of vfx_loudness_tp_rows_f32 (R = 1: not read,
+ * may be NULL).  record: device float64[2] = {min g, max |out|} over [m0, m1).  ws: >= vfx_limit_span_workspace_bytes(m1 - m0,
+ * H) bytes, 16-byte aligned.  Three launches (envelope, limit, fold) whatever the span; no host synchronisation.
+ * An empty span (m0 == m1) is VFX_OK, launches nothing and leaves record alone (its value is {1, 0}).
+ * VFX_EINVAL, nothing launched: a NULL xw, out, record or ws; g0, wlen, m0 < 0, m0 > m1, m1 > n_total, m1 - m0 > 2^30; a window
+ * that does not cover the range above; H outside [1, 4096]; R not in {1, 2, 4}; at R > 1 a NULL bank, J outside [1, 2048] or c
+ * outside [0, R J); a gain that is not finite and positive, a ceiling that is not finite; ws too small or misaligned; out
+ * overlapping xw. */
+int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0, int64_t m1, double gain,
+                       double ceiling_db, int H, const float* bank, int J, int R, int c, float* out, double* record, void* ws,
+                       size_t ws_bytes, vfx_stream_t stream);
+
 /* ---- word-length reduction: 16- / 24-bit PCM with seeded dither (voicefixer_amd/wordlength.py) ----------------- */
 
 /* The last stage of the output chain (the reference's save_wave truncates to int16 on the host, voicefixer/tools/wav.py:27-34;

@@ -6,6 +6,11 @@
 
 Median of --repeats runs each (alternating), the session's device-memory high-water mark above what the model holds, and
 the time from the first push to the first non-empty result.  Prints one JSON line.
+
+--limiter: the cost of the session's fixed-gain look-ahead limiter instead.  The signal gets one impulse per
+second and the gain is set from the plain session's output so that every output chunk is bound; the plain session and the
+session with gain_db and limiter=True (true peak) run alternating in one process, median of --repeats with the spread, and
+one ops.limit_span call over one second of output is timed with HIP events.
 """
 import argparse
 import json
@@ -21,6 +26,68 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from voicefixer_amd import VoiceFixer, api, weights, _lib  # noqa: E402
 
 
+def _spread(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts), "all": ts}
+
+
+def limiter_leg(args, vf, wav, blk):
+    from voicefixer_amd import loudness, ops
+    cs, ov, rate = args.chunk_seconds, args.overlap_seconds, args.output_sample_rate
+    n = len(wav)
+
+    def session(**kw):
+        outs = []
+        with vf.open_stream(cs, ov, batch_size=1, output_sample_rate=rate, **kw) as s:
+            for a in range(0, n, blk):
+                outs.append(s.push(wav[a:a + blk]))
+            outs.append(s.finish())
+            stats = s.limiter_stats
+        return np.concatenate(outs, axis=1), stats
+
+    Z, _ = session()                      # warm-up, and the level the gain is set from
+    step = int(cs * rate)
+    peaks = [float(np.abs(Z[0, a:a + step]).max()) for a in range(0, Z.shape[1], step)]
+    ceiling = -1.0
+    gain_db = 20.0 * np.log10(10.0 ** (ceiling / 20.0) / min(peaks)) + 6.0     # the quietest chunk's peak 6 dB over the ceiling
+    kw = dict(gain_db=float(gain_db), limiter=True, peak_ceiling=ceiling, true_peak=True)
+    lim, stats = session(**kw)
+    per_chunk = [float(np.abs(lim[0, a:a + step]).max()) for a in range(0, lim.shape[1], step)]
+    t_plain, t_lim = [], []
+    for _ in range(args.repeats):
+        for ts, k in ((t_plain, {}), (t_lim, kw)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            session(**k)
+            ts.append(time.perf_counter() - t0)
+    # one ops.limit_span call over one second of output, HIP events
+    H, Bk, Fw = loudness.limiter_reach(rate, 3.0, True)
+    dev = vf._get_pipe().device
+    row = torch.from_numpy(np.ascontiguousarray(Z[0, :3 * rate])).to(dev)
+    out = torch.empty((rate,), dtype=torch.float32, device=dev)
+    m0 = rate
+    lo, hi = m0 - 2 * H - Bk, m0 + rate + 2 * H + Fw
+    call = lambda: ops.limit_span(row[lo:hi], lo, None, rate, float(gain_db), m0, m0 + rate, out, ceiling, True, 3.0)
+    for _ in range(3):
+        call()
+    ev = []
+    for _ in range(20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1) * 1e-3)
+    mp, ml = statistics.median(t_plain), statistics.median(t_lim)
+    res = {"leg": "limiter", "minutes": args.minutes, "block_seconds": args.block_seconds, "chunk_seconds": cs, "overlap_seconds": ov,
+           "output_sample_rate": rate, "repeats": args.repeats, "gain_db": float(gain_db), "peak_ceiling": ceiling,
+           "every_chunk_bound": bool(min(peaks) * 10.0 ** (gain_db / 20.0) > 10.0 ** (ceiling / 20.0)),
+           "chunk_peaks_out_db": [20.0 * np.log10(p) for p in per_chunk], "limiter_stats": stats,
+           "plain_s": _spread(t_plain), "limiter_s": _spread(t_lim), "limiter_over_plain": ml / mp - 1.0,
+           "limit_span_1s_call_s": _spread(ev), "device": torch.cuda.get_device_name(dev),
+           "build_id": _lib.lib().vfx_build_id().decode()}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=5.0)
@@ -29,6 +96,7 @@ def main():
     ap.add_argument("--overlap-seconds", type=float, default=1.0)
     ap.add_argument("--output-sample-rate", type=int, default=48000)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--limiter", action="store_true", help="measure the fixed-gain limiter of the session against the plain session")
     args = ap.parse_args()
     n = int(args.minutes * 60 * 44100)
     rng = np.random.default_rng(0)
@@ -38,6 +106,10 @@ def main():
     vf = VoiceFixer.from_state(weights.seeded_vocoder_state(1234), weights.seeded_restorer_state(4321))
     dev = vf._get_pipe().device
     cs, ov, rate = args.chunk_seconds, args.overlap_seconds, args.output_sample_rate
+
+    if args.limiter:
+        wav[::44100] = 0.9
+        return limiter_leg(args, vf, wav, blk)
 
     def two_step():
         y44 = vf.restore_stream(wav, cs, ov, batch_size=1)

@@ -613,6 +613,57 @@ def quantize(wav, bit_depth=16, dither="tpdf", dither_seed=0):
     return out[0] if single else out
 
 
+LIMIT_SPAN = 1 << 22      # outputs per ops.limit_span call of ``limit``: bounds the scratch, changes no bit
+
+
+def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, sample_rate=44100, stats=None, _span=None):
+    """The fixed-gain look-ahead limiter F (loudness.py) on the device: a float32 array (N,) at ``sample_rate``
+    -- or every array of a list, each row on its own -- is multiplied by 10^(gain_db/20) and a gain curve that looks
+    ``lookahead_ms`` ahead holds every sample under ``peak_ceiling`` (dBFS; with ``true_peak=True`` the envelope includes the
+    interpolated values between the samples).  Nothing is measured and nothing is trimmed afterwards: this is what a streaming
+    session (``open_stream(gain_db=..., limiter=True)``) applies, bit for bit, and the inter-sample peak of the result is bounded
+    only approximately -- lower ``peak_ceiling`` for a margin.  Where no sample within reach is above the ceiling the output is
+    float32(gL) x exactly.  ``stats``: a dict that receives {"max_reduction_db", "peak_out_db"} (lists of one value per row
+    when a list went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span."""
+    from . import loudness as ld, ops
+    gain_db = ld.check_gain(gain_db)
+    if gain_db is None:
+        raise ValueError("limit: gain_db must be a number (0.0: the limiter alone)")
+    peak_ceiling, true_peak = ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
+    rate = _check_rate(sample_rate)
+    H, Bk, Fw = ld.limiter_reach(rate, lookahead_ms, true_peak)
+    if stats is not None and not isinstance(stats, dict):
+        raise ValueError("stats must be a dict or None")
+    span = LIMIT_SPAN if _span is None else int(_span)
+    if span < 1:
+        raise ValueError("_span must be positive")
+    single = not isinstance(x, (list, tuple))
+    items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
+    for w in items:
+        if w.ndim != 1:
+            raise ValueError("limit: a row is a 1-D array of samples (got shape %r)" % (w.shape,))
+    outs, recs = [], []
+    dev = _device() if items else None
+    for w in items:
+        n = w.shape[0]
+        xd = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+        y = torch.empty((n,), dtype=torch.float32, device=dev)
+        rec = None
+        for m0 in range(0, n, span):
+            m1 = min(m0 + span, n)
+            lo, hi = max(m0 - 2 * H - Bk, 0), min(m1 + 2 * H + Fw, n)      # the minimal window, as a view of the row
+            r = ops.limit_span(xd[lo:hi], lo, n, rate, gain_db, m0, m1, y[m0:m1], peak_ceiling, true_peak, lookahead_ms)
+            rec = r if rec is None else torch.stack([torch.minimum(rec[0], r[0]), torch.maximum(rec[1], r[1])])
+        outs.append(y.cpu().numpy())
+        recs.append((1.0, 0.0) if rec is None else tuple(float(v) for v in rec.cpu().numpy()))
+    if stats is not None:
+        red = [-ld.to_db(g) + 0.0 for g, _ in recs]
+        pk = [ld.to_db(p) for _, p in recs]
+        stats["max_reduction_db"] = red[0] if single else red
+        stats["peak_out_db"] = pk[0] if single else pk
+    return outs[0] if single else outs
+
+
 class Vocoder(nn.Module):
     """44.1 kHz TFGAN-style universal vocoder (voicefixer/vocoder/base.py)."""
 
@@ -1232,22 +1283,32 @@ class VoiceFixer(nn.Module):
 
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                     sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
-                    dither="tpdf", dither_seed=0):
+                    dither="tpdf", dither_seed=0, gain_db=None, peak_ceiling=-1.0, true_peak=False):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
         returns for the concatenated blocks (converted to 44.1 kHz as a whole) with the same ``chunk_seconds``,
         ``overlap_seconds``, ``batch_size`` and ``mode`` -- bit for bit at ``batch_size=1`` -- converted as a whole to the
         output rate.  Modes 0 and 1; ``mode=2`` raises NotImplementedError.  The arguments are checked here, before the
-        device is touched.  ``limiter=True`` raises NotImplementedError, as ``restore_stream`` does: a session
-        never sees the whole file.  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
+        device is touched.  ``gain_db`` (dB, [-60, 60]; default None: no level stage at all): a FIXED gain, float32(10^(gain_db/20))
+        times every output sample on the device; with ``limiter=True`` as well, the fixed-gain look-ahead limiter (loudness.py,
+        DESIGN.md 3.16) holds the peaks under ``peak_ceiling`` (dBFS, or dBTP with ``true_peak=True``) at the output rate, looking
+        ``limiter_lookahead_ms`` ahead, which delays the output by 2 H + 93 samples; ``session.limiter_stats`` reports what it
+        did.  ``peak_ceiling``, ``true_peak`` and ``limiter_lookahead_ms`` are checked always and used only there.  The limiter
+        bounds every SAMPLE by the ceiling; the inter-sample peak of the gain-modulated output is bounded only approximately and a
+        session cannot trim afterwards: lower ``peak_ceiling`` for a margin.  ``limiter=True`` without ``gain_db`` raises
+        NotImplementedError, as ``restore_stream`` does with any limiter: a loudness TARGET needs the whole file, and a session
+        never sees it (nor does it offer a trim, several channels or ``restore_stream``'s refusal lifted).  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
         on the device, each from the session's position on, so that all of them, concatenated, are the whole output quantised
         once; ``push`` and ``finish`` then return int16 / int32 arrays."""
-        if _check_limiter(limiter, limiter_lookahead_ms):
-            raise NotImplementedError("open_stream: the limiter is not built -- it follows a whole-file loudness measurement; use "
+        from . import loudness as ld
+        if _check_limiter(limiter, limiter_lookahead_ms) and ld.check_gain(gain_db) is None:
+            raise NotImplementedError("open_stream: the limiter behind a loudness target is not built -- it follows a whole-file "
+                                      "measurement; give a fixed gain (gain_db=...) for the session's fixed-gain limiter, or use "
                                       "restore_inmem or restore_folder")
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
-                              output_sample_rate, bit_depth, dither, dither_seed)
+                              output_sample_rate, bit_depth, dither, dither_seed, gain_db, peak_ceiling, true_peak, limiter,
+                              limiter_lookahead_ms)
 
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
@@ -1735,6 +1796,65 @@ class _SpanConverter:
         return y
 
 
+class _SpanLimiter:
+    """The fixed-gain look-ahead limiter F (loudness.py) of ONE row that arrives in pieces (ops.limit_span): ``feed`` takes the
+    next samples (device (k,)) and returns the outputs that became final with them (loudness.limiter_ready), ``finish`` the rest
+    with the row's end known.  Every output has the bits of one span over the whole row.  Kept between calls: the samples that
+    later outputs read (at most 4 H + Bk + Fw + 1 of them beyond a block) with their global offset, and the calls' records
+    {min g, max |out|} -- device scalars, folded exactly (min and max) and read by ``stats()`` only."""
+
+    def __init__(self, rate, gain_db, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0):
+        from . import loudness
+        self.rate, self.gain_db, self.ceiling, self.true_peak, self.ms = rate, gain_db, peak_ceiling, true_peak, lookahead_ms
+        self.H, self.Bk, self.Fw = loudness.limiter_reach(rate, lookahead_ms, true_peak)
+        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
+        self.g0 = 0
+        self.n_in = 0        # samples fed
+        self.m_done = 0      # outputs returned
+        self.recs = []       # device float64 (2,) each: {min g, max |out|} of the calls so far, folded when read
+
+    def feed(self, x):
+        from . import loudness
+        self.win = x if self.win is None else torch.cat([self.win, x])
+        self.n_in += x.numel()
+        return self._emit(loudness.limiter_ready(self.n_in, self.H, self.Fw), None)
+
+    def finish(self, device):
+        if self.win is None:
+            return torch.empty((0,), dtype=torch.float32, device=device)
+        return self._emit(self.n_in, self.n_in)
+
+    def _emit(self, m1, n_total):
+        from . import ops
+        m0, m1 = self.m_done, max(m1, self.m_done)
+        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
+        if m1 > m0:
+            rec = ops.limit_span(self.win, self.g0, n_total, self.rate, self.gain_db, m0, m1, y, self.ceiling, self.true_peak,
+                                 self.ms)
+            self.recs.append(rec)
+            if len(self.recs) >= 256:                         # (bounded, whatever the session's length)
+                self.recs = [self._fold()]
+        self.m_done = m1
+        # drop what no later output reads: output m1 reads from m1 - 2 H - Bk on (one sample always stays)
+        keep = min(max(m1 - 2 * self.H - self.Bk, 0), self.n_in - 1)
+        if keep > self.g0:
+            self.win = self.win[keep - self.g0:].clone()
+            self.g0 = keep
+        return y
+
+    def _fold(self):
+        r = torch.stack(self.recs)
+        return torch.stack([r[:, 0].min(), r[:, 1].max()])
+
+    def stats(self):
+        """{"max_reduction_db", "peak_out_db"} over what has been returned (reads the device record: the one synchronisation)."""
+        from . import loudness
+        if len(self.recs) > 1:
+            self.recs = [self._fold()]
+        gmin, peak = (float(v) for v in self.recs[0].cpu().numpy()) if self.recs else (1.0, 0.0)
+        return {"max_reduction_db": -loudness.to_db(gmin) + 0.0, "peak_out_db": loudness.to_db(peak)}
+
+
 class RestoreSession:
     """``VoiceFixer.open_stream``: the overlap-add long-form mode as a push-style session on the device.
 
@@ -1755,16 +1875,30 @@ class RestoreSession:
     stretches, which therefore never visit the host).  Held between calls: the 44.1 kHz samples from the next chunk's
     start on, one overlap, two filter windows -- O(chunk + the largest block), whatever has been pushed.  A chunk is
     settled once more than chunk + min_tail samples (1024; mode 1: 1535) beyond its start are known at 44.1 kHz: the
-    session's latency.  Loudness normalisation and a true-peak ceiling need the whole file and are not offered here; the
-    word-length reduction (``bit_depth``) is: its dither is a function of a sample's position, not of the file.
+    session's latency.  Loudness normalisation to a TARGET and a trim need the whole file and are not offered here (nor are
+    several channels); a FIXED gain (``gain_db``) is, alone or followed by the fixed-gain look-ahead limiter (``limiter=True``;
+    loudness.py) under ``peak_ceiling`` at the output rate, carried across stretches like the converters and
+    2 H + 93 samples late; ``limiter_stats`` is then {"max_reduction_db", "peak_out_db"} over what has been delivered (None
+    without a limiter).  The limiter bounds every sample by the ceiling, the inter-sample peak only approximately: lower
+    ``peak_ceiling`` for a margin.  The word-length reduction (``bit_depth``) is offered too: its dither is a function of a
+    sample's position, not of the file.  The stages behind the stitcher: output converter, gain / limiter, word length, host.
     A context manager; leaving it without ``finish`` discards what is pending."""
 
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
-                 sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0):
+                 sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0, gain_db=None,
+                 peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0):
+        from . import loudness as ld
         _check_stream_mode(mode, "open_stream")
         self._word = _Output(bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)     # (checks the three)
         self._dtype = {None: np.float32, 16: np.int16, 24: np.int32}[self._word.bit_depth]
         self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
+        gain_db, peak_ceiling, true_peak = ld.check_gain(gain_db), ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
+        limiter, limiter_lookahead_ms = ld.check_limiter(limiter, limiter_lookahead_ms)
+        if limiter and gain_db is None:
+            raise NotImplementedError("RestoreSession: limiter=True needs a fixed gain (gain_db=...)")
+        self._gain = None if gain_db is None else float(np.float32(10.0 ** (gain_db / 20.0)))
+        # (limiter_reach: ValueError for a look-ahead outside [1, 4096] samples at the output rate)
+        self._lim = _SpanLimiter(self._rate_out, gain_db, peak_ceiling, true_peak, limiter_lookahead_ms) if limiter else None
         for r in (self._rate_in, self._rate_out):
             if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
                 raise ValueError("open_stream: the device resampler does not take the ratio of %d Hz to 44100 Hz" % r)
@@ -1794,6 +1928,14 @@ class RestoreSession:
         """Drop what is pending (nothing more is delivered); ``push`` and ``finish`` raise afterwards."""
         self._closed = True
         self._buf = self._tail = self._fade = self._conv_in = self._conv_out = None
+        if self._lim is not None:
+            self._lim.win = None     # (the record stays: limiter_stats outlives the session)
+
+    @property
+    def limiter_stats(self):
+        """{"max_reduction_db": -20 log10(min g), "peak_out_db": 20 log10(max |out|)} over what has been delivered -- exact folds,
+        the values of one call over the whole row -- or None without a limiter."""
+        return None if self._lim is None else self._lim.stats()
 
     @torch.no_grad()
     def push(self, block):
@@ -1867,12 +2009,19 @@ class RestoreSession:
         return out
 
     def _deliver(self, pipe, stretches, at_end):
-        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs and, with a
-        ``bit_depth``, through the word-length reduction: sample k of what is delivered has the absolute index position + k."""
+        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs, the fixed gain or
+        the fixed-gain limiter when the session has one and, with a ``bit_depth``, through the word-length reduction: sample k of
+        what is delivered has the absolute index position + k."""
         if self._conv_out is not None:
             stretches = [self._conv_out.feed(y) for y in stretches if y.numel()]
             if at_end:
                 stretches.append(self._conv_out.finish(pipe.device))
+        if self._lim is not None:
+            stretches = [self._lim.feed(y) for y in stretches if y.numel()]
+            if at_end:
+                stretches.append(self._lim.finish(pipe.device))
+        elif self._gain is not None:
+            stretches = [y * self._gain for y in stretches]      # (float32(gL) y: one rounding per sample)
         if not stretches:
             return np.zeros((1, 0), self._dtype)
         y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches))[None]

@@ -900,3 +900,7 @@ extern "C" int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const in
     return lk_run(3, x, x_stride, n_rows, B, n_max, coef, mpow, S, hop, lookback, target, ceiling_db, bank, J, R, c, out,
                   out_stride, result, ws, ws_bytes, stream, G, group_start, weight, H);
 }
+
+/* ---- fixed-gain look-ahead limiter of a streaming session, span form -------------------------------------- */
+
+#include "vfx_limit_span.inc"

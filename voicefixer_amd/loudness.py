@@ -66,6 +66,25 @@ samples at fs, or per programme of linked channels, after the measurement above 
      same definition (the sample peak in the sample-peak mode, where t = 1 always); t = min(1, Cl / TPv); the output is t v.
   8. Result record per row or programme, device float64: {L, gL, P, TP, bound (0/1), min_n g[n], t, TPv t}; a row that is
      not bound records {L, gL, P, TP, 0, 1, 1, float32(gL) TP}.
+
+Fixed-gain limiter of a streaming session (``open_stream(gain_db=..., limiter=True)``, ``voicefixer_amd.limit``;
+``vfx_limit_span_f32``).  F is steps 2-6 above on one row x[0..N) at fs with a GIVEN gain
+gL = 10^(gain_db/20): nothing is measured, there is no bound test and no trim (step 7 needs the whole row).  R = R(fs) with
+``true_peak=True``, else 1; H = ``limiter_window(fs, lookahead_ms)[0]``; Cl = 10^(peak_ceiling/20); thr = float32(Cl / gL);
+c[n] = thr / e[n] where e[n] > thr, else 1; out[n] = x[n] (float32(gL) g[n]).  Hence
+
+  * where no sample within reach exceeds thr, g = 1 exactly and out = float32(gL) x, the bits of a plain product;
+  * |out[n]| <= Cl up to fp32 rounding (g[n] <= c[n] and e[n] >= |x[n]|).  The INTER-SAMPLE peak of a gain-modulated row is
+    bounded only approximately, and a session cannot trim: whoever needs a margin lowers ``peak_ceiling``.
+
+Output n depends on the input within 2 H + Bk behind and 2 H + Fw ahead of n: (H, Bk, Fw) = ``limiter_reach(fs, lookahead_ms,
+true_peak)``, Fw = c // R = 93 and Bk = J - 1 - c // R = 94 for both banks, 0 and 0 at R = 1.  The span form computes outputs
+[m0, m1) from a window of the row, every value a function of global positions, clipped and clamped against [0, N) only: the
+bits of the whole row, whatever the split.  Ready rule: with n_known samples seen and the end unknown, outputs
+[0, ``limiter_ready(n_known, H, Fw)``) = [0, max(0, n_known - 2 H - Fw)) are final whatever arrives later and whatever N turns
+out to be (m[j] is read for j <= n + H and reads c up to n + 2 H, whose interpolated values read x up to n + 2 H + Fw; the
+clamp at the row's end and the values behind the last sample change nothing below N - 1 - H >= that bound).  At the end all
+N are final.  The added latency is 2 H + Fw samples of the output rate.
 """
 import math
 
@@ -269,3 +288,35 @@ def limiter_window(fs, ms=3.0):
         raise ValueError("limiter: a look-ahead of %r ms at %d Hz is %d samples, outside [1, %d]" % (ms, fs, H, LOOKAHEAD_MAX))
     k = np.arange(-H, H + 1, dtype=np.float64)
     return H, (1.0 + np.cos(np.pi * k / (H + 1))) / (2.0 * H + 2.0)
+
+
+GAIN_RANGE = (-60.0, 60.0)    # dB, [lo, hi]
+
+
+def check_gain(gain_db):
+    """None (no gain stage) or a fixed gain in [-60, 60] dB."""
+    if gain_db is None:
+        return None
+    v = _number(gain_db, "gain_db")
+    if not GAIN_RANGE[0] <= v <= GAIN_RANGE[1]:
+        raise ValueError("gain_db must be in [-60, 60] dB (got %r)" % (gain_db,))
+    return v
+
+
+def limiter_reach(fs, lookahead_ms=3.0, true_peak=False):
+    """(H, Bk, Fw) of the fixed-gain limiter at ``fs`` Hz: the look-ahead in samples and how far the peak envelope of a sample
+    reads behind and ahead of it -- Bk = J - 1 - c // R and Fw = c // R of the true-peak bank (94 and 93 at R = 4 and at R = 2),
+    0 and 0 at R = 1 and with ``true_peak=False``.  Output n reads the input in [n - 2 H - Bk, n + 2 H + Fw]."""
+    H = limiter_window(fs, lookahead_ms)[0]
+    R = oversampling(fs) if check_true_peak(true_peak) else 1
+    if R == 1:
+        return H, 0, 0
+    from . import audio_io
+    _, J, c = audio_io.hq_bank(R, 1)
+    return H, J - 1 - c // R, c // R
+
+
+def limiter_ready(n_known, H, Fw):
+    """How many outputs of the fixed-gain limiter are final once ``n_known`` samples of a row of unknown length are known:
+    max(0, n_known - 2 H - Fw)."""
+    return max(0, int(n_known) - 2 * int(H) - int(Fw))

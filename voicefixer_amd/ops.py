@@ -791,6 +791,40 @@ def loudness_limit(x, n_rows, rate, target, ceiling_db=-1.0, true_peak=True, loo
     return res
 
 
+def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, true_peak=False, lookahead_ms=3.0):
+    """Outputs [m0, m1) of the fixed-gain look-ahead limiter over ONE row from a window of it (vfx_limit_span_f32; loudness.py,
+    DESIGN.md 3.16): xw (wlen,) device holds samples [g0, g0 + wlen) of a row of ``n_total`` samples at ``rate`` Hz (None: its
+    end is not known yet), out (>= m1 - m0,) receives output n at out[n - m0] -- the bits the single span [0, n_total) over the
+    whole row writes for it.  The window must cover [m0 - 2 H - Bk, m1 - 1 + 2 H + Fw] clipped to the row
+    (loudness.limiter_reach), or VfxError.  Returns the record, a device float64 (2,) of {min g, max |out|} over the span
+    ({1, 0} for an empty one).  Three launches, no synchronisation."""
+    from . import loudness
+    _need_cuda(xw, out)
+    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 1 and out.dim() == 1
+    assert (xw.numel() == 0 or xw.stride(0) == 1) and (out.numel() == 0 or out.stride(0) == 1)
+    gain_db = loudness.check_gain(gain_db)
+    if gain_db is None:
+        raise ValueError("limit_span: the limiter needs a gain (gain_db=...)")
+    ceiling_db = loudness.check_ceiling(ceiling_db)
+    true_peak = loudness.check_true_peak(true_peak)
+    H = loudness.limiter_window(rate, lookahead_ms)[0]
+    m0, m1 = int(m0), int(m1)
+    if m1 - m0 > out.numel():
+        raise _lib.VfxError("limit_span: %d outputs into a buffer of %d" % (m1 - m0, out.numel()))
+    if m1 == m0:
+        return torch.tensor([1.0, 0.0], dtype=torch.float64).to(xw.device)
+    R = loudness.oversampling(rate) if true_peak else 1
+    bank, J, c = true_peak_bank(xw.device, R) if R > 1 else (None, 1, 0)
+    h = _lib.lib()
+    nb = h.vfx_limit_span_workspace_bytes(max(m1 - m0, 0), H)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    rec = torch.empty((2,), dtype=torch.float64, device=xw.device)
+    check(h.vfx_limit_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total), m0, m1,
+                               10.0 ** (gain_db / 20.0), ceiling_db, H, _ptr(bank), J, R, c, _ptr(out), _ptr(rec), _ptr(ws), nb,
+                               _stream()), "vfx_limit_span_f32")
+    return rec
+
+
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):
     """Loudness report of programmes of several channels (vfx_loudness_report_groups_f32; arguments as loudness_groups): a
     device float64 (G, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample
