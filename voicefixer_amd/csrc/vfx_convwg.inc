@@ -17,8 +17,8 @@
 //    tap -- out-of-row taps get an out-of-range offset and read 0, which IS the zero padding: no guard band, nothing masked
 //    afterwards, per-row lengths cost nothing), pre-activation, B^T, planes to LDS [plane][channel][group], double buffered;
 //  * the staging of chunk s+1 is WOVEN between the MFMAs of chunk s (sched_barrier after every MFMA pins the order);
-//  * bias and residual enter through the accumulators, so the residual loads overlap the first chunk and the in-place
-//    update of a ResStack pair (res == y) stays exact (a lane reads what it later writes);
+//  * every accumulator starts at zero; bias and residual are added BEHIND the K loop (convwg4_kernel: see there), and the
+//    in-place update of a ResStack pair (res == y) stays exact: a lane reads the residual elements it later writes;
 //  * XCD-aware tile order with the Cout / BM channel blocks of a tile folded into the workgroup id.
 
 // channel blocks of a tile adjacent in dispatch order on one XCD (see the kernel); VFX_WINO_MFOLD=0: development
@@ -45,8 +45,14 @@ static void convwg_fold_blocks(ConvArgs& a, dim3& grid, int gy) {
 // 32*WGP consecutive quads x 32*WGM output channels; a wave 32 rows x 32 quads x 6 planes = 6 accumulator tiles (96 VGPRs,
 // against 128 for the pair kernel).  Staging, weights (packing.pack_wino4: [6 planes][Cin/8][Cout][8]), the woven loop and
 // the dispatch order follow convwg_kernel; A vectors are prefetched one 8-channel group ahead in two register sets.
-// Bias and residual enter through the accumulators: planes (0, 1, 3, 5) start at the unique solution of A^T m = r + b with
-// m2 = m4 = 0:  m3 = (t2-t1)/2, m1 = 2 t1 - t2, m0 = t0 - m1 - m3, m5 = t3 - m1 - 8 m3  (t_i = residual_i + bias).
+// Bias and residual never pass through the accumulators' partial sums.  All six planes start at zero (the C operand of the first
+// k-step).  The run-time instance (SPEC 0) adds bias, then residual, to the transformed outputs in its epilogue, in torch's
+// order; the specialised ones close plane 1 with one extra MFMA  acc[1] += bias (x) 1  behind the last k-step (y_i = m1 + ...
+// for all four outputs), exactly as convwg4p_kernel / convwg4x_kernel do, so that the three kernels return the same bits.
+// Until tests/test_wg4_gpu.py measured it, planes (0, 1, 3, 5) STARTED at the unique solution of A^T m = r + b with m2 = m4 = 0
+// (m3 = (t2-t1)/2, m1 = 2 t1 - t2, m0 = t0 - m1 - m3, m5 = t3 - m1 - 8 m3, t_i = residual_i + bias; SPEC 1 / 2: plane 1 at the
+// bias): every one of the Cin partial sums then rounded at several times the residual, and the output transform multiplied
+// that by up to 8 -- 14 - 31 x the fp32 statement's error under heavy-tailed weight-norm gains (profiles/wg4_parity.txt).
 // (The 3x3 convolutions of the ResUNet ran here in round 2, kernel columns as virtual chunks; now convwg4s_kernel.)
 // Occupancy is not what bounds this kernel.  Round 2: three waves per SIMD with ~10 spilled registers, slower.  Round 3: the
 // A operands as two sets of 8-BYTE vectors (24 instead of 48 registers: 150-166 VGPRs, three waves per SIMD, no spills)
@@ -95,7 +101,7 @@ static void convwg_fold_blocks(ConvArgs& a, dim3& grid, int gy) {
 // the staging takes its issue cycles out of the matrix pipe's, so instructions that compute nothing are worth removing.
 // SPEC (round 5): what is known about the launch at compile time, so that prologue and epilogue hold no instruction that computes
 // nothing (every VALU instruction takes its issue cycles out of the matrix pipe's, see PRE):
-//   0  anything (residual / bias / post-activation decided at run time; residual and bias enter through start values, see above)
+//   0  anything (residual / bias / post-activation decided at run time; bias and residual are loaded and added in the epilogue)
 //   1  the FIRST convolution of a ResStack layer: no residual, leaky ReLU after
 //   2  the SECOND one (D1 only): residual, no activation after.  The residual quads are LOADED IN THE EPILOGUE (four accumulator
 //      rows per batch, two batches in flight, into registers the A vectors and taps have left by then) and added to the outputs: 4
@@ -107,14 +113,12 @@ static void convwg_fold_blocks(ConvArgs& a, dim3& grid, int gy) {
 // Measured: the launch and the step do NOT get faster (profiles/r05_convwg4_spec_pk_ab.txt) -- prologue and epilogue already ran
 // under the co-resident workgroups' K loops, and the kernel runs at the chip's power cap (profiles/r05_power_cap.txt): fewer
 // instructions per product pay as energy -- a slightly higher clock -- not as issue cycles.
-// For SPEC 1 / 2 no accumulator is initialised at all: the first k-step's MFMAs of planes 0, 2, 3, 4, 5 take the inline constant 0
-// as their C operand, plane 1 takes the bias as loaded (four 16-byte loads = the sixteen rows of the lane, in accumulator order):
-// y_i = m1 + ... for all four outputs, so a start value of bias in plane 1 IS the bias.
+// No accumulator is initialised at all: the first k-step's MFMAs of all six planes take the inline constant 0 as their C operand.
 template <int WGM, int WGP, bool D1 = false, int XD = 2, bool PRE = true, int SPEC = 0>
 __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : VFX_WG4_OCC) void convwg4_kernel(const ConvArgs a) {
     static_assert(WGM * WGP == 4, "four waves");
     static_assert(SPEC == 0 || (SPEC == 1 && PRE) || (SPEC == 2 && D1 && !PRE), "specialised instances");
-    constexpr bool ZSTART = SPEC != 0;            // accumulators start from the MFMA's C operand (0 / bias), not from registers
+    constexpr bool ZSTART = true;                 // accumulators start from the MFMA's C operand (0), not from registers
     static_assert(XD == 2 || XD == 3, "prefetch distance");
     constexpr int XSETS = XD - 1;
     constexpr int KC = 16, NSTEP = KC / 2;
@@ -274,42 +278,13 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         aw[SET][k] = make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
     };
 
-    // ---- output addressing and accumulator start values
-    const int row0 = m0 + wm * 32;
-    int rv[4];                                    // (the output offsets are recomputed in the epilogue: 4 registers less in the loop)
-    int rvq = VFX_W_OOB;                          // D1: the whole quad as one 16-byte vector (all four outputs inside the row)
-    {
-        const int q = quad_q(Q0 + wp * 32 + lo);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rv[i] = q + i * d < Lrow ? (4 * hi * (int)a.r_cs + q + i * d) * 4 : VFX_W_OOB;
-        if constexpr (D1) {
-            const bool full = q + 3 < Lrow;
-            rvq = (full && a.res) ? rv[0] : VFX_W_OOB;   // (no residual: out of range, the vector loads below return zeros)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = full ? VFX_W_OOB : rv[i];   // single elements: the straddling quad only
-        }
-    }
     // ---- the issue block: every load the prologue needs, in the order in which the results are consumed (vmcnt counts in
-    // order): bias (4 x 16 bytes per lane, L2 hits), the taps of chunk 0, the first A vectors, THEN the residual -- raw, into
-    // the accumulator registers of planes 0, 1, 3, 5 (D1: into rq).  Round 4 (tools/wg4_phase.py, -DVFX_ABL=8 timers of wave 0):
-    // the prologue was 16-25 k ticks of a workgroup's 73-115 k, and 6-11 k of it sat in acc_start -- the bias used to be a
-    // plain global load issued AFTER the tap loads of chunks 1 and 2, so the start values waited for those HBM round trips;
-    // and chunk 0 could only be staged once the 64 residual loads queued in front of its taps had returned.  Now the
-    // staging of chunk 0 waits for the bias and its own taps alone, and the start values find bias and residual delivered.
-    // Nothing but loads may stand in this block: any arithmetic on a loaded value costs the precise vmcnt bookkeeping.
+    // order): the taps of chunk 0, the first A vectors.  Nothing but loads may stand in this block: any arithmetic on a loaded
+    // value costs the precise vmcnt bookkeeping.  (Bias and residual are loaded in the epilogue.)
+    const int row0 = m0 + wm * 32;
     f32x16 acc[6];
-    u32x4 rq[(D1 && SPEC == 0) ? 16 : 1];         // D1: the residual quads as loaded (scattering them over four accumulator
-                                                  // tiles here would need moves, i.e. a wait right behind the loads)
     const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(a.res ? a.res : a.x) + (long long)b * a.r_bs, (short)0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
-    u32x4 bq[4];                                  // bias of rows row0 + 4 hi + 8 g + (0..3); no bias: out of range = zeros
-    {
-        const int bvoff = a.bias ? (row0 + 4 * hi) * 4 : VFX_W_OOB;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(brsrc, bvoff, g * 32, 0);
-    }
     using X0 = std::integral_constant<int, 0>;
     using X1 = std::integral_constant<int, XSETS - 1>;   // (the second register set; the first again when there is one)
 #if VFX_ABL & 8
@@ -326,88 +301,11 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
     __builtin_amdgcn_sched_barrier(0);
 #endif
     DBG_T(dbg_ts);
-#if VFX_ABL & 8
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    if constexpr (SPEC == 0) {
-        const int cs4 = (int)a.r_cs * 4;
-        if constexpr (D1) {
-            // unconditional (a branch here would leave the loaded quads behind a join: copies, i.e. a wait per load)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                rq[r] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, rvq, (row0 + (r & 3) + 8 * (r >> 2)) * cs4, 0);
-        } else if (a.res) {
-            // (no launch of the model takes this path -- a dilated convolution with a residual -- and the join after it
-            // makes the wait in front of the staging of chunk 0 conservative; correct, exercised by the op tests)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * cs4;
-                acc[0][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[0], soff, 0));
-                acc[1][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[1], soff, 0));
-                acc[3][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[2], soff, 0));
-                acc[5][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[3], soff, 0));
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; acc[3][r] = 0.f; acc[5][r] = 0.f; }
-        }
-    }
     __builtin_amdgcn_sched_barrier(0);            // (nothing that consumes a loaded value may be scheduled up into the issue block)
     DBG_T(dbg_ta);
-    // start values: planes (0, 1, 3, 5) = the solution of A^T m = residual + bias with m2 = m4 = 0
-    auto acc_start = [&]() {
-        if constexpr (ZSTART) return;             // (the first k-step's C operands are 0 / the bias vector, see mma_chunk)
-        if constexpr (D1 && SPEC == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc[0][r] = __uint_as_float(rq[r].x); acc[1][r] = __uint_as_float(rq[r].y);
-                acc[3][r] = __uint_as_float(rq[r].z); acc[5][r] = __uint_as_float(rq[r].w);
-            }
-        }
-        if (D1 && has_tail && a.res) {            // (workgroup-uniform, one tile per row at most) the straddling quad's elements
-            const int cs4 = (int)a.r_cs * 4;
-#pragma unroll 1
-            for (int r = 0; r < 16; ++r) {
-                const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * cs4;
-                const float t0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[0], soff, 0));
-                const float t1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[1], soff, 0));
-                const float t2 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[2], soff, 0));
-                const float t3 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[3], soff, 0));
-                acc[0][r] += t0; acc[1][r] += t1; acc[3][r] += t2; acc[5][r] += t3;
-            }
-        }
-        if (!a.res) {
-            // no residual: t0 = .. = t3 = bias, whose solution is m1 = bias, everything else 0 (12 VALU operations per
-            // accumulator row less; workgroup-uniform, outside the K loop)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e;
-                    acc[0][r] = 0.f;
-                    acc[1][r] = __uint_as_float(e == 0 ? bq[g].x : (e == 1 ? bq[g].y : (e == 2 ? bq[g].z : bq[g].w)));
-                    acc[2][r] = 0.f; acc[3][r] = 0.f; acc[4][r] = 0.f; acc[5][r] = 0.f;
-                }
-            return;
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * g + e;
-                const float bb = __uint_as_float(e == 0 ? bq[g].x : (e == 1 ? bq[g].y : (e == 2 ? bq[g].z : bq[g].w)));
-                const float t0 = acc[0][r] + bb, t1 = acc[1][r] + bb, t2 = acc[3][r] + bb, t3 = acc[5][r] + bb;
-                const float m3 = 0.5f * (t2 - t1);
-                const float m1 = 2.f * t1 - t2;
-                acc[0][r] = t0 - m1 - m3;
-                acc[1][r] = m1;
-                acc[2][r] = 0.f;
-                acc[3][r] = m3;
-                acc[4][r] = 0.f;
-                acc[5][r] = t3 - m1 - 8.f * m3;
-            }
-        }
-    };
+    // SPEC 1 / 2: the bias as the A operand of the MFMA that closes plane 1 (lanes 0-31: k-column 0; see convwg4p_kernel)
+    float bias_a = 0.f;
+    if constexpr (SPEC != 0) bias_a = (a.bias && hi == 0) ? a.bias[row0 + lo] : 0.f;
 
     // ---- B fragments: lane (column lo, k-half hi) of k-pair u of plane k reads xs[k*PLANE + (2u + hi)*BQ + column]
     // (BQ == 64: the wave's 32 quads wp*32 .. +31; odd channels are rotated by 32 within the 64-column row)
@@ -418,16 +316,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
     // element s of the thread is handled during steps s*SPAN .. s*SPAN + SPAN - 1 (first half: transform + 6 LDS writes,
     // second half: its 6 tap loads for the chunk after next); the 6 A vectors of the next 8-channel group are loaded in the
     // first step of each group into the register set the previous group used.
-    // first_tag (specialised instances, chunk 0 only): the MFMAs of k-step 0 start the accumulators -- C = 0 (inline constant) for
-    // planes 0, 2, 3, 4, 5 and C = the bias vector for plane 1
-    f32x16 biasv;
-    if constexpr (ZSTART) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            biasv[4 * g + 0] = __uint_as_float(bq[g].x); biasv[4 * g + 1] = __uint_as_float(bq[g].y);
-            biasv[4 * g + 2] = __uint_as_float(bq[g].z); biasv[4 * g + 3] = __uint_as_float(bq[g].w);
-        }
-    }
+    // first_tag (chunk 0 only): the MFMAs of k-step 0 start the accumulators -- C = 0 (inline constant)
     auto mma_chunk = [&](auto set_tag, auto first_tag, const float* xs, float* wdst, int xchunk, int agrp0, int glast) {
         constexpr bool FIRST = decltype(first_tag)::value;
         const float* bp = xs + boffs;
@@ -465,7 +354,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
                 if constexpr (FIRST) {
                     if (u == 0) {
                         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], k == 1 ? biasv : zero16, 0, 0, 0);
+                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], zero16, 0, 0, 0);
                     } else {
                         acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], acc[k], 0, 0, 0);
                     }
@@ -485,13 +374,12 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
     x_load(X0{}, S > 1 ? 1 : 0);
     if constexpr (XSETS == 2) x_load(X1{}, min(2, S - 1));
     __builtin_amdgcn_sched_barrier(0);
-    acc_start();
     DBG_T(dbg_tc);
     WG4_SYNC();
     DBG_T(dbg_t1);
     using NotFirst = std::false_type;
     int s_begin = 0;
-    if constexpr (ZSTART) {                       // chunks 0 and 1 peeled: chunk 0's first k-step initialises the accumulators
+    if constexpr (ZSTART) {                       // chunks 0 and 1 peeled: chunk 0's first k-step starts the accumulators at zero
         mma_chunk(X0{}, std::true_type{}, smem, wbase + BUF, min(XD, S - 1), 0, glast);
         WG4_SYNC();
         mma_chunk(X1{}, NotFirst{}, smem + BUF, wbase, min(1 + XD, S - 1), 2, glast);
@@ -509,6 +397,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         WG4_SYNC();
     }
     DBG_T(dbg_t2);
+    if constexpr (SPEC != 0) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, acc[1], 0, 0, 0);   // + bias, rounded once
 
     // ---- output transform, activation, stores
     const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -547,6 +436,63 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         y[1] = fmaf(2.f, m34, m12);
         y[2] = fmaf(4.f, p34, p12);
         y[3] = fmaf(8.f, m34, m12) + acc[5][r];
+    };
+    if constexpr (SPEC == 0) {
+        // The run-time instance: bias and residual are loaded here -- the A vectors and taps have left their registers -- and added
+        // to the transformed outputs, bias first, in torch's order.  The sums go back into the registers of planes 0 .. 3 (dead after
+        // the transform), so that the post-activation loops below find them there.  In place (res == y): every lane loads exactly the
+        // residual elements it stores afterwards, and no other lane or workgroup touches them.
+        const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(a.bias ? a.bias : a.x), (short)0, 0x7fffffff, 0x00020000);
+        u32x4 bq[4];                              // bias of rows row0 + 4 hi + 8 g + (0..3); no bias: out of range = zeros
+        const int bvoff = a.bias ? (row0 + 4 * hi) * 4 : VFX_W_OOB;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(brsrc, bvoff, g * 32, 0);
+        const int cs4 = (int)a.r_cs * 4;
+        const int qe = quad_q(Q0 + wp * 32 + lo);
+        int rv[4];                                // single residual elements (D1: the straddling quad's only); no residual: out of range = zeros
+        int rvq = VFX_W_OOB;                      // D1: the whole quad as one 16-byte vector (all four outputs inside the row)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rv[i] = (a.res && qe + i * d < Lrow) ? (4 * hi * (int)a.r_cs + qe + i * d) * 4 : VFX_W_OOB;
+        if constexpr (D1) {
+            const bool full = qe + 3 < Lrow;
+            rvq = full ? rv[0] : VFX_W_OOB;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rv[i] = full ? VFX_W_OOB : rv[i];
+        }
+        u32x4 rq[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * cs4;
+            if constexpr (D1) {
+                rq[r] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, rvq, soff, 0);
+            } else {
+                rq[r].x = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[0], soff, 0);
+                rq[r].y = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[1], soff, 0);
+                rq[r].z = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[2], soff, 0);
+                rq[r].w = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[3], soff, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const u32x4 bg = bq[r >> 2];
+            const float bb = __uint_as_float((r & 3) == 0 ? bg.x : ((r & 3) == 1 ? bg.y : ((r & 3) == 2 ? bg.z : bg.w)));
+            float y[4];
+            outs(r, y);
+            float t[4] = {__uint_as_float(rq[r].x), __uint_as_float(rq[r].y), __uint_as_float(rq[r].z), __uint_as_float(rq[r].w)};
+            if (D1 && has_tail && a.res) {        // (workgroup-uniform, one tile per row at most; every other lane's offsets read 0,
+                                                  // this quad's vector load returned zeros)
+                const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * cs4;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) t[i] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, rv[i], soff, 0));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i][r] = (y[i] + bb) + t[i];
+        }
+    }
+    auto sums = [&](int r, float (&y)[4]) {       // SPEC 0: transformed output + bias + residual of accumulator row r (see above)
+        y[0] = acc[0][r]; y[1] = acc[1][r]; y[2] = acc[2][r]; y[3] = acc[3][r];
     };
     if constexpr (SPEC == 1) {                    // first convolution of a ResStack layer: leaky ReLU, nothing else
 #pragma unroll
@@ -600,7 +546,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         for (int r = 0; r < 16; ++r) {
             const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * ycs4;
             float y[4];
-            outs(r, y);
+            sums(r, y);
             store4(y, soff);
         }
     } else if (post == VFX_POST_LRELU) {
@@ -608,7 +554,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         for (int r = 0; r < 16; ++r) {
             const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * ycs4;
             float y[4];
-            outs(r, y);
+            sums(r, y);
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[i] = fmaxf(y[i], y[i] * ps);   // (0 <= slope <= 1, checked on the host)
             store4(y, soff);
@@ -618,7 +564,7 @@ __global__ __launch_bounds__(256, (SPEC == 2 && WGM == 4) ? VFX_WG4_SPEC2_OCC : 
         for (int r = 0; r < 16; ++r) {
             const int soff = (row0 + (r & 3) + 8 * (r >> 2)) * ycs4;
             float y[4];
-            outs(r, y);
+            sums(r, y);
 #pragma unroll
             for (int i = 0; i < 4; ++i) y[i] = vfx_post(y[i], post, ps);
             store4(y, soff);

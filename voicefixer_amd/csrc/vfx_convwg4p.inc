@@ -1,7 +1,8 @@
 // vfx_convwg4p.inc -- included by vfx_conv.hip after vfx_convwg.inc.
 //
 // convwg4p_kernel (round 5): convwg4_kernel's arithmetic (Winograd F(4,3) along the dilated axis, exact fp32 MFMA; same staging map,
-// same woven K loop, same weights, results bit-identical) as PERSISTENT workgroups whose pipeline runs ACROSS tiles.
+// same woven K loop, same weights, results bit-identical to its SPEC 1 / 2 instances: tests/test_wg4_gpu.py launches the same operands
+// on either side of the threshold below and compares the bits) as PERSISTENT workgroups whose pipeline runs ACROSS tiles.
 //
 // Why.  tools/wg4_timeline.py on the one-tile-per-workgroup kernel (profiles/r05_wg4_timeline_and_stagger.txt, r05_wg4_slots.txt): a CU's
 // two workgroup slots are EMPTY 5-12 % of the time (a freed slot is re-filled 3.5-4 us later), a workgroup spends 10-39 % of its life
@@ -23,8 +24,8 @@
 // prefetch simply CONTINUE from the last chunks of tile n into the first chunks of tile n + 64: where convwg4_kernel re-issues clamped
 // duplicate loads at the end of its K loop, this kernel loads chunks 0 and 1 of the next tile, stages chunk 0 while the last chunk
 // multiplies, and wraps the A groups around.  Between two tiles stand the output transform and the stores of the finished one -- no
-// load round trip, no barrier wait, no dispatch.  The accumulators restart through the C operand of the first k-step (0 / bias), as in
-// the SPEC instances of convwg4_kernel, so nothing has to be zeroed either; the residual quads of the second convolution (SPEC 2) are
+// load round trip, no barrier wait, no dispatch.  The accumulators restart through the C operand of the first k-step (0), as in
+// convwg4_kernel, so nothing has to be zeroed either; the residual quads of the second convolution (SPEC 2) are
 // requested at the start of the last chunk and added in the epilogue.
 // Instances exist for the two launches a ResStack layer consists of (SPEC 1 / 2, see convwg4_kernel) with at least four chunks
 // (Cin >= 64); everything else stays on convwg4_kernel.  Per-row lengths (ragged batches): a tile past its row's end is skipped, the
@@ -165,10 +166,12 @@ __global__ __launch_bounds__(256, 2) void convwg4p_kernel(const ConvArgs a) {
     using A0 = std::integral_constant<int, 0>;
     using A1 = std::integral_constant<int, 1>;
 
-    // ---- bias: ONE register.  Every tile opens plane 1 with an extra MFMA  acc[1] = bias (x) 1 : A operand = bias[row] in k-column 0 (lanes
-    // 0-31) and 0 in k-column 1, B operand = 1.0 -- y_i = m1 + ... for all four outputs, so a start value of bias in plane 1 IS the
-    // bias.  (convwg4_kernel hands the bias over as the C operand of the first MFMA: sixteen registers that would stay live across
-    // every tile here.)  One MFMA in 48 S.
+    // ---- bias: ONE register.  Every tile closes plane 1 with an extra MFMA  acc[1] += bias (x) 1  behind its last k-step: A operand =
+    // bias[row] in k-column 0 (lanes 0-31) and 0 in k-column 1, B operand = 1.0 -- y_i = m1 + ... for all four outputs, so the bias
+    // added to plane 1 IS the bias.  BEHIND the K loop, not in front of it: as the start value of plane 1 the bias made every one of
+    // the Cin partial sums of m1 round at the size of the bias (tests/test_wg4_gpu.py, profiles/wg4_parity.txt: up to 7 x the fp32
+    // statement's RMS under heavy-tailed weight-norm gains); here it is rounded once, into the finished sum.  (The SPEC instances of
+    // convwg4_kernel do the same; its run-time instance adds bias and residual to the transformed outputs.)  One MFMA in 48 S.
     const float bias_a = (a.bias && hi == 0) ? a.bias[row0 + lo] : 0.f;
     f32x16 acc[6];
     const int bcol = BQ == 32 ? lo : ((wp * 32 + lo + 32 * hi) & 63);
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void convwg4p_kernel(const ConvArgs a) {
     const int ycs4 = (int)a.y_cs * 4;
 
     // One chunk (8 k-pair steps x 6 MFMAs) with the staging of the next chunk and the A vectors of the next group woven in, as in
-    // convwg4_kernel.  first_tag: k-step 0 starts the accumulators (C = 0, plane 1: the bias product).
+    // convwg4_kernel.  first_tag: k-step 0 starts the accumulators (C = 0).
     auto mma_chunk = [&](auto first_tag, const __amdgpu_buffer_rsrc_t& rsl, const float* xs, float* wdst, int xchunk, int agrp0) {
         constexpr bool FIRST = decltype(first_tag)::value;
         const float* bp = xs + boffs;
@@ -213,8 +216,7 @@ __global__ __launch_bounds__(256, 2) void convwg4p_kernel(const ConvArgs a) {
                 if constexpr (FIRST) {
                     if (u == 0) {
                         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        if (k == 1) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, zero16, 0, 0, 0);
-                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], k == 1 ? acc[1] : zero16, 0, 0, 0);
+                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], zero16, 0, 0, 0);
                     } else {
                         acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k], acc[k], 0, 0, 0);
                     }
@@ -301,7 +303,8 @@ __global__ __launch_bounds__(256, 2) void convwg4p_kernel(const ConvArgs a) {
                 __syncthreads();
             }
 
-            // ---- output transform, activation / residual, stores of the finished tile
+            // ---- the bias product closes plane 1 (see bias_a); output transform, activation / residual, stores of the finished tile
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, acc[1], 0, 0, 0);
             const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
                 a.y + (long long)t_b * a.y_bs, (short)0, 0x7fffffff, 0x00020000);
             const float ps = a.post_slope;

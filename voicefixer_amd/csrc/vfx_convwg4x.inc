@@ -20,7 +20,9 @@
 // under the NEXT tile's K loop, a few per k-pair step, their LDS reads and residual loads issued one chunk before they are used.
 // To make room the staging chunk is 8 channels (two 12 KB buffers; a barrier per 48 MFMAs per wave).
 //
-// Work list, tile walk, SPEC instances, bias through an extra MFMA, per-row lengths: exactly convwg4p_kernel (see there).
+// Work list, tile walk, SPEC instances, bias through an extra MFMA behind the last k-step, per-row lengths: exactly convwg4p_kernel
+// (see there).  Every output is one chain over the input channels in ascending order and the bias closes plane 1, as in the SPEC
+// instances of convwg4_kernel: the three kernels return the same bits (tests/test_wg4_gpu.py pins it on either side of the threshold).
 // Development ablations (wrong results, timing only; `make dev DEVDEFS=-DVFX_WG4X_ABL=n DEVNAME=xabln`):
 //   1 = no output transform / LDS hand-over / trickle     2 = no staging in the K loop (no tap loads, transform, LDS writes)
 //   4 = no barriers in the K loop     8 = every A vector from 8-channel group 0 (L1 hits instead of the L2 stream)     16 = no trickle (outputs stay in LDS)
@@ -165,7 +167,8 @@ __global__ __launch_bounds__(256, 1) void convwg4x_kernel(const ConvArgs a) {
     using A0 = std::integral_constant<int, 0>;
     using A1 = std::integral_constant<int, 1>;
 
-    // ---- bias: every tile opens plane 1 of both quad blocks with an extra MFMA  acc = bias (x) 1  (see convwg4p_kernel)
+    // ---- bias: every tile CLOSES plane 1 of both quad blocks with an extra MFMA  acc += bias (x) 1  behind its last k-step (see
+    // convwg4p_kernel): the bias is rounded once, into the finished sum -- never into the partial sums of the K loop
     const float bias_a = (a.bias && hi == 0) ? a.bias[row0 + lo] : 0.f;
     f32x16 acc[6][2];
     const int boffs = hi * BQ + 2 * lo;           // B fragments of quads lo, lo + 32: one 8-byte read
@@ -294,13 +297,9 @@ __global__ __launch_bounds__(256, 1) void convwg4x_kernel(const ConvArgs a) {
                 if constexpr (FIRST) {
                     if (u == 0) {
                         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        if (k == 1) {
-                            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, zero16, 0, 0, 0);
-                            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, zero16, 0, 0, 0);
-                        }
-                        acc[k][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k].x, k == 1 ? acc[1][0] : zero16, 0, 0, 0);
+                        acc[k][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k].x, zero16, 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
-                        acc[k][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k].y, k == 1 ? acc[1][1] : zero16, 0, 0, 0);
+                        acc[k][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k].y, zero16, 0, 0, 0);
                     } else {
                         acc[k][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bf[k].x, acc[k][0], 0, 0, 0);
                         __builtin_amdgcn_sched_barrier(0);
@@ -383,8 +382,10 @@ __global__ __launch_bounds__(256, 1) void convwg4x_kernel(const ConvArgs a) {
 #pragma unroll 1
             for (int s = SA; s < S; s += 2) chunk_pair(s, No{});
 
-            // ---- the finished tile: whatever the previous one still owes goes out first (short K loops only), then output transform ->
-            // LDS, and the tile becomes the pending one
+            // ---- the finished tile: the bias product closes plane 1 of both quad blocks (see bias_a), whatever the previous tile still
+            // owes goes out (short K loops only), then output transform -> LDS, and the tile becomes the pending one
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, 1.0f, acc[1][1], 0, 0, 0);
             trickle_drain();
             if constexpr ((VFX_WG4X_ABL & 1) == 0) {
 #pragma unroll

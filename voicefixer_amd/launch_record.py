@@ -39,6 +39,10 @@ def _describe(name, a):
         d.update(H=a["h"], pitch=1 << a["in_pitch_log2"], k=3, step=2, pad="zero")
     d["pre"] = act.c.pre_act if isinstance(act, ops.Act) else _lib.PRE_NONE
     d["post"] = act.c.post_act if isinstance(act, ops.Act) else (a.get("post", _lib.POST_NONE) if name.startswith("resblock") else _lib.POST_NONE)
+    if isinstance(act, ops.Act):
+        d["post_slope"] = float(act.c.post_slope)
+    elif not name.startswith("resblock"):
+        d["post_slope"] = 0.0
     d["bias"] = a.get("bias") is not None
     d["res"] = "none" if res is None else ("in place" if res.data_ptr() == y.data_ptr() else "separate")
     d["rows"] = getattr(x, "_vfx_rows", None) is not None
@@ -98,6 +102,11 @@ class LaunchRecorder:
         """The records that ran on resblk4_kernel / resblk4s_kernel (codes 96 / 97: one whole C = 64 ResStack layer, both
         halves Winograd F(4,3), on the block tile / the strip tile)."""
         return [r for r in self.records if r["code"] in (96, 97)]
+
+    def wg4(self):
+        """The records that ran on the stand-alone Winograd F(4,3) convolutions (codes 80 / 81 / 82: convwg4_kernel, its
+        persistent form convwg4p_kernel and the re-blocked persistent convwg4x_kernel)."""
+        return [r for r in self.records if r["code"] in (80, 81, 82)]
 
 
 def split_k(rec):
