@@ -570,6 +570,42 @@ int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_tota
                        double ceiling_db, int H, const float* bank, int J, int R, int c, float* out, double* record, void* ws,
                        size_t ws_bytes, vfx_stream_t stream);
 
+/* ---- streaming loudness leveller of a session: the span form (voicefixer_amd/loudness.py) ---------------------- */
+
+#define VFX_LEVEL_STATE 64 /* float64 values of the caller's state */
+
+/* Bytes of the workspace of vfx_level_span_f32 for spans of up to n_span outputs at quarters of hop samples (0 on bad arguments:
+ * n_span < 0 or > 2^30, hop outside [400, 19200]): 12 bytes per quarter of the span and a few more. */
+size_t vfx_level_span_workspace_bytes(int64_t n_span, int hop);
+
+/* Outputs [m0, m1) of the loudness leveller over ONE row of n_total samples at fs Hz (INT64_MAX: the row's end is not known yet)
+ * from the window xw[k] = x[g0 + k], k < wlen; out[t - m0] receives output t.  hop = (fs + 5) / 10, Q = n_total / hop:
+ *   E_q = the K-weighted energy (fp32 filter of coef, fp64 sum) of quarter q = [q hop, (q + 1) hop), the filter started from zero
+ *         at sample max(0, (q - 2) hop);
+ *   l_q = -0.691 + 10 log10(mean of E_j / hop over j in [q - 20, q + 9] within [0, Q)), q = 0..Q (ascending fp64 sum);
+ *   G_q = clamp(target - l_q, -40, max_gain_db) where l_q > gate, else G_{q-1} (G_{-1} = 0; an empty or silent window holds);
+ *   a_q = (float)10^(G_q / 20);  out[t] = x[t] * (a_q + (a_{q+1} - a_q) * ((float)(t - q hop) / (float)hop)) for t in quarter
+ *   q < Q, fp32, every operation rounded once in this order;  out[t] = x[t] * a_Q for t >= Q hop.
+ * Every value is a function of global positions: output t has the bits one call over the whole row writes for it, whatever the
+ * split, the window or g0.  While the end is unknown, outputs below (n_known / hop - 10) hop are final (n_known = g0 + wlen).
+ * Calls come IN ORDER: the first has m0 = 0 (which initialises state), every other the m1 of the one before, so that what a
+ * call finds in state follows from m0: the anchors [0, na(m0)) evaluated, the energies [0, ne(m0)) computed,
+ *   na(m) = m == 0 ? 0 : min(Q, (m - 1) / hop + 1) + 1,   ne(m) = m == 0 ? 0 : min(Q, na(m) + 9)   (Q = infinity while unknown).
+ * The window must cover [m0, m1) and, when ne(m1) > ne(m0), [max(0, ne(m0) - 2) hop, ne(m1) hop); nothing else is read.
+ * coef: the 10 K-weighting values of vfx_loudness_rows_f32 (host); S = 32 ceil(3 hop / 8192), mpow: device float64[8][16],
+ * M^(2^i) of the zero-input transition M of S samples.  state: device float64[VFX_LEVEL_STATE], the caller's, one per row:
+ *   [0] min G  [1] max G  [2] anchors evaluated  [3] anchors gated  [4] G of the last anchor  [5] energies computed
+ *   [6] 1 once a call came out of order  [8..12) the last four a_q  [16..48) the last 32 E_j  -- [0..4) is the record, folded
+ *   exactly over the calls.  ws: >= vfx_level_span_workspace_bytes(m1 - m0, hop) bytes, 16-byte aligned.
+ * At most three launches (new quarters, anchors, apply); no host synchronisation.  An empty span is VFX_OK and launches nothing.
+ * VFX_EINVAL, nothing launched: a NULL pointer; g0, wlen, m0 < 0, m0 > m1, m1 > n_total, m1 - m0 > 2^30; fs outside [4000, 192000];
+ * S not the chunk length of fs; a coefficient that is not finite; target outside [-70, 0), max_gain_db outside [0, 40], gate
+ * outside [-70, target); m1 beyond the ready bound while the end is unknown; a window that does not cover the ranges above; ws
+ * too small or misaligned; out overlapping xw. */
+int vfx_level_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0, int64_t m1, int fs,
+                       const double* coef, const double* mpow, int S, double target, double max_gain_db, double gate,
+                       double* state, float* out, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
 /* ---- word-length reduction: 16- / 24-bit PCM with seeded dither (voicefixer_amd/wordlength.py) ----------------- */
 
 /* The last stage of the output chain (the reference's save_wave truncates to int16 on the host, voicefixer/tools/wav.py:27-34;

@@ -664,6 +664,46 @@ def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, 
     return outs[0] if single else outs
 
 
+LEVEL_SPAN = 1 << 22      # outputs per ops.level_span call of ``level``: bounds the scratch, changes no bit
+
+
+def level(x, target=-16.0, max_gain_db=12.0, gate=-50.0, sample_rate=44100, stats=None, _span=None):
+    """The streaming loudness leveller (loudness.py) on the device: a float32 array (N,) at ``sample_rate`` (at
+    most 192 kHz) -- or every array of a list, each row on its own -- is multiplied by a slowly moving gain that brings the
+    loudness of the 3 s around every 100 ms anchor to ``target`` LUFS: at most ``max_gain_db`` up ([0, 40] dB) and 40 dB down,
+    held wherever that loudness is not above ``gate`` (LUFS, in [-70, target)), so that pauses are not pumped up.  This is what a
+    streaming session (``open_stream(leveller=target)``) applies, bit for bit.  A row shorter than 100 ms comes back as it is.
+    ``stats``: a dict that receives {"min_gain_db", "max_gain_db", "anchors", "gated"} (lists of one value per row when a list
+    went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span."""
+    from . import loudness as ld
+    rate = _check_rate(sample_rate)
+    target, max_gain_db, gate = ld.check_leveller(target, max_gain_db, gate, rate)
+    if stats is not None and not isinstance(stats, dict):
+        raise ValueError("stats must be a dict or None")
+    span = LEVEL_SPAN if _span is None else int(_span)
+    if span < 1:
+        raise ValueError("_span must be positive")
+    single = not isinstance(x, (list, tuple))
+    items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
+    for w in items:
+        if w.ndim != 1:
+            raise ValueError("level: a row is a 1-D array of samples (got shape %r)" % (w.shape,))
+    outs, recs = [], []
+    dev = _device() if items else None
+    for w in items:
+        lv = _SpanLeveller(rate, target, max_gain_db, gate, span)
+        if w.shape[0] == 0:
+            outs.append(np.zeros((0,), np.float32))
+        else:
+            xd = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+            outs.append(torch.cat([lv.feed(xd), lv.finish(dev)]).cpu().numpy())
+        recs.append(lv.stats())
+    if stats is not None:
+        for key in ("min_gain_db", "max_gain_db", "anchors", "gated"):
+            stats[key] = recs[0][key] if single else [r[key] for r in recs]
+    return outs[0] if single else outs
+
+
 class Vocoder(nn.Module):
     """44.1 kHz TFGAN-style universal vocoder (voicefixer/vocoder/base.py)."""
 
@@ -1283,7 +1323,8 @@ class VoiceFixer(nn.Module):
 
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                     sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
-                    dither="tpdf", dither_seed=0, gain_db=None, peak_ceiling=-1.0, true_peak=False):
+                    dither="tpdf", dither_seed=0, gain_db=None, peak_ceiling=-1.0, true_peak=False, leveller=None,
+                    leveller_max_gain_db=12.0, leveller_gate=-50.0):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
@@ -1300,15 +1341,24 @@ class VoiceFixer(nn.Module):
         NotImplementedError, as ``restore_stream`` does with any limiter: a loudness TARGET needs the whole file, and a session
         never sees it (nor does it offer a trim, several channels or ``restore_stream``'s refusal lifted).  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
         on the device, each from the session's position on, so that all of them, concatenated, are the whole output quantised
-        once; ``push`` and ``finish`` then return int16 / int32 arrays."""
+        once; ``push`` and ``finish`` then return int16 / int32 arrays.
+        ``leveller`` (LUFS, [-70, 0); default None: none): the streaming loudness leveller (loudness.py) behind the
+        output converter and in front of the gain / limiter stage: a slowly moving gain that brings the loudness of the 3 s
+        around every 100 ms anchor of the output to this target, at most ``leveller_max_gain_db`` up ([0, 40] dB) and 40 dB down,
+        held wherever that loudness is not above ``leveller_gate`` (LUFS, [-70, target)) -- what ``voicefixer_amd.level`` gives
+        for the whole output, bit for bit, less than 1.1 s late; output rates up to 192 kHz.  With a leveller ``limiter=True``
+        needs no ``gain_db`` (the limiter then runs at 0 dB; a ``gain_db`` follows the leveller as it follows the converter
+        today); ``session.leveller_stats`` reports {"min_gain_db", "max_gain_db", "anchors", "gated"}."""
         from . import loudness as ld
-        if _check_limiter(limiter, limiter_lookahead_ms) and ld.check_gain(gain_db) is None:
+        if leveller is not None:
+            ld.check_leveller(leveller, leveller_max_gain_db, leveller_gate)
+        if _check_limiter(limiter, limiter_lookahead_ms) and ld.check_gain(gain_db) is None and leveller is None:
             raise NotImplementedError("open_stream: the limiter behind a loudness target is not built -- it follows a whole-file "
                                       "measurement; give a fixed gain (gain_db=...) for the session's fixed-gain limiter, or use "
                                       "restore_inmem or restore_folder")
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
                               output_sample_rate, bit_depth, dither, dither_seed, gain_db, peak_ceiling, true_peak, limiter,
-                              limiter_lookahead_ms)
+                              limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate)
 
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)
@@ -1855,6 +1905,67 @@ class _SpanLimiter:
         return {"max_reduction_db": -loudness.to_db(gmin) + 0.0, "peak_out_db": loudness.to_db(peak)}
 
 
+class _SpanLeveller:
+    """The loudness leveller (loudness.py) of ONE row that arrives in pieces (ops.level_span): ``feed`` takes the
+    next samples (device (k,)) and returns the outputs that became final with them (loudness.leveller_ready), ``finish`` the rest
+    with the row's end known.  Every output has the bits of one call over the whole row.  Kept between calls: the samples from
+    the first output not yet returned on (fewer than 11 quarters, 1.1 s, beyond a block: the energies behind them live in the
+    device state), their global offset and the device state with the record, read by ``stats()`` only.  Nothing touches the
+    device before the first ``feed``."""
+
+    def __init__(self, rate, target, max_gain_db=12.0, gate=-50.0, span=None):
+        from . import loudness
+        self.target, self.max_gain_db, self.gate = loudness.check_leveller(target, max_gain_db, gate, rate)
+        self.rate, self.hop = int(rate), loudness.hop_length(rate)
+        self.span = LEVEL_SPAN if span is None else int(span)
+        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
+        self.g0 = 0
+        self.n_in = 0        # samples fed
+        self.m_done = 0      # outputs returned
+        self.state = None    # device float64 (loudness.LEVELLER_STATE,)
+
+    def feed(self, x):
+        from . import loudness
+        self.win = x if self.win is None else torch.cat([self.win, x])
+        self.n_in += x.numel()
+        return self._emit(loudness.leveller_ready(self.n_in, self.hop), None)
+
+    def finish(self, device):
+        if self.win is None:
+            return torch.empty((0,), dtype=torch.float32, device=device)
+        return self._emit(self.n_in, self.n_in)
+
+    def _emit(self, m1, n_total):
+        from . import loudness, ops
+        m0, m1 = self.m_done, max(m1, self.m_done)
+        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
+        if self.state is None and m1 > m0:
+            self.state = ops.level_state(self.win.device)
+        for a in range(m0, m1, self.span):
+            b = min(a + self.span, m1)
+            ops.level_span(self.win, self.g0, n_total, self.rate, self.target, a, b, y[a - m0:b - m0], self.state,
+                           self.max_gain_db, self.gate)
+        self.m_done = m1
+        # drop what no later call reads: the next outputs themselves and the region of the next quarter to be measured, which
+        # starts two quarters before it (one sample always stays: a window is never empty)
+        ne = loudness.leveller_counts(m1, self.hop)[1]
+        keep = min(m1, max(ne - loudness.LEVELLER_WARMUP, 0) * self.hop, self.n_in - 1)
+        if keep > self.g0:
+            self.win = self.win[keep - self.g0:].clone()
+            self.g0 = keep
+        return y
+
+    def stats(self):
+        """{"min_gain_db", "max_gain_db", "anchors", "gated"} over what has been returned (reads the device state: the one
+        synchronisation); zeros before the first anchor."""
+        if self.state is None:
+            return {"min_gain_db": 0.0, "max_gain_db": 0.0, "anchors": 0, "gated": 0}
+        v = self.state[:7].cpu().numpy()
+        if v[6] != 0.0:
+            raise VfxError("leveller: the spans of a row did not come in order")
+        return {"min_gain_db": float(v[0]), "max_gain_db": float(v[1]), "anchors": int(v[2]), "gated": int(v[3])}
+
+
 class RestoreSession:
     """``VoiceFixer.open_stream``: the overlap-add long-form mode as a push-style session on the device.
 
@@ -1881,12 +1992,18 @@ class RestoreSession:
     2 H + 93 samples late; ``limiter_stats`` is then {"max_reduction_db", "peak_out_db"} over what has been delivered (None
     without a limiter).  The limiter bounds every sample by the ceiling, the inter-sample peak only approximately: lower
     ``peak_ceiling`` for a margin.  The word-length reduction (``bit_depth``) is offered too: its dither is a function of a
-    sample's position, not of the file.  The stages behind the stitcher: output converter, gain / limiter, word length, host.
+    sample's position, not of the file.  A loudness target without the whole file is the LEVELLER's (``leveller=T`` LUFS,
+    ``leveller_max_gain_db``, ``leveller_gate``; loudness.py; ``voicefixer_amd.level`` on the whole output, bit
+    for bit): a gain that follows the loudness of the 3 s around every 100 ms anchor, carried across stretches like the
+    converters and less than 1.1 s late; with it ``limiter=True`` needs no ``gain_db`` (the limiter then runs at 0 dB) and
+    ``leveller_stats`` is {"min_gain_db", "max_gain_db", "anchors", "gated"} (None without a leveller).  The stages behind the
+    stitcher: output converter, leveller, gain / limiter, word length, host.
     A context manager; leaving it without ``finish`` discards what is pending."""
 
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                  sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0, gain_db=None,
-                 peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0):
+                 peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0, leveller=None,
+                 leveller_max_gain_db=12.0, leveller_gate=-50.0):
         from . import loudness as ld
         _check_stream_mode(mode, "open_stream")
         self._word = _Output(bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)     # (checks the three)
@@ -1894,11 +2011,16 @@ class RestoreSession:
         self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
         gain_db, peak_ceiling, true_peak = ld.check_gain(gain_db), ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
         limiter, limiter_lookahead_ms = ld.check_limiter(limiter, limiter_lookahead_ms)
-        if limiter and gain_db is None:
-            raise NotImplementedError("RestoreSession: limiter=True needs a fixed gain (gain_db=...)")
+        if limiter and gain_db is None and leveller is None:
+            raise NotImplementedError("RestoreSession: limiter=True needs a fixed gain (gain_db=...) or a leveller (leveller=...)")
         self._gain = None if gain_db is None else float(np.float32(10.0 ** (gain_db / 20.0)))
-        # (limiter_reach: ValueError for a look-ahead outside [1, 4096] samples at the output rate)
-        self._lim = _SpanLimiter(self._rate_out, gain_db, peak_ceiling, true_peak, limiter_lookahead_ms) if limiter else None
+        # (check_leveller: ValueError for an output rate above 192 kHz too; nothing touches the device before the first stretch)
+        self._lev = (_SpanLeveller(self._rate_out, leveller, leveller_max_gain_db, leveller_gate)
+                     if leveller is not None else None)
+        # (limiter_reach: ValueError for a look-ahead outside [1, 4096] samples at the output rate; behind a leveller and
+        # without a gain the limiter runs at 0 dB)
+        self._lim = (_SpanLimiter(self._rate_out, 0.0 if gain_db is None else gain_db, peak_ceiling, true_peak,
+                                  limiter_lookahead_ms) if limiter else None)
         for r in (self._rate_in, self._rate_out):
             if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
                 raise ValueError("open_stream: the device resampler does not take the ratio of %d Hz to 44100 Hz" % r)
@@ -1930,12 +2052,20 @@ class RestoreSession:
         self._buf = self._tail = self._fade = self._conv_in = self._conv_out = None
         if self._lim is not None:
             self._lim.win = None     # (the record stays: limiter_stats outlives the session)
+        if self._lev is not None:
+            self._lev.win = None     # (so does the leveller's state)
 
     @property
     def limiter_stats(self):
         """{"max_reduction_db": -20 log10(min g), "peak_out_db": 20 log10(max |out|)} over what has been delivered -- exact folds,
         the values of one call over the whole row -- or None without a limiter."""
         return None if self._lim is None else self._lim.stats()
+
+    @property
+    def leveller_stats(self):
+        """{"min_gain_db", "max_gain_db", "anchors", "gated"} of the leveller over what has been delivered -- exact folds, the
+        values of ``level`` over the whole output -- or None without a leveller."""
+        return None if self._lev is None else self._lev.stats()
 
     @torch.no_grad()
     def push(self, block):
@@ -2009,13 +2139,17 @@ class RestoreSession:
         return out
 
     def _deliver(self, pipe, stretches, at_end):
-        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs, the fixed gain or
+        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs, the leveller, the fixed gain or
         the fixed-gain limiter when the session has one and, with a ``bit_depth``, through the word-length reduction: sample k of
         what is delivered has the absolute index position + k."""
         if self._conv_out is not None:
             stretches = [self._conv_out.feed(y) for y in stretches if y.numel()]
             if at_end:
                 stretches.append(self._conv_out.finish(pipe.device))
+        if self._lev is not None:
+            stretches = [self._lev.feed(y) for y in stretches if y.numel()]
+            if at_end:
+                stretches.append(self._lev.finish(pipe.device))
         if self._lim is not None:
             stretches = [self._lim.feed(y) for y in stretches if y.numel()]
             if at_end:

@@ -904,3 +904,4 @@ extern "C" int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const in
 /* ---- fixed-gain look-ahead limiter of a streaming session, span form -------------------------------------- */
 
 #include "vfx_limit_span.inc"
+#include "vfx_level_span.inc"

@@ -85,6 +85,36 @@ bits of the whole row, whatever the split.  Ready rule: with n_known samples see
 out to be (m[j] is read for j <= n + H and reads c up to n + 2 H, whose interpolated values read x up to n + 2 H + Fw; the
 clamp at the row's end and the values behind the last sample change nothing below N - 1 - H >= that bound).  At the end all
 N are final.  The added latency is 2 H + Fw samples of the output rate.
+
+Streaming loudness leveller (``open_stream(leveller=T)``, ``voicefixer_amd.level``; ``vfx_level_span_f32``): a
+slowly moving gain that follows the short-term loudness (EBU Tech 3341: 3 s) where no whole-file measurement exists.  Per row
+x[0..N) at fs <= 192 kHz: hop = ``hop_length(fs)``, quarter q = [q hop, (q + 1) hop), Q = N // hop complete quarters (a partial
+last quarter is never measured).  Parameters: the target T (``check_target``), ``max_gain_db`` in [0, 40] (default 12), ``gate``
+(LUFS) in [-70, T) (default -50).  LEVELLER_WARMUP = 2, LEVELLER_BEHIND = 20, LEVELLER_AHEAD = 10 quarters, LEVELLER_MAX_CUT = 40 dB.
+
+  1. Local quarter energy: E_q = the sum over quarter q of y^2 (float64 sum), y the K-weighting (the fp32 coefficients of
+     ``coefficients(fs)``, as the kernels run them) started from ZERO state at sample max(0, (q - 2) hop).  The truncated warm-up
+     is the definition: ``transition(fs)^(2 hop)`` has no entry above 1.4e-16 for 4 kHz <= fs <= 192 kHz (7e-19 at 4 kHz, 1.4e-17
+     at 44.1 kHz, 9e-18 at 48 kHz, 1.4e-16 at 192 kHz), far below fp32 resolution; at 768 kHz it is 3.5e-5, so the leveller
+     refuses fs > 192000 (ValueError).  E_q depends on x[(q - 2) hop .. (q + 1) hop) only.
+  2. Anchor loudness: anchor q sits at sample q hop, q = 0..Q; its window is the quarters j in [q - 20, q + 9] within [0, Q);
+     z_q = (sum of E_j, ascending j, float64, a direct sum per anchor) / (count hop); l_q = -0.691 + 10 log10 z_q.  An empty
+     window or z_q = 0 counts as gated.
+  3. Anchor gain: G_q = clamp(T - l_q, -40, max_gain_db) if l_q > gate, else G_{q-1} (hold), G_{-1} = 0 dB;
+     a_q = float32(10^(G_q / 20)), evaluated in float64 and rounded once.
+  4. Output: for t in quarter q <= Q - 1, with r = t - q hop, in float32 and every operation rounded once, in this order:
+         f = float32(r) / float32(hop);   d = a_{q+1} - a_q;   p = d * f;   g = a_q + p;   out[t] = x[t] * g
+     (no fused multiply-add; ``level_reference`` is this in numpy float32); for the partial tail t >= Q hop: out[t] = x[t] * a_Q.
+     N < hop: Q = 0, the one anchor is gated, a_0 = 1 and out = x exactly.
+  5. Ready rule: with n_known samples seen and the end unknown, outputs [0, ``leveller_ready(n_known, hop)``) =
+     [0, max(0, (n_known // hop - 10) hop)) are final whatever arrives later and whatever N turns out to be: every window they
+     read consists of complete, existing quarters.  At the end all N are final.  Added latency: less than 11 quarters (1.1 s).
+  6. Record (device float64): {min G, max G, anchors evaluated, anchors gated} and G of the last anchor (what the hold carries);
+     exact folds (min, max, integer counts): the values of one call over the whole row.
+
+The span form takes its calls in order; after outputs [0, m) the anchors [0, na) are evaluated and the energies [0, ne) computed,
+(na, ne) = ``leveller_counts(m, hop, Q)``, which is what the caller's device state then holds (the last 32 energies, the last four
+anchor gains, the carried G and the record).
 """
 import math
 
@@ -320,3 +350,152 @@ def limiter_ready(n_known, H, Fw):
     """How many outputs of the fixed-gain limiter are final once ``n_known`` samples of a row of unknown length are known:
     max(0, n_known - 2 H - Fw)."""
     return max(0, int(n_known) - 2 * int(H) - int(Fw))
+
+
+# ---- streaming loudness leveller (module docstring; DESIGN.md 3.17) ---------------------------------------------------------------
+LEVELLER_WARMUP = 2           # quarters the filter runs from zero before a measured quarter
+LEVELLER_BEHIND = 20          # quarters of an anchor's window behind it
+LEVELLER_AHEAD = 10           # ... and from it on
+LEVELLER_MAX_CUT = 40.0       # dB
+LEVELLER_MAX_RATE = 192000
+LEVELLER_MAX_GAIN_RANGE = (0.0, 40.0)   # dB, [lo, hi]
+LEVELLER_GATE_MIN = -70.0     # LUFS; gate in [-70, T)
+LEVELLER_STATE = 64           # float64 values of the device state (VFX_LEVEL_STATE)
+
+
+def check_leveller(target, max_gain_db=12.0, gate=-50.0, fs=None):
+    """(T, max_gain_db, gate) of the leveller as floats: T in [-70, 0) LUFS (not None), ``max_gain_db`` in [0, 40] dB, ``gate``
+    in [-70, T) LUFS; ``fs`` (when given) an integer rate in [4000, 192000].  ValueError otherwise."""
+    T = check_target(target)
+    if T is None:
+        raise ValueError("leveller: the target must be a number in [-70, 0) LUFS (got None)")
+    g = _number(max_gain_db, "leveller_max_gain_db")
+    if not LEVELLER_MAX_GAIN_RANGE[0] <= g <= LEVELLER_MAX_GAIN_RANGE[1]:
+        raise ValueError("leveller_max_gain_db must be in [0, 40] dB (got %r)" % (max_gain_db,))
+    gt = _number(gate, "leveller_gate")
+    if not LEVELLER_GATE_MIN <= gt < T:
+        raise ValueError("leveller_gate must be in [-70, target) LUFS (got %r with a target of %r)" % (gate, target))
+    if fs is not None and _check_rate(fs) > LEVELLER_MAX_RATE:
+        raise ValueError("leveller: rates above %d Hz are refused -- the two-quarter warm-up of the K-weighting no longer decays "
+                         "below fp32 resolution (got %r)" % (LEVELLER_MAX_RATE, fs))
+    return T, g, gt
+
+
+def leveller_chunk(fs):
+    """Samples one lane of the quarter kernel filters: 32 ceil(3 hop / 8192), so that 256 chunks cover a region of 3 hop."""
+    return 32 * ((3 * hop_length(fs) + 8191) // 8192)
+
+
+_LEVELLER_PLANS = {}
+
+
+def leveller_plan(fs):
+    """What the leveller's kernels need at ``fs`` (cached): dict with coef (float64[10]), hop, S = ``leveller_chunk(fs)`` and
+    mpow (float64[8, 4, 4]: M^(2^i), M = ``transition(fs)``^S)."""
+    check_leveller(-16.0, fs=fs)
+    fs = int(fs)
+    hit = _LEVELLER_PLANS.get(fs)
+    if hit is None:
+        S = leveller_chunk(fs)
+        pw = [np.linalg.matrix_power(transition(fs), S)]
+        for _ in range(7):
+            pw.append(pw[-1] @ pw[-1])
+        hit = {"coef": coefficients(fs), "hop": hop_length(fs), "S": S, "mpow": np.ascontiguousarray(np.stack(pw))}
+        _LEVELLER_PLANS[fs] = hit
+    return hit
+
+
+def leveller_ready(n_known, hop):
+    """How many outputs of the leveller are final once ``n_known`` samples of a row of unknown length are known:
+    max(0, (n_known // hop - 10) hop)."""
+    return max(0, (int(n_known) // int(hop) - LEVELLER_AHEAD) * int(hop))
+
+
+def leveller_counts(m, hop, Q=None):
+    """(na, ne): the anchors evaluated and the energies computed once outputs [0, m) of a row of Q complete quarters are done
+    (None: the end is unknown): na = min(Q, (m - 1) // hop + 1) + 1, ne = min(Q, na + 9); (0, 0) for m = 0."""
+    m, hop = int(m), int(hop)
+    if m <= 0:
+        return 0, 0
+    a = (m - 1) // hop + 1
+    na = (a if Q is None else min(a, Q)) + 1
+    ne = na + LEVELLER_AHEAD - 1
+    return na, (ne if Q is None else min(ne, Q))
+
+
+def leveller_energies(x, fs):
+    """E_q, q < N // hop, of one row (step 1 of the definition) in float64: scipy.signal.lfilter over every quarter's own region
+    [max(0, (q - 2) hop), (q + 1) hop) from zero state, with the fp32-rounded coefficients."""
+    from scipy.signal import lfilter
+    check_leveller(-16.0, fs=fs)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("leveller_energies: a row is a 1-D array (got shape %r)" % (x.shape,))
+    hop = hop_length(fs)
+    c = coefficients(fs).astype(np.float32).astype(np.float64)
+    sb, sa, hb, ha = c[0:3], np.array([1.0, c[3], c[4]]), c[5:8], np.array([1.0, c[8], c[9]])
+    Q = x.shape[0] // hop
+    E = np.zeros(Q)
+    for q in range(Q):
+        r0 = max(0, (q - LEVELLER_WARMUP) * hop)
+        y = lfilter(hb, ha, lfilter(sb, sa, x[r0:(q + 1) * hop]))[q * hop - r0:]
+        E[q] = float(np.dot(y, y))
+    return E
+
+
+def leveller_gains(E, N, fs, T, max_gain_db=12.0, gate=-50.0):
+    """Steps 2 and 3 on the quarter energies ``E`` (N // hop of them) of a row of N samples: dict with l (float64[Q + 1], the
+    anchors' loudness; -inf for an empty or silent window), held (bool[Q + 1]: gated), G (float64[Q + 1], dB) and a (float32[Q + 1])."""
+    T, max_gain_db, gate = check_leveller(T, max_gain_db, gate, fs)
+    hop = hop_length(fs)
+    Q = int(N) // hop
+    E = np.asarray(E, dtype=np.float64)
+    if E.shape != (Q,):
+        raise ValueError("leveller_gains: %d samples at %d Hz have %d quarters (got %r energies)" % (N, fs, Q, E.shape))
+    l = np.full(Q + 1, -np.inf)
+    G = np.zeros(Q + 1)
+    gated = np.zeros(Q + 1, dtype=bool)
+    prev = 0.0
+    for q in range(Q + 1):
+        j0, j1 = max(0, q - LEVELLER_BEHIND), min(Q, q + LEVELLER_AHEAD)
+        z = 0.0
+        for j in range(j0, j1):
+            z += float(E[j])
+        if j1 > j0 and z > 0.0:
+            l[q] = -0.691 + 10.0 * math.log10(z / (float(j1 - j0) * float(hop)))
+        if l[q] > gate:
+            prev = min(max(T - l[q], -LEVELLER_MAX_CUT), max_gain_db)
+        else:
+            gated[q] = True
+        G[q] = prev
+    a = np.array([np.float32(10.0 ** (g / 20.0)) for g in G], dtype=np.float32)
+    return {"l": l, "held": gated, "G": G, "a": a}
+
+
+def leveller_apply(x, a, hop):
+    """Step 4 in numpy float32, in the operation order of the definition: x (N,) float32, a (N // hop + 1,) float32."""
+    x = np.asarray(x, dtype=np.float32)
+    a = np.asarray(a, dtype=np.float32)
+    N = x.shape[0]
+    Q = N // hop
+    t = np.arange(N, dtype=np.int64)
+    q = np.minimum(t // hop, Q)
+    body = q < Q
+    f = (t - q * hop).astype(np.float32) / np.float32(hop)
+    a0 = a[q]
+    a1 = a[np.minimum(q + 1, Q)]
+    d = a1 - a0
+    p = d * f
+    g = np.where(body, a0 + p, a0).astype(np.float32)
+    return x * g
+
+
+def level_reference(x, fs, target=-16.0, max_gain_db=12.0, gate=-50.0, stats=None):
+    """The leveller of one row on the host: float64 energies and gains, the float32 output of step 4.  ``stats``: a dict that
+    receives {"min_gain_db", "max_gain_db", "anchors", "gated"} and the arrays of ``leveller_gains``."""
+    x = np.asarray(x, dtype=np.float32)
+    r = leveller_gains(leveller_energies(x, fs), x.shape[0], fs, target, max_gain_db, gate)
+    if stats is not None:
+        stats.update(r, min_gain_db=float(r["G"].min()), max_gain_db=float(r["G"].max()), anchors=int(r["G"].shape[0]),
+                     gated=int(r["held"].sum()))
+    return leveller_apply(x, r["a"], hop_length(fs))

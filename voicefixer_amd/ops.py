@@ -825,6 +825,47 @@ def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, tru
     return rec
 
 
+_LEVELLER_MPOW = {}
+
+
+def level_state(device):
+    """A fresh state of the leveller for one row: device float64 (loudness.LEVELLER_STATE,); the first call (m0 = 0) fills it."""
+    from . import loudness
+    return torch.zeros((loudness.LEVELLER_STATE,), dtype=torch.float64, device=device)
+
+
+def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12.0, gate=-50.0):
+    """Outputs [m0, m1) of the streaming loudness leveller over ONE row from a window of it (vfx_level_span_f32; loudness.py,
+    DESIGN.md 3.17): xw (wlen,) device holds samples [g0, g0 + wlen) of a row of ``n_total`` samples at ``rate`` Hz (None: its
+    end is not known yet, and m1 may not pass loudness.leveller_ready(g0 + wlen, hop)), out (>= m1 - m0,) receives output t at
+    out[t - m0] -- the bits one call over the whole row writes for it.  Calls come in order (m0 = 0 first, then the m1 of the call
+    before) on one ``state`` (``level_state``), which carries the last quarters' energies, the held gain and the record
+    state[:4] = {min G, max G, anchors, gated}.  The window must cover [m0, m1) and the regions of the quarters that become
+    measurable (loudness.leveller_counts), or VfxError.  At most three launches, no synchronisation."""
+    from . import loudness
+    _need_cuda(xw, out, state)
+    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 1 and out.dim() == 1
+    assert (xw.numel() == 0 or xw.stride(0) == 1) and (out.numel() == 0 or out.stride(0) == 1)
+    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
+    target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
+    p = loudness.leveller_plan(rate)
+    m0, m1 = int(m0), int(m1)
+    if m1 - m0 > out.numel():
+        raise _lib.VfxError("level_span: %d outputs into a buffer of %d" % (m1 - m0, out.numel()))
+    key = (str(xw.device), int(rate))
+    mpow = _LEVELLER_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
+        _LEVELLER_MPOW[key] = mpow
+    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
+    h = _lib.lib()
+    nb = h.vfx_level_span_workspace_bytes(max(m1 - m0, 0), p["hop"])
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    check(h.vfx_level_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total), m0, m1, int(rate),
+                               coef, _ptr(mpow), p["S"], target, max_gain_db, gate, _ptr(state), _ptr(out), _ptr(ws), nb,
+                               _stream()), "vfx_level_span_f32")
+
+
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):
     """Loudness report of programmes of several channels (vfx_loudness_report_groups_f32; arguments as loudness_groups): a
     device float64 (G, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample
