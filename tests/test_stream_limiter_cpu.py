@@ -302,3 +302,79 @@ def test_entry_points_declared_mapped_and_bound():
     mk = open(os.path.join(ROOT, "voicefixer_amd", "csrc", "Makefile")).read()
     assert "vfx_limit_span.inc" in mk
     assert '#include "vfx_limit_span.inc"' in open(os.path.join(ROOT, "voicefixer_amd", "csrc", "vfx_loudness.hip")).read()
+
+
+# ---- limit() and level(): the row runner on the host ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fs", [8000, 44100])
+@pytest.mark.parametrize("span", [977, 1 << 22])
+def test_limit_and_level_rows_on_the_host(monkeypatch, fs, span):
+    """``limit`` and ``level`` with the device replaced by the CPU and the launchers by stand-ins: every row goes through a fresh
+    stage as a whole, in runs of ``_span`` outputs that come in order with the row's end known, and the stats arrive as scalars
+    for one array and as lists for a list."""
+    import torch
+    from voicefixer_amd import ops
+    monkeypatch.setattr(api, "_device", lambda: torch.device("cpu"))
+    rng = np.random.default_rng(fs + span % 1000)
+    H, Bk, Fw = loudness.limiter_reach(fs, 3.0, True)
+    for N in (1, 2 * H + Fw - 5, 9 * H + 1500):
+        x = _row(rng, N, [0, N // 3, N // 3 + H, N - 1])
+        runs = -(-N // span)
+        for as_list in (False, True):
+            stand, ends = _StandIn(x, fs, 6.0, -2.0, True, 3.0), []
+
+            def limit_span(xw, g0, n_total, *a, stand=stand, ends=ends, **kw):
+                ends.append(n_total)
+                return stand(xw, g0, n_total, *a, **kw)
+
+            monkeypatch.setattr(ops, "limit_span", limit_span)
+            st = {}
+            got = voicefixer_amd.limit([x] if as_list else x, 6.0, -2.0, True, 3.0, fs, st, span)
+            want = {"max_reduction_db": -loudness.to_db(float(np.float32(stand.g.min()))) + 0.0,
+                    "peak_out_db": loudness.to_db(float(np.abs(stand.out).max()))}
+            if as_list:
+                assert isinstance(got, list) and len(got) == 1 and st == {k: [v] for k, v in want.items()}
+                got = got[0]
+            else:
+                assert st == want
+            assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), stand.out.view(np.uint32))
+            assert stand.calls == runs and stand.done == N and ends == [N] * runs      # (in order: the stand-in asserts m0 == done)
+
+        calls = {"state": 0, "span": 0, "m1": 0}
+
+        def level_state(device):
+            calls["state"] += 1
+            return torch.zeros((loudness.LEVELLER_STATE,), dtype=torch.float64, device=device)
+
+        def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12.0, gate=-50.0):
+            assert (n_total, rate, target, max_gain_db, gate) == (N, fs, -20.0, 6.0, -60.0)
+            assert m0 == calls["m1"] and m0 < m1 <= N and m1 - m0 <= span and g0 <= m0 and m1 <= g0 + xw.numel()
+            out[:m1 - m0] = xw[m0 - g0:m1 - g0]
+            state[2] += 1
+            calls["span"], calls["m1"] = calls["span"] + 1, m1
+
+        monkeypatch.setattr(ops, "level_state", level_state)
+        monkeypatch.setattr(ops, "level_span", level_span)
+        for as_list in (False, True):
+            calls.update(state=0, span=0, m1=0)
+            st = {}
+            got = voicefixer_amd.level([x] if as_list else x, -20.0, 6.0, -60.0, fs, st, span)
+            want = {"min_gain_db": 0.0, "max_gain_db": 0.0, "anchors": runs, "gated": 0}
+            if as_list:
+                assert isinstance(got, list) and len(got) == 1 and st == {k: [v] for k, v in want.items()}
+                got = got[0]
+            else:
+                assert st == want
+            assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), x.view(np.uint32))
+            assert calls == {"state": 1, "span": runs, "m1": N}
+    calls.update(state=0, span=0, m1=0)
+    st = {}
+    assert voicefixer_amd.level(np.zeros(0, np.float32), -20.0, 6.0, -60.0, fs, st, span).shape == (0,)
+    assert calls == {"state": 0, "span": 0, "m1": 0} and st == {"min_gain_db": 0.0, "max_gain_db": 0.0, "anchors": 0, "gated": 0}
+    st = {}
+    assert voicefixer_amd.level([], -20.0, 6.0, -60.0, fs, st, span) == [] and st["anchors"] == []
+    monkeypatch.setattr(ops, "limit_span", None)                 # (an empty row makes no call)
+    st = {}
+    assert voicefixer_amd.limit(np.zeros(0, np.float32), 6.0, -2.0, True, 3.0, fs, st, span).shape == (0,)
+    assert st == {"max_reduction_db": 0.0, "peak_out_db": -np.inf}
+    assert voicefixer_amd.limit([], stats=st) == [] and st == {"max_reduction_db": [], "peak_out_db": []}

@@ -265,3 +265,77 @@ def test_session_bookkeeping_equals_restore_stream(host_ops, mode, rate_in, rate
     if rate_in != 44100 or rate_out != 44100:              # the windows stay a filter length plus a block, not the file
         assert 0 < host_ops["window"] < 12000 and host_ops["span"] >= 3
     assert host_ops["xfade"] == n_chunks - 1               # one cross-fade per chunk boundary
+
+
+# ---- the contract of a span stage (stream._SpanStage), on a toy operator ---------------------------------------------------
+
+def _toy_stage(d, b, span):
+    """Output m = x[m - b] + 2 x[m + d] (indices clipped to the row): ``d`` samples late, reading ``b`` samples behind itself."""
+    import torch
+    from voicefixer_amd import stream
+
+    class Toy(stream._SpanStage):
+        def __init__(self):
+            super().__init__(span)
+            self.calls, self.window, self.at = 0, 0, 0     # (at: the output the next call starts with)
+
+        def _ready(self, n):
+            return max(0, n - d)
+
+        def _run(self, a, e, n_total, y):
+            assert a == self.at and a < e and y.numel() == e - a        # in order, no output twice, no empty call
+            assert self.span is None or e - a <= self.span
+            last = 2 ** 62 if n_total is None else n_total - 1
+            lo, hi = max(a - b, 0), min(e - 1 + d, last)
+            assert self.g0 <= lo and hi < self.g0 + self.win.numel(), "the window does not cover the span"
+            m = torch.arange(a, e)
+            y.copy_(self.win[(m - b).clamp(min=0) - self.g0] + 2.0 * self.win[(m + d).clamp(max=last) - self.g0])
+            self.calls += 1
+            self.window = max(self.window, self.win.numel())
+            self.at = e
+
+        def _keep(self, m1):
+            return m1 - b
+
+    return Toy()
+
+
+@pytest.mark.parametrize("d,b", [(0, 0), (5, 3), (40, 17)])
+@pytest.mark.parametrize("span", [None, 7, 1 << 22])
+def test_span_stage_contract(d, b, span):
+    import torch
+    rng = np.random.default_rng(1000 * d + b)
+    for n in sorted({1, d, d + 1, 1000}):
+        x = torch.from_numpy(rng.integers(-1000, 1000, n).astype(np.float32))
+        m = np.arange(n)
+        want = x.numpy()[np.clip(m - b, 0, None)] + 2.0 * x.numpy()[np.clip(m + d, None, max(n - 1, 0))]
+        whole_stage = _toy_stage(d, b, span)
+        whole = whole_stage.whole(x)
+        assert whole.dtype == torch.float32 and np.array_equal(whole.numpy(), want) and whole_stage.m_done == n
+        assert whole_stage.calls == (0 if n == 0 else 1 if span is None else -(-n // span))
+        for trial in range(5):
+            # random cuts (equal ones: empty blocks); the last trial opens with one sample and an empty block
+            cuts = sorted(int(v) for v in rng.integers(0, n + 1, int(rng.integers(0, 9))))
+            if trial == 4:
+                cuts = sorted([min(1, n), min(1, n), n // 2])
+            st = _toy_stage(d, b, span)
+            got, at, empty_handed, largest = [], 0, 0, 0
+            for cpos in cuts + ([n] if n else []):
+                blk = x[at:cpos].clone()
+                at, largest = cpos, max(largest, blk.numel())
+                got.append(st.feed(blk))
+                empty_handed += got[-1].numel() == 0
+                assert st.n_in == at and st.m_done == st._ready(at) == sum(g.numel() for g in got)
+                assert st.win.numel() <= d + b + 1 + largest
+            got.append(st.finish("cpu"))
+            assert st.m_done == n
+            got = torch.cat(got)
+            assert np.array_equal(got.numpy(), want) and np.array_equal(got.numpy(), whole.numpy())     # once each, in order
+            assert st.window <= d + b + 1 + largest
+            calls = st.calls
+            st.release()
+            assert st.win is None and st.calls == calls and st.m_done == n       # what the stage recorded outlives the window
+            assert trial < 4 or empty_handed > 0
+    never = _toy_stage(d, b, span)
+    y = never.finish("cpu")
+    assert y.shape == (0,) and y.dtype == torch.float32 and never.calls == 0 and never.m_done == 0

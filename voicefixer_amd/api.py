@@ -26,6 +26,9 @@ import torch.nn as nn
 
 from . import audio_io, engine, weights
 from ._lib import VfxError
+# the overlap-add streaming mode lives in stream.py; its names stay reachable here
+from .stream import (LEVEL_SPAN, LIMIT_SPAN, RestoreSession, StreamPlanner, _SpanConverter, _SpanLeveller,  # noqa: F401
+                     _SpanLimiter, _check_stream_mode, _stream_geometry, plan_stream_chunks)
 
 SEG_LENGTH = 44100 * 30  # voicefixer/base.py:117
 
@@ -89,82 +92,6 @@ def plan_batches(sorted_lengths, batch_size, ragged_ratio=0.5, ragged=True, rows
             plan.append(("samples", list(range(i, j))))
         i = j
     return plan
-
-
-def plan_stream_chunks(n, chunk, overlap, min_tail=1024):
-    """Chunk starts / lengths of the overlap-add streaming mode: chunks of ``chunk`` samples every
-    ``chunk - overlap`` samples; the last one is shorter.  A tail that would be too short to restore
-    (<= overlap + ``min_tail`` samples: one cross-fade plus the reflect pad of the STFT; mode 1 passes 1535 because its
-    pre-filter first shortens a chunk to 512 * (len // 512) samples) is merged into its predecessor."""
-    if chunk <= overlap + 1024 or overlap < 0:
-        raise ValueError("chunk must exceed overlap + 1024 samples")
-    hop = chunk - overlap
-    plan = []
-    start = 0
-    while True:
-        length = min(chunk, n - start)
-        plan.append([start, length])
-        if start + length >= n:
-            break
-        start += hop
-    if len(plan) > 1 and plan[-1][1] <= overlap + min_tail:
-        last = plan.pop()
-        plan[-1][1] = last[0] + last[1] - plan[-1][0]
-    return [tuple(c) for c in plan]
-
-
-def _check_stream_mode(mode, what):
-    """The overlap-add modes (``restore_stream``, ``open_stream``) take modes 0 and 1."""
-    if mode == 2:
-        raise NotImplementedError("%s: mode=2 is not built -- its per-segment statistics have no overlap-add form" % what)
-    if mode not in (0, 1):
-        raise ValueError("mode must be 0, 1 or 2")
-
-
-def _stream_geometry(chunk_seconds, overlap_seconds, mode):
-    """(chunk, overlap, min_tail) in 44.1 kHz samples of the overlap-add modes.  Mode 1's pre-filter returns 512 * (len // 512)
-    samples, so its chunks are a multiple of 512 long (every full chunk keeps its length) and its shortest tail is 1535
-    (``plan_stream_chunks``)."""
-    chunk, overlap = int(round(chunk_seconds * 44100)), int(round(overlap_seconds * 44100))
-    if mode == 1:
-        chunk -= chunk % 512
-    return chunk, overlap, 1535 if mode == 1 else 1024
-
-
-class StreamPlanner:
-    """``plan_stream_chunks`` for a waveform whose length is not known yet: ``feed(n_new)`` announces ``n_new`` more
-    samples and returns the chunks (start, length) that are settled now, ``finish()`` the rest.  Everything returned,
-    concatenated, is ``plan_stream_chunks(n, chunk, overlap, min_tail)`` of the final n, whatever the block sizes.
-    ``plan_stream_chunks`` merges a tail of <= overlap + min_tail samples into its predecessor, so the chunk at ``start``
-    is settled at length ``chunk`` only once MORE than start + chunk + min_tail samples are known: that is the latency of
-    a streaming session."""
-
-    def __init__(self, chunk, overlap, min_tail=1024):
-        if chunk <= overlap + 1024 or overlap < 0:
-            raise ValueError("chunk must exceed overlap + 1024 samples")
-        self.chunk, self.overlap, self.min_tail = int(chunk), int(overlap), int(min_tail)
-        self.known = 0       # samples announced so far
-        self.start = 0       # start of the first chunk not yet returned
-        self.finished = False
-
-    def feed(self, n_new):
-        if self.finished:
-            raise RuntimeError("StreamPlanner: feed after finish")
-        if n_new < 0:
-            raise ValueError("StreamPlanner: a negative number of samples")
-        self.known += int(n_new)
-        out = []
-        while self.known > self.start + self.chunk + self.min_tail:
-            out.append((self.start, self.chunk))
-            self.start += self.chunk - self.overlap
-        return out
-
-    def finish(self):
-        if self.finished:
-            raise RuntimeError("StreamPlanner: finish called twice")
-        self.finished = True
-        rest = plan_stream_chunks(self.known - self.start, self.chunk, self.overlap, self.min_tail)
-        return [(self.start + a, length) for a, length in rest]
 
 
 def _check_rate(rate, what="sample_rate"):
@@ -613,7 +540,31 @@ def quantize(wav, bit_depth=16, dither="tpdf", dither_seed=0):
     return out[0] if single else out
 
 
-LIMIT_SPAN = 1 << 22      # outputs per ops.limit_span call of ``limit``: bounds the scratch, changes no bit
+def _span_rows(what, x, stage, stats, _span):
+    """``limit`` and ``level``: one float32 array (N,) -- or every array of a list, each row on its own -- through a fresh
+    ``stage(span)`` (a stream._SpanStage) as a whole row on the device.  ``stats`` (a dict or None) receives the stage's
+    ``stats()``: scalars for one array, lists of one value per row for a list.  Everything is checked before the device is
+    touched."""
+    if stats is not None and not isinstance(stats, dict):
+        raise ValueError("stats must be a dict or None")
+    span = None if _span is None else int(_span)
+    if span is not None and span < 1:
+        raise ValueError("_span must be positive")
+    single = not isinstance(x, (list, tuple))
+    items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
+    for w in items:
+        if w.ndim != 1:
+            raise ValueError("%s: a row is a 1-D array of samples (got shape %r)" % (what, w.shape))
+    outs, recs = [], []
+    dev = _device() if items else None
+    for w in items:
+        st = stage(span)
+        outs.append(st.whole(torch.from_numpy(np.ascontiguousarray(w)).to(dev)).cpu().numpy())
+        recs.append(st.stats())
+    if stats is not None:
+        for key in (recs[0] if recs else stage(span).stats()):      # (an empty list reports its keys too)
+            stats[key] = recs[0][key] if single else [r[key] for r in recs]
+    return outs[0] if single else outs
 
 
 def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, sample_rate=44100, stats=None, _span=None):
@@ -625,46 +576,15 @@ def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, 
     only approximately -- lower ``peak_ceiling`` for a margin.  Where no sample within reach is above the ceiling the output is
     float32(gL) x exactly.  ``stats``: a dict that receives {"max_reduction_db", "peak_out_db"} (lists of one value per row
     when a list went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span."""
-    from . import loudness as ld, ops
+    from . import loudness as ld
     gain_db = ld.check_gain(gain_db)
     if gain_db is None:
         raise ValueError("limit: gain_db must be a number (0.0: the limiter alone)")
     peak_ceiling, true_peak = ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
     rate = _check_rate(sample_rate)
-    H, Bk, Fw = ld.limiter_reach(rate, lookahead_ms, true_peak)
-    if stats is not None and not isinstance(stats, dict):
-        raise ValueError("stats must be a dict or None")
-    span = LIMIT_SPAN if _span is None else int(_span)
-    if span < 1:
-        raise ValueError("_span must be positive")
-    single = not isinstance(x, (list, tuple))
-    items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
-    for w in items:
-        if w.ndim != 1:
-            raise ValueError("limit: a row is a 1-D array of samples (got shape %r)" % (w.shape,))
-    outs, recs = [], []
-    dev = _device() if items else None
-    for w in items:
-        n = w.shape[0]
-        xd = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
-        y = torch.empty((n,), dtype=torch.float32, device=dev)
-        rec = None
-        for m0 in range(0, n, span):
-            m1 = min(m0 + span, n)
-            lo, hi = max(m0 - 2 * H - Bk, 0), min(m1 + 2 * H + Fw, n)      # the minimal window, as a view of the row
-            r = ops.limit_span(xd[lo:hi], lo, n, rate, gain_db, m0, m1, y[m0:m1], peak_ceiling, true_peak, lookahead_ms)
-            rec = r if rec is None else torch.stack([torch.minimum(rec[0], r[0]), torch.maximum(rec[1], r[1])])
-        outs.append(y.cpu().numpy())
-        recs.append((1.0, 0.0) if rec is None else tuple(float(v) for v in rec.cpu().numpy()))
-    if stats is not None:
-        red = [-ld.to_db(g) + 0.0 for g, _ in recs]
-        pk = [ld.to_db(p) for _, p in recs]
-        stats["max_reduction_db"] = red[0] if single else red
-        stats["peak_out_db"] = pk[0] if single else pk
-    return outs[0] if single else outs
-
-
-LEVEL_SPAN = 1 << 22      # outputs per ops.level_span call of ``level``: bounds the scratch, changes no bit
+    ld.limiter_reach(rate, lookahead_ms, true_peak)      # (ValueError: a look-ahead outside [1, 4096] samples)
+    return _span_rows("limit", x, lambda span: _SpanLimiter(rate, gain_db, peak_ceiling, true_peak, lookahead_ms, span),
+                      stats, _span)
 
 
 def level(x, target=-16.0, max_gain_db=12.0, gate=-50.0, sample_rate=44100, stats=None, _span=None):
@@ -678,30 +598,7 @@ def level(x, target=-16.0, max_gain_db=12.0, gate=-50.0, sample_rate=44100, stat
     from . import loudness as ld
     rate = _check_rate(sample_rate)
     target, max_gain_db, gate = ld.check_leveller(target, max_gain_db, gate, rate)
-    if stats is not None and not isinstance(stats, dict):
-        raise ValueError("stats must be a dict or None")
-    span = LEVEL_SPAN if _span is None else int(_span)
-    if span < 1:
-        raise ValueError("_span must be positive")
-    single = not isinstance(x, (list, tuple))
-    items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
-    for w in items:
-        if w.ndim != 1:
-            raise ValueError("level: a row is a 1-D array of samples (got shape %r)" % (w.shape,))
-    outs, recs = [], []
-    dev = _device() if items else None
-    for w in items:
-        lv = _SpanLeveller(rate, target, max_gain_db, gate, span)
-        if w.shape[0] == 0:
-            outs.append(np.zeros((0,), np.float32))
-        else:
-            xd = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
-            outs.append(torch.cat([lv.feed(xd), lv.finish(dev)]).cpu().numpy())
-        recs.append(lv.stats())
-    if stats is not None:
-        for key in ("min_gain_db", "max_gain_db", "anchors", "gated"):
-            stats[key] = recs[0][key] if single else [r[key] for r in recs]
-    return outs[0] if single else outs
+    return _span_rows("level", x, lambda span: _SpanLeveller(rate, target, max_gain_db, gate, span), stats, _span)
 
 
 class Vocoder(nn.Module):
@@ -1349,13 +1246,6 @@ class VoiceFixer(nn.Module):
         for the whole output, bit for bit, less than 1.1 s late; output rates up to 192 kHz.  With a leveller ``limiter=True``
         needs no ``gain_db`` (the limiter then runs at 0 dB; a ``gain_db`` follows the leveller as it follows the converter
         today); ``session.leveller_stats`` reports {"min_gain_db", "max_gain_db", "anchors", "gated"}."""
-        from . import loudness as ld
-        if leveller is not None:
-            ld.check_leveller(leveller, leveller_max_gain_db, leveller_gate)
-        if _check_limiter(limiter, limiter_lookahead_ms) and ld.check_gain(gain_db) is None and leveller is None:
-            raise NotImplementedError("open_stream: the limiter behind a loudness target is not built -- it follows a whole-file "
-                                      "measurement; give a fixed gain (gain_db=...) for the session's fixed-gain limiter, or use "
-                                      "restore_inmem or restore_folder")
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
                               output_sample_rate, bit_depth, dither, dither_seed, gain_db, peak_ceiling, true_peak, limiter,
                               limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate)
@@ -1805,362 +1695,3 @@ class VoiceFixer(nn.Module):
             audio_io.save_pcm(out_np_wav, output, job.rate_out, job.bit_depth, channels_first=True)
             return
         audio_io.save_wave(out_np_wav, fname=output, sample_rate=job.rate_out, channels_first=True)
-
-
-class _SpanConverter:
-    """Rate conversion of ONE row that arrives in pieces (ops.resample_span): ``feed`` takes the next samples (device
-    (k,)) and returns the outputs that read nothing beyond what has arrived (audio_io.ready_outputs), ``finish`` the rest
-    up to ceil(n * up / down) with the row's end known.  Every output has the bits of ops.resample_rows on the whole row.
-    Kept between calls: the samples future outputs still read (at most J + down / up + 1 of them) and their global offset."""
-
-    def __init__(self, rate_in, rate_out):
-        self.up, self.down = audio_io.rate_ratio(rate_in, rate_out)
-        _, self.J, self.c = audio_io.hq_bank(self.up, self.down)
-        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
-        self.g0 = 0
-        self.n_in = 0        # samples fed
-        self.m_done = 0      # outputs returned
-
-    def feed(self, x):
-        self.win = x if self.win is None else torch.cat([self.win, x])
-        self.n_in += x.numel()
-        return self._emit(audio_io.ready_outputs(self.n_in, self.up, self.down, self.c), None)
-
-    def finish(self, device):
-        if self.win is None:
-            return torch.empty((0,), dtype=torch.float32, device=device)
-        return self._emit(-(-self.n_in * self.up // self.down), self.n_in)
-
-    def _emit(self, m1, n_total):
-        from . import ops
-        m0, m1 = self.m_done, max(m1, self.m_done)
-        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
-        if m1 > m0:
-            ops.resample_span(self.win, self.g0, n_total, self.up, self.down, m0, m1, y)
-        self.m_done = m1
-        # drop what no later output reads: output m1 starts at lo(m1) (one sample always stays: a window is never empty)
-        keep = min(max(audio_io.span_window(m1, m1 + 1, self.up, self.down, self.J, self.c)[0], 0), self.n_in - 1)
-        if keep > self.g0:
-            self.win = self.win[keep - self.g0:].clone()
-            self.g0 = keep
-        return y
-
-
-class _SpanLimiter:
-    """The fixed-gain look-ahead limiter F (loudness.py) of ONE row that arrives in pieces (ops.limit_span): ``feed`` takes the
-    next samples (device (k,)) and returns the outputs that became final with them (loudness.limiter_ready), ``finish`` the rest
-    with the row's end known.  Every output has the bits of one span over the whole row.  Kept between calls: the samples that
-    later outputs read (at most 4 H + Bk + Fw + 1 of them beyond a block) with their global offset, and the calls' records
-    {min g, max |out|} -- device scalars, folded exactly (min and max) and read by ``stats()`` only."""
-
-    def __init__(self, rate, gain_db, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0):
-        from . import loudness
-        self.rate, self.gain_db, self.ceiling, self.true_peak, self.ms = rate, gain_db, peak_ceiling, true_peak, lookahead_ms
-        self.H, self.Bk, self.Fw = loudness.limiter_reach(rate, lookahead_ms, true_peak)
-        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
-        self.g0 = 0
-        self.n_in = 0        # samples fed
-        self.m_done = 0      # outputs returned
-        self.recs = []       # device float64 (2,) each: {min g, max |out|} of the calls so far, folded when read
-
-    def feed(self, x):
-        from . import loudness
-        self.win = x if self.win is None else torch.cat([self.win, x])
-        self.n_in += x.numel()
-        return self._emit(loudness.limiter_ready(self.n_in, self.H, self.Fw), None)
-
-    def finish(self, device):
-        if self.win is None:
-            return torch.empty((0,), dtype=torch.float32, device=device)
-        return self._emit(self.n_in, self.n_in)
-
-    def _emit(self, m1, n_total):
-        from . import ops
-        m0, m1 = self.m_done, max(m1, self.m_done)
-        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
-        if m1 > m0:
-            rec = ops.limit_span(self.win, self.g0, n_total, self.rate, self.gain_db, m0, m1, y, self.ceiling, self.true_peak,
-                                 self.ms)
-            self.recs.append(rec)
-            if len(self.recs) >= 256:                         # (bounded, whatever the session's length)
-                self.recs = [self._fold()]
-        self.m_done = m1
-        # drop what no later output reads: output m1 reads from m1 - 2 H - Bk on (one sample always stays)
-        keep = min(max(m1 - 2 * self.H - self.Bk, 0), self.n_in - 1)
-        if keep > self.g0:
-            self.win = self.win[keep - self.g0:].clone()
-            self.g0 = keep
-        return y
-
-    def _fold(self):
-        r = torch.stack(self.recs)
-        return torch.stack([r[:, 0].min(), r[:, 1].max()])
-
-    def stats(self):
-        """{"max_reduction_db", "peak_out_db"} over what has been returned (reads the device record: the one synchronisation)."""
-        from . import loudness
-        if len(self.recs) > 1:
-            self.recs = [self._fold()]
-        gmin, peak = (float(v) for v in self.recs[0].cpu().numpy()) if self.recs else (1.0, 0.0)
-        return {"max_reduction_db": -loudness.to_db(gmin) + 0.0, "peak_out_db": loudness.to_db(peak)}
-
-
-class _SpanLeveller:
-    """The loudness leveller (loudness.py) of ONE row that arrives in pieces (ops.level_span): ``feed`` takes the
-    next samples (device (k,)) and returns the outputs that became final with them (loudness.leveller_ready), ``finish`` the rest
-    with the row's end known.  Every output has the bits of one call over the whole row.  Kept between calls: the samples from
-    the first output not yet returned on (fewer than 11 quarters, 1.1 s, beyond a block: the energies behind them live in the
-    device state), their global offset and the device state with the record, read by ``stats()`` only.  Nothing touches the
-    device before the first ``feed``."""
-
-    def __init__(self, rate, target, max_gain_db=12.0, gate=-50.0, span=None):
-        from . import loudness
-        self.target, self.max_gain_db, self.gate = loudness.check_leveller(target, max_gain_db, gate, rate)
-        self.rate, self.hop = int(rate), loudness.hop_length(rate)
-        self.span = LEVEL_SPAN if span is None else int(span)
-        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
-        self.g0 = 0
-        self.n_in = 0        # samples fed
-        self.m_done = 0      # outputs returned
-        self.state = None    # device float64 (loudness.LEVELLER_STATE,)
-
-    def feed(self, x):
-        from . import loudness
-        self.win = x if self.win is None else torch.cat([self.win, x])
-        self.n_in += x.numel()
-        return self._emit(loudness.leveller_ready(self.n_in, self.hop), None)
-
-    def finish(self, device):
-        if self.win is None:
-            return torch.empty((0,), dtype=torch.float32, device=device)
-        return self._emit(self.n_in, self.n_in)
-
-    def _emit(self, m1, n_total):
-        from . import loudness, ops
-        m0, m1 = self.m_done, max(m1, self.m_done)
-        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
-        if self.state is None and m1 > m0:
-            self.state = ops.level_state(self.win.device)
-        for a in range(m0, m1, self.span):
-            b = min(a + self.span, m1)
-            ops.level_span(self.win, self.g0, n_total, self.rate, self.target, a, b, y[a - m0:b - m0], self.state,
-                           self.max_gain_db, self.gate)
-        self.m_done = m1
-        # drop what no later call reads: the next outputs themselves and the region of the next quarter to be measured, which
-        # starts two quarters before it (one sample always stays: a window is never empty)
-        ne = loudness.leveller_counts(m1, self.hop)[1]
-        keep = min(m1, max(ne - loudness.LEVELLER_WARMUP, 0) * self.hop, self.n_in - 1)
-        if keep > self.g0:
-            self.win = self.win[keep - self.g0:].clone()
-            self.g0 = keep
-        return y
-
-    def stats(self):
-        """{"min_gain_db", "max_gain_db", "anchors", "gated"} over what has been returned (reads the device state: the one
-        synchronisation); zeros before the first anchor."""
-        if self.state is None:
-            return {"min_gain_db": 0.0, "max_gain_db": 0.0, "anchors": 0, "gated": 0}
-        v = self.state[:7].cpu().numpy()
-        if v[6] != 0.0:
-            raise VfxError("leveller: the spans of a row did not come in order")
-        return {"min_gain_db": float(v[0]), "max_gain_db": float(v[1]), "anchors": int(v[2]), "gated": int(v[3])}
-
-
-class RestoreSession:
-    """``VoiceFixer.open_stream``: the overlap-add long-form mode as a push-style session on the device.
-
-        s = vf.open_stream(chunk_seconds=30.0, overlap_seconds=1.0, sample_rate=16000, output_sample_rate=48000)
-        y = s.push(block)        # float32 (k,) at sample_rate, any k >= 0 -> float32 numpy (1, j) at the output rate, j >= 0
-        y = s.finish()           # the rest; afterwards push / finish raise RuntimeError
-        s.position               # output samples delivered so far
-
-    Definition: with X the concatenation of all pushed blocks, X44 its whole-row conversion to 44.1 kHz (``convert_rows``),
-    Y44 = ``restore_stream(X44, chunk_seconds, overlap_seconds, batch_size, mode)`` and Z = Y44 converted as a whole row to
-    the output rate by ops.resample_rows (Z = Y44 at 44.1 kHz), the results of all ``push`` calls and of ``finish``
-    concatenate to Z.  NO second peak rule is applied to a converted output (``convert_output`` applies one to whole
-    files): a stretch leaves before the file's peak exists, so a converted stretch may overshoot 1.0 slightly.
-    Four stages, all on the device and on the current stream: the input converter (ops.resample_span on the samples that
-    future outputs still read; a copy at 44.1 kHz), the chunker (``StreamPlanner``; settled chunks of equal length go
-    through the path in groups of up to ``batch_size``), the stitcher (ops.xfade of the previous chunk's last ``overlap``
-    samples with the next chunk's head) and the output converter (the input converter again, fed with the final 44.1 kHz
-    stretches, which therefore never visit the host).  Held between calls: the 44.1 kHz samples from the next chunk's
-    start on, one overlap, two filter windows -- O(chunk + the largest block), whatever has been pushed.  A chunk is
-    settled once more than chunk + min_tail samples (1024; mode 1: 1535) beyond its start are known at 44.1 kHz: the
-    session's latency.  Loudness normalisation to a TARGET and a trim need the whole file and are not offered here (nor are
-    several channels); a FIXED gain (``gain_db``) is, alone or followed by the fixed-gain look-ahead limiter (``limiter=True``;
-    loudness.py) under ``peak_ceiling`` at the output rate, carried across stretches like the converters and
-    2 H + 93 samples late; ``limiter_stats`` is then {"max_reduction_db", "peak_out_db"} over what has been delivered (None
-    without a limiter).  The limiter bounds every sample by the ceiling, the inter-sample peak only approximately: lower
-    ``peak_ceiling`` for a margin.  The word-length reduction (``bit_depth``) is offered too: its dither is a function of a
-    sample's position, not of the file.  A loudness target without the whole file is the LEVELLER's (``leveller=T`` LUFS,
-    ``leveller_max_gain_db``, ``leveller_gate``; loudness.py; ``voicefixer_amd.level`` on the whole output, bit
-    for bit): a gain that follows the loudness of the 3 s around every 100 ms anchor, carried across stretches like the
-    converters and less than 1.1 s late; with it ``limiter=True`` needs no ``gain_db`` (the limiter then runs at 0 dB) and
-    ``leveller_stats`` is {"min_gain_db", "max_gain_db", "anchors", "gated"} (None without a leveller).  The stages behind the
-    stitcher: output converter, leveller, gain / limiter, word length, host.
-    A context manager; leaving it without ``finish`` discards what is pending."""
-
-    def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
-                 sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0, gain_db=None,
-                 peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0, leveller=None,
-                 leveller_max_gain_db=12.0, leveller_gate=-50.0):
-        from . import loudness as ld
-        _check_stream_mode(mode, "open_stream")
-        self._word = _Output(bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)     # (checks the three)
-        self._dtype = {None: np.float32, 16: np.int16, 24: np.int32}[self._word.bit_depth]
-        self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
-        gain_db, peak_ceiling, true_peak = ld.check_gain(gain_db), ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
-        limiter, limiter_lookahead_ms = ld.check_limiter(limiter, limiter_lookahead_ms)
-        if limiter and gain_db is None and leveller is None:
-            raise NotImplementedError("RestoreSession: limiter=True needs a fixed gain (gain_db=...) or a leveller (leveller=...)")
-        self._gain = None if gain_db is None else float(np.float32(10.0 ** (gain_db / 20.0)))
-        # (check_leveller: ValueError for an output rate above 192 kHz too; nothing touches the device before the first stretch)
-        self._lev = (_SpanLeveller(self._rate_out, leveller, leveller_max_gain_db, leveller_gate)
-                     if leveller is not None else None)
-        # (limiter_reach: ValueError for a look-ahead outside [1, 4096] samples at the output rate; behind a leveller and
-        # without a gain the limiter runs at 0 dB)
-        self._lim = (_SpanLimiter(self._rate_out, 0.0 if gain_db is None else gain_db, peak_ceiling, true_peak,
-                                  limiter_lookahead_ms) if limiter else None)
-        for r in (self._rate_in, self._rate_out):
-            if r != 44100 and max(audio_io.rate_ratio(r, 44100)) > audio_io.DEVICE_MAX_RATIO:
-                raise ValueError("open_stream: the device resampler does not take the ratio of %d Hz to 44100 Hz" % r)
-        if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
-            raise ValueError("batch_size must be a positive integer")
-        chunk, ov, min_tail = _stream_geometry(chunk_seconds, overlap_seconds, mode)
-        self._planner = StreamPlanner(chunk, ov, min_tail)     # (ValueError: chunk <= overlap + 1024)
-        self._vf, self._mode, self._voc, self._batch, self._ov = vf, mode, your_vocoder_func, int(batch_size), ov
-        self._conv_in = _SpanConverter(self._rate_in, 44100) if self._rate_in != 44100 else None
-        self._conv_out = _SpanConverter(44100, self._rate_out) if self._rate_out != 44100 else None
-        self._n_in = 0           # samples pushed
-        self._buf = None         # device (k,): 44.1 kHz samples [b0, b0 + k)
-        self._b0 = 0
-        self._tail = None        # device (ov,): the previous chunk's stitched last ``ov`` samples
-        self._fade = None        # device (ov,): restore_stream's fade-in ramp, uploaded once
-        self._closed = False
-        self.position = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def close(self):
-        """Drop what is pending (nothing more is delivered); ``push`` and ``finish`` raise afterwards."""
-        self._closed = True
-        self._buf = self._tail = self._fade = self._conv_in = self._conv_out = None
-        if self._lim is not None:
-            self._lim.win = None     # (the record stays: limiter_stats outlives the session)
-        if self._lev is not None:
-            self._lev.win = None     # (so does the leveller's state)
-
-    @property
-    def limiter_stats(self):
-        """{"max_reduction_db": -20 log10(min g), "peak_out_db": 20 log10(max |out|)} over what has been delivered -- exact folds,
-        the values of one call over the whole row -- or None without a limiter."""
-        return None if self._lim is None else self._lim.stats()
-
-    @property
-    def leveller_stats(self):
-        """{"min_gain_db", "max_gain_db", "anchors", "gated"} of the leveller over what has been delivered -- exact folds, the
-        values of ``level`` over the whole output -- or None without a leveller."""
-        return None if self._lev is None else self._lev.stats()
-
-    @torch.no_grad()
-    def push(self, block):
-        """The next ``block`` (float32 (k,), k >= 0, at the session's input rate) -> the output that became final with it:
-        float32 numpy (1, j) at the output rate, j >= 0."""
-        if self._closed:
-            raise RuntimeError("RestoreSession: push after finish / close")
-        block = np.asarray(block, dtype=np.float32)
-        if block.ndim != 1:
-            raise ValueError("push: a block is a 1-D array of samples (got shape %r)" % (block.shape,))
-        if block.shape[0] == 0:
-            return np.zeros((1, 0), self._dtype)
-        pipe = self._vf._get_pipe()
-        x = torch.from_numpy(np.ascontiguousarray(block)).to(pipe.device)
-        self._n_in += block.shape[0]
-        if self._conv_in is not None:
-            x = self._conv_in.feed(x)
-        self._buf = x if self._buf is None else torch.cat([self._buf, x])
-        return self._deliver(pipe, self._restore(pipe, self._planner.feed(x.numel()), False), False)
-
-    @torch.no_grad()
-    def finish(self):
-        """The rest of the output, float32 numpy (1, j); the session is closed afterwards.  ValueError, nothing launched,
-        when fewer 44.1 kHz samples than ``VoiceFixer.MIN_SAMPLES[mode]`` were pushed."""
-        if self._closed:
-            raise RuntimeError("RestoreSession: finish called twice (or after close)")
-        try:
-            n44 = audio_io.converted_length(self._n_in, self._rate_in, 44100)
-            if n44 < VoiceFixer.MIN_SAMPLES[self._mode]:
-                raise ValueError("RestoreSession: %d samples at 44.1 kHz were pushed, mode %d needs at least %d"
-                                 % (n44, self._mode, VoiceFixer.MIN_SAMPLES[self._mode]))
-            pipe = self._vf._get_pipe()
-            n_new = 0
-            if self._conv_in is not None:
-                x = self._conv_in.finish(pipe.device)
-                self._buf = torch.cat([self._buf, x])
-                n_new = x.numel()
-            plan = self._planner.feed(n_new) + self._planner.finish()
-            return self._deliver(pipe, self._restore(pipe, plan, True), True)
-        finally:
-            self.close()
-
-    def _restore(self, pipe, plan, at_end):
-        """The settled chunks ``plan`` through the path and the stitcher; returns their final 44.1 kHz stretches (device)."""
-        from . import ops
-        ov, out, i = self._ov, [], 0
-        while i < len(plan):
-            length = plan[i][1]
-            grp = [c for c in plan[i:i + self._batch] if c[1] == length]
-            seg = torch.stack([self._buf[a - self._b0:a - self._b0 + length] for a, _ in grp])
-            res = pipe.run_checked(lambda: VoiceFixer._restore_segments(pipe, seg, length, self._mode, self._voc))
-            got = res.shape[1]          # == length in mode 0; 512 * (length // 512) in mode 1
-            for k, (a, _) in enumerate(grp):
-                y = res[k]
-                if a > 0 and ov > 0:    # cross-fade with what the previous chunk left in the overlap, in place
-                    ops.xfade(self._tail, y[:ov], self._fade, y[:ov])
-                last = at_end and i + k == len(plan) - 1
-                if last:
-                    out.append(y)
-                else:
-                    out.append(y[:got - ov])
-                    if ov > 0:
-                        if self._fade is None:
-                            self._fade = torch.from_numpy(np.arange(ov, dtype=np.float32) / max(ov, 1)).to(pipe.device)
-                        self._tail = y[got - ov:].clone()
-            i += len(grp)
-        # the next chunk starts at the planner's start: nothing before it is read again
-        if not at_end and self._planner.start > self._b0:
-            self._buf = self._buf[self._planner.start - self._b0:].clone()
-            self._b0 = self._planner.start
-        return out
-
-    def _deliver(self, pipe, stretches, at_end):
-        """Final 44.1 kHz stretches -> the host, through the output converter when the output rate differs, the leveller, the fixed gain or
-        the fixed-gain limiter when the session has one and, with a ``bit_depth``, through the word-length reduction: sample k of
-        what is delivered has the absolute index position + k."""
-        if self._conv_out is not None:
-            stretches = [self._conv_out.feed(y) for y in stretches if y.numel()]
-            if at_end:
-                stretches.append(self._conv_out.finish(pipe.device))
-        if self._lev is not None:
-            stretches = [self._lev.feed(y) for y in stretches if y.numel()]
-            if at_end:
-                stretches.append(self._lev.finish(pipe.device))
-        if self._lim is not None:
-            stretches = [self._lim.feed(y) for y in stretches if y.numel()]
-            if at_end:
-                stretches.append(self._lim.finish(pipe.device))
-        elif self._gain is not None:
-            stretches = [y * self._gain for y in stretches]      # (float32(gL) y: one rounding per sample)
-        if not stretches:
-            return np.zeros((1, 0), self._dtype)
-        y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches))[None]
-        if self._word.bit_depth is not None and y.shape[1] > 0:
-            y, _ = self._word.quantize(y, [y.shape[1]], None, self.position)
-        y = y.cpu().numpy().astype(self._dtype, copy=False)
-        self.position += y.shape[1]
-        return y

@@ -505,17 +505,24 @@ def resample_rows(x, n_rows, y, up, down, ny_max=None, row_index=None):
 INT64_MAX = 2 ** 63 - 1
 
 
+def _check_span(name, xw, out, m0, m1):
+    """What the ``*_span`` wrappers ask of their window and their output: float32, 1-D, contiguous, on the device, and room for
+    the m1 - m0 outputs (VfxError otherwise).  Returns (m0, m1) as ints."""
+    _need_cuda(xw, out)
+    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 1 and out.dim() == 1
+    assert (xw.numel() == 0 or xw.stride(0) == 1) and (out.numel() == 0 or out.stride(0) == 1)
+    m0, m1 = int(m0), int(m1)
+    if m1 - m0 > out.numel():
+        raise _lib.VfxError("%s: %d outputs into a buffer of %d" % (name, m1 - m0, out.numel()))
+    return m0, m1
+
+
 def resample_span(xw, g0, n_total, up, down, m0, m1, y):
     """Outputs [m0, m1) of ONE row's rate conversion from a window of it (vfx_resample_span_f32): xw (wlen,) device holds
     samples [g0, g0 + wlen) of a row of ``n_total`` samples (None: its end is not known yet), y (>= m1 - m0,) receives
     output m at y[m - m0] -- the bits ops.resample_rows writes for output m of the whole row.  The window must cover what
     the span reads (audio_io.span_window clipped to [0, n_total)), or VfxError.  The bank is resample_bank's."""
-    _need_cuda(xw, y)
-    assert xw.dtype == torch.float32 and y.dtype == torch.float32 and xw.dim() == 1 and y.dim() == 1
-    assert (xw.numel() == 0 or xw.stride(0) == 1) and (y.numel() == 0 or y.stride(0) == 1)
-    m0, m1 = int(m0), int(m1)
-    if m1 - m0 > y.numel():
-        raise _lib.VfxError("resample_span: %d outputs into a buffer of %d" % (m1 - m0, y.numel()))
+    m0, m1 = _check_span("resample_span", xw, y, m0, m1)
     bank, J, c = resample_bank(xw.device, int(up), int(down))
     check(_lib.lib().vfx_resample_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total),
                                            _ptr(bank), J, int(up), int(down), c, m0, m1, _ptr(y), _stream()),
@@ -799,18 +806,13 @@ def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, tru
     (loudness.limiter_reach), or VfxError.  Returns the record, a device float64 (2,) of {min g, max |out|} over the span
     ({1, 0} for an empty one).  Three launches, no synchronisation."""
     from . import loudness
-    _need_cuda(xw, out)
-    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 1 and out.dim() == 1
-    assert (xw.numel() == 0 or xw.stride(0) == 1) and (out.numel() == 0 or out.stride(0) == 1)
+    m0, m1 = _check_span("limit_span", xw, out, m0, m1)
     gain_db = loudness.check_gain(gain_db)
     if gain_db is None:
         raise ValueError("limit_span: the limiter needs a gain (gain_db=...)")
     ceiling_db = loudness.check_ceiling(ceiling_db)
     true_peak = loudness.check_true_peak(true_peak)
     H = loudness.limiter_window(rate, lookahead_ms)[0]
-    m0, m1 = int(m0), int(m1)
-    if m1 - m0 > out.numel():
-        raise _lib.VfxError("limit_span: %d outputs into a buffer of %d" % (m1 - m0, out.numel()))
     if m1 == m0:
         return torch.tensor([1.0, 0.0], dtype=torch.float64).to(xw.device)
     R = loudness.oversampling(rate) if true_peak else 1
@@ -843,15 +845,11 @@ def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12
     state[:4] = {min G, max G, anchors, gated}.  The window must cover [m0, m1) and the regions of the quarters that become
     measurable (loudness.leveller_counts), or VfxError.  At most three launches, no synchronisation."""
     from . import loudness
-    _need_cuda(xw, out, state)
-    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 1 and out.dim() == 1
-    assert (xw.numel() == 0 or xw.stride(0) == 1) and (out.numel() == 0 or out.stride(0) == 1)
+    m0, m1 = _check_span("level_span", xw, out, m0, m1)
+    _need_cuda(state)
     assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
     target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
     p = loudness.leveller_plan(rate)
-    m0, m1 = int(m0), int(m1)
-    if m1 - m0 > out.numel():
-        raise _lib.VfxError("level_span: %d outputs into a buffer of %d" % (m1 - m0, out.numel()))
     key = (str(xw.device), int(rate))
     mpow = _LEVELLER_MPOW.get(key)
     if mpow is None:
