@@ -606,6 +606,49 @@ int vfx_level_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_tota
                        const double* coef, const double* mpow, int S, double target, double max_gain_db, double gate,
                        double* state, float* out, void* ws, size_t ws_bytes, vfx_stream_t stream);
 
+/* ---- the span stages of a session of several channels: ONE gain curve per programme ------------------------- */
+
+/* Bytes of the workspace of vfx_limit_span_rows_f32 for spans of up to n_span outputs per channel at look-ahead H (0 on bad
+ * arguments: those of vfx_limit_span_workspace_bytes, or C outside [1, 8]).  One envelope per programme: the size does not grow
+ * with C. */
+size_t vfx_limit_span_rows_workspace_bytes(int64_t n_span, int H, int C);
+
+/* Outputs [m0, m1) of the LINKED fixed-gain limiter over a programme of C channels of n_total samples each: vfx_limit_span_f32
+ * with the envelope e[n] = max over the channels of the per-channel envelope (|x_c[n]| and, at R > 1, its R interpolated values),
+ * so that every channel is multiplied by the same float(gain) g[n].  Channel ch's window is xw + ch w_stride (wlen samples from
+ * g0 of the row, as there), its outputs go to out + ch out_stride; g0, wlen, n_total, m0, m1 hold for every channel.  Every
+ * output has the bits of the single span [0, n_total), whatever the split, the strides and the alignment; C = 1 gives the bits
+ * and the record of vfx_limit_span_f32.  Ready rule, window coverage (per channel), bank / J / c, ws alignment: as there, with ws
+ * >= vfx_limit_span_rows_workspace_bytes(m1 - m0, H, C).  Nothing outside a channel's window is read.  record: device float64[2]
+ * = {min g, max |out| over all channels} over [m0, m1).  Three launches (envelope, limit, fold) whatever the span and C; no
+ * host synchronisation.  An empty span is VFX_OK, launches nothing and leaves record alone.
+ * VFX_EINVAL, nothing launched: everything vfx_limit_span_f32 refuses; C outside [1, 8]; w_stride < wlen; out_stride < m1 - m0;
+ * the block of the outputs [out, out + (C - 1) out_stride + m1 - m0) overlapping the block of the windows
+ * [xw, xw + (C - 1) w_stride + wlen). */
+int vfx_limit_span_rows_f32(const float* xw, int64_t w_stride, int C, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0,
+                            int64_t m1, double gain, double ceiling_db, int H, const float* bank, int J, int R, int c, float* out,
+                            int64_t out_stride, double* record, void* ws, size_t ws_bytes, vfx_stream_t stream);
+
+/* Bytes of the workspace of vfx_level_span_rows_f32 (0 on bad arguments: those of vfx_level_span_workspace_bytes, or C outside
+ * [1, 8]): 8 bytes per quarter of the span and channel on top of the mono size. */
+size_t vfx_level_span_rows_workspace_bytes(int64_t n_span, int hop, int C);
+
+/* Outputs [m0, m1) of the LINKED loudness leveller over a programme of C channels: vfx_level_span_f32 with the quarter energy
+ *   E_q = sum_c weight[c] E_{q,c}   (float64, c ascending from 0.0, every product and every sum rounded on its own),
+ * E_{q,c} the quarter energy of channel c as defined there -- BS.1770-4's sum over the channels -- and the one ramp applied to
+ * every channel.  Channel ch's window is xw + ch w_stride, its outputs go to out + ch out_stride.  weight: C HOST doubles,
+ * finite and >= 0 (copied into the kernel arguments: nothing is uploaded).  state: ONE device float64[VFX_LEVEL_STATE] per
+ * programme, laid out as there; it holds the linked energies.  Order of the calls, ready rule, window coverage (per channel),
+ * coef / mpow / S: as there.  C = 1 with weight {1} gives the bits and the state of vfx_level_span_f32.  ws: >=
+ * vfx_level_span_rows_workspace_bytes(m1 - m0, hop, C) bytes, 16-byte aligned.  At most three launches (new quarters of all
+ * channels, anchors, apply) whatever C; no host synchronisation.  An empty span is VFX_OK and launches nothing.
+ * VFX_EINVAL, nothing launched: everything vfx_level_span_f32 refuses; a NULL weight, or one that is not finite or < 0; C
+ * outside [1, 8]; w_stride < wlen; out_stride < m1 - m0; the block of the outputs overlapping the block of the windows. */
+int vfx_level_span_rows_f32(const float* xw, int64_t w_stride, int C, const double* weight, int64_t g0, int64_t wlen,
+                            int64_t n_total, int64_t m0, int64_t m1, int fs, const double* coef, const double* mpow, int S,
+                            double target, double max_gain_db, double gate, double* state, float* out, int64_t out_stride,
+                            void* ws, size_t ws_bytes, vfx_stream_t stream);
+
 /* ---- word-length reduction: 16- / 24-bit PCM with seeded dither (voicefixer_amd/wordlength.py) ----------------- */
 
 /* The last stage of the output chain (the reference's save_wave truncates to int16 on the host, voicefixer/tools/wav.py:27-34;

@@ -11,6 +11,12 @@ the time from the first push to the first non-empty result.  Prints one JSON lin
 second and the gain is set from the plain session's output so that every output chunk is bound; the plain session and the
 session with gain_db and limiter=True (true peak) run alternating in one process, median of --repeats with the spread, and
 one ops.limit_span call over one second of output is timed with HIP events.
+
+--channels C: a session of C channels (channels="all").  Three legs alternate in one process -- the plain
+C-channel session, C mono sessions back to back on the same channels (the route a stereo stream had to take before), and the
+C-channel session with the linked leveller and limiter on -- median of --repeats with the spread; then one ops.limit_span_rows
+and one ops.level_span_rows call over 1 s and over one chunk of C-channel output are timed with HIP events against C mono calls
+and against a device copy of the same samples.
 """
 import argparse
 import json
@@ -88,6 +94,82 @@ def limiter_leg(args, vf, wav, blk):
     print(json.dumps(res))
 
 
+def _events(call, reps=20):
+    for _ in range(3):
+        call()
+    ev = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1) * 1e-3)
+    return _spread(ev)
+
+
+def channels_leg(args, vf, wav, blk):
+    from voicefixer_amd import loudness, ops
+    cs, ov, rate, C = args.chunk_seconds, args.overlap_seconds, args.output_sample_rate, args.channels
+    n = wav.shape[1]
+
+    def session(x, **kw):
+        outs = []
+        with vf.open_stream(cs, ov, batch_size=1, output_sample_rate=rate, **kw) as s:
+            for a in range(0, n, blk):
+                outs.append(s.push(x[..., a:a + blk]))
+            outs.append(s.finish())
+            stats = (s.leveller_stats, s.limiter_stats)
+        return np.concatenate(outs, axis=1), stats
+
+    linked = dict(channels="all", leveller=-20.0, limiter=True, true_peak=True)
+    Z, _ = session(wav, channels="all")                          # warm-up of every leg
+    monos = [session(wav[c])[0] for c in range(C)]
+    _, stats = session(wav, **linked)
+    rms = [float(np.sqrt(np.mean(np.square(Z[c].astype(np.float64) - monos[c][0])))) for c in range(C)]
+    t_all, t_mono, t_link = [], [], []
+    for _ in range(args.repeats):
+        for ts, run in ((t_all, lambda: session(wav, channels="all")), (t_mono, lambda: [session(wav[c]) for c in range(C)]),
+                        (t_link, lambda: session(wav, **linked))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            ts.append(time.perf_counter() - t0)
+    # single calls of the linked span kernels over 1 s and over one chunk of output, HIP events
+    dev = vf._get_pipe().device
+    H, Bk, Fw = loudness.limiter_reach(rate, 3.0, True)
+    hop = loudness.hop_length(rate)
+    calls = {}
+    for name, secs in (("1s", 1.0), ("chunk", cs)):
+        m = int(secs * rate)
+        m0 = 3 * rate
+        need = m0 + m + 2 * rate
+        reps_ = -(-need // Z.shape[1])
+        prog = torch.from_numpy(np.ascontiguousarray(np.tile(Z, (1, reps_))[:, :need])).to(dev)
+        out = torch.empty((C, m), dtype=torch.float32, device=dev)
+        lo, hi = m0 - 2 * H - Bk, m0 + m + 2 * H + Fw
+        win = prog[:, lo:hi].contiguous()
+        calls["limit_rows_" + name] = _events(lambda: ops.limit_span_rows(win, lo, None, rate, 6.0, m0, m0 + m, out, -1.0, True, 3.0))
+        calls["limit_mono_x%d_" % C + name] = _events(lambda: [ops.limit_span(win[c], lo, None, rate, 6.0, m0, m0 + m, out[c], -1.0,
+                                                                               True, 3.0) for c in range(C)])
+        # the leveller from the row's start (calls come in order): outputs [0, m) of a programme of m + 1.1 s
+        head = prog[:, :m + 11 * hop].contiguous()
+        state = ops.level_state(dev)
+        calls["level_rows_" + name] = _events(lambda: ops.level_span_rows(head, 0, None, rate, -20.0, 0, m - m % hop, out, state))
+        states = [ops.level_state(dev) for _ in range(C)]
+        calls["level_mono_x%d_" % C + name] = _events(lambda: [ops.level_span(head[c], 0, None, rate, -20.0, 0, m - m % hop, out[c],
+                                                                               states[c]) for c in range(C)])
+        src = prog[:, m0:m0 + m].contiguous()
+        calls["device_copy_" + name] = _events(lambda: out.copy_(src))
+    ma, mm, ml = statistics.median(t_all), statistics.median(t_mono), statistics.median(t_link)
+    res = {"leg": "channels", "channels": C, "minutes": args.minutes, "block_seconds": args.block_seconds, "chunk_seconds": cs,
+           "overlap_seconds": ov, "output_sample_rate": rate, "repeats": args.repeats, "rms_vs_mono": rms,
+           "leveller_stats": stats[0], "limiter_stats": stats[1], "all_s": _spread(t_all), "mono_sessions_s": _spread(t_mono),
+           "linked_s": _spread(t_link), "all_over_monos": ma / mm - 1.0, "linked_over_all": ml / ma - 1.0, "span_calls_s": calls,
+           "device": torch.cuda.get_device_name(dev), "build_id": _lib.lib().vfx_build_id().decode()}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=5.0)
@@ -97,6 +179,8 @@ def main():
     ap.add_argument("--output-sample-rate", type=int, default=48000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--limiter", action="store_true", help="measure the fixed-gain limiter of the session against the plain session")
+    ap.add_argument("--channels", type=int, default=None, help="measure a session of this many channels (channels='all') against "
+                    "as many mono sessions, and its linked leveller and limiter against the plain one")
     args = ap.parse_args()
     n = int(args.minutes * 60 * 44100)
     rng = np.random.default_rng(0)
@@ -110,6 +194,12 @@ def main():
     if args.limiter:
         wav[::44100] = 0.9
         return limiter_leg(args, vf, wav, blk)
+    if args.channels is not None:
+        if not 1 <= args.channels <= 8:
+            ap.error("--channels takes 1..8")
+        gains = [1.0, 0.5, 0.25, 0.7, 0.35, 0.9, 0.6, 0.45][:args.channels]
+        prog = np.stack([(g * np.roll(wav, 4410 * c)).astype(np.float32) for c, g in enumerate(gains)])
+        return channels_leg(args, vf, prog, blk)
 
     def two_step():
         y44 = vf.restore_stream(wav, cs, ov, batch_size=1)

@@ -540,11 +540,12 @@ def quantize(wav, bit_depth=16, dither="tpdf", dither_seed=0):
     return out[0] if single else out
 
 
-def _span_rows(what, x, stage, stats, _span):
+def _span_rows(what, x, stage, stats, _span, channels=None):
     """``limit`` and ``level``: one float32 array (N,) -- or every array of a list, each row on its own -- through a fresh
     ``stage(span)`` (a stream._SpanStage) as a whole row on the device.  ``stats`` (a dict or None) receives the stage's
-    ``stats()``: scalars for one array, lists of one value per row for a list.  Everything is checked before the device is
-    touched."""
+    ``stats()``: scalars for one array, lists of one value per row for a list.  With ``channels="all"`` a (C, N) array, C in
+    1..8, is ONE programme through the stage (the linked form) and comes back (C, N); ``stage(span, C)`` is
+    then called with its channel count.  Everything is checked before the device is touched."""
     if stats is not None and not isinstance(stats, dict):
         raise ValueError("stats must be a dict or None")
     span = None if _span is None else int(_span)
@@ -552,14 +553,25 @@ def _span_rows(what, x, stage, stats, _span):
         raise ValueError("_span must be positive")
     single = not isinstance(x, (list, tuple))
     items = [np.asarray(w, dtype=np.float32) for w in ([x] if single else x)]
+    from . import loudness as ld
+    if ld.check_channels(channels) not in (None, "all"):
+        raise ValueError('%s: channels must be None or "all" (got %r)' % (what, channels))
     for w in items:
-        if w.ndim != 1:
+        if w.ndim == 2 and channels == "all":
+            ld.check_channel_count(int(w.shape[0]))
+        elif w.ndim != 1:
             raise ValueError("%s: a row is a 1-D array of samples (got shape %r)" % (what, w.shape))
+    if channels == "all":
+        for c in sorted({w.shape[0] for w in items if w.ndim == 2}):
+            stage(span, c)                                           # (ValueError: weights for another channel count)
     outs, recs = [], []
     dev = _device() if items else None
     for w in items:
-        st = stage(span)
-        outs.append(st.whole(torch.from_numpy(np.ascontiguousarray(w)).to(dev)).cpu().numpy())
+        st = stage(span) if w.ndim == 1 else stage(span, w.shape[0])
+        if w.ndim == 2 and w.shape[1] == 0:                          # (a window is never empty)
+            outs.append(w.copy())
+        else:
+            outs.append(st.whole(torch.from_numpy(np.ascontiguousarray(w)).to(dev)).cpu().numpy())
         recs.append(st.stats())
     if stats is not None:
         for key in (recs[0] if recs else stage(span).stats()):      # (an empty list reports its keys too)
@@ -567,7 +579,8 @@ def _span_rows(what, x, stage, stats, _span):
     return outs[0] if single else outs
 
 
-def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, sample_rate=44100, stats=None, _span=None):
+def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, sample_rate=44100, stats=None, _span=None,
+          channels=None):
     """The fixed-gain look-ahead limiter F (loudness.py) on the device: a float32 array (N,) at ``sample_rate``
     -- or every array of a list, each row on its own -- is multiplied by 10^(gain_db/20) and a gain curve that looks
     ``lookahead_ms`` ahead holds every sample under ``peak_ceiling`` (dBFS; with ``true_peak=True`` the envelope includes the
@@ -575,7 +588,10 @@ def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, 
     session (``open_stream(gain_db=..., limiter=True)``) applies, bit for bit, and the inter-sample peak of the result is bounded
     only approximately -- lower ``peak_ceiling`` for a margin.  Where no sample within reach is above the ceiling the output is
     float32(gL) x exactly.  ``stats``: a dict that receives {"max_reduction_db", "peak_out_db"} (lists of one value per row
-    when a list went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span."""
+    when a list went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span.
+    ``channels="all"``: a (C, N) array (or each (C, N) array of a list) is ONE programme of C channels through the LINKED limiter
+    (DESIGN.md 3.18): one envelope, the maximum over the channels, one gain curve for all of them, one record -- what a session
+    with channels="all" applies, bit for bit.  Without it a 2-D array raises ValueError."""
     from . import loudness as ld
     gain_db = ld.check_gain(gain_db)
     if gain_db is None:
@@ -583,22 +599,34 @@ def limit(x, gain_db=0.0, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, 
     peak_ceiling, true_peak = ld.check_ceiling(peak_ceiling), ld.check_true_peak(true_peak)
     rate = _check_rate(sample_rate)
     ld.limiter_reach(rate, lookahead_ms, true_peak)      # (ValueError: a look-ahead outside [1, 4096] samples)
-    return _span_rows("limit", x, lambda span: _SpanLimiter(rate, gain_db, peak_ceiling, true_peak, lookahead_ms, span),
-                      stats, _span)
+    return _span_rows("limit", x, lambda span, C=None: _SpanLimiter(rate, gain_db, peak_ceiling, true_peak, lookahead_ms, span),
+                      stats, _span, channels)
 
 
-def level(x, target=-16.0, max_gain_db=12.0, gate=-50.0, sample_rate=44100, stats=None, _span=None):
+def level(x, target=-16.0, max_gain_db=12.0, gate=-50.0, sample_rate=44100, stats=None, _span=None, channels=None,
+          channel_weights=None):
     """The streaming loudness leveller (loudness.py) on the device: a float32 array (N,) at ``sample_rate`` (at
     most 192 kHz) -- or every array of a list, each row on its own -- is multiplied by a slowly moving gain that brings the
     loudness of the 3 s around every 100 ms anchor to ``target`` LUFS: at most ``max_gain_db`` up ([0, 40] dB) and 40 dB down,
     held wherever that loudness is not above ``gate`` (LUFS, in [-70, target)), so that pauses are not pumped up.  This is what a
     streaming session (``open_stream(leveller=target)``) applies, bit for bit.  A row shorter than 100 ms comes back as it is.
     ``stats``: a dict that receives {"min_gain_db", "max_gain_db", "anchors", "gated"} (lists of one value per row when a list
-    went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span."""
+    went in).  A row is processed in spans of at most 2^22 outputs; the bits do not depend on the span.
+    ``channels="all"``: a (C, N) array (or each (C, N) array of a list) is ONE programme of C channels through the LINKED leveller
+    (DESIGN.md 3.18): the loudness is BS.1770-4's over the channels, weighted by ``channel_weights`` (C numbers >= 0; default
+    loudness.channel_weights(C); needs channels="all"), and one gain multiplies every channel -- what a session with
+    channels="all" applies, bit for bit.  Without it a 2-D array raises ValueError."""
     from . import loudness as ld
     rate = _check_rate(sample_rate)
     target, max_gain_db, gate = ld.check_leveller(target, max_gain_db, gate, rate)
-    return _span_rows("level", x, lambda span: _SpanLeveller(rate, target, max_gain_db, gate, span), stats, _span)
+    if channel_weights is not None and channels != "all":
+        raise ValueError('level: channel_weights weigh the channels of a programme and need channels="all"')
+
+    def stage(span, C=None):
+        weights = None if C is None or channel_weights is None else ld.channel_weights(C, channel_weights)
+        return _SpanLeveller(rate, target, max_gain_db, gate, span, weights)
+
+    return _span_rows("level", x, stage, stats, _span, channels)
 
 
 class Vocoder(nn.Module):
@@ -1221,7 +1249,7 @@ class VoiceFixer(nn.Module):
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                     sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
                     dither="tpdf", dither_seed=0, gain_db=None, peak_ceiling=-1.0, true_peak=False, leveller=None,
-                    leveller_max_gain_db=12.0, leveller_gate=-50.0):
+                    leveller_max_gain_db=12.0, leveller_gate=-50.0, **programme):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
@@ -1236,7 +1264,7 @@ class VoiceFixer(nn.Module):
         bounds every SAMPLE by the ceiling; the inter-sample peak of the gain-modulated output is bounded only approximately and a
         session cannot trim afterwards: lower ``peak_ceiling`` for a margin.  ``limiter=True`` without ``gain_db`` raises
         NotImplementedError, as ``restore_stream`` does with any limiter: a loudness TARGET needs the whole file, and a session
-        never sees it (nor does it offer a trim, several channels or ``restore_stream``'s refusal lifted).  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
+        never sees it (nor does it offer a trim or ``restore_stream``'s refusal lifted).  ``bit_depth`` / ``dither`` / ``dither_seed`` (restore_inmem): the stretches are reduced to PCM
         on the device, each from the session's position on, so that all of them, concatenated, are the whole output quantised
         once; ``push`` and ``finish`` then return int16 / int32 arrays.
         ``leveller`` (LUFS, [-70, 0); default None: none): the streaming loudness leveller (loudness.py) behind the
@@ -1245,10 +1273,24 @@ class VoiceFixer(nn.Module):
         held wherever that loudness is not above ``leveller_gate`` (LUFS, [-70, target)) -- what ``voicefixer_amd.level`` gives
         for the whole output, bit for bit, less than 1.1 s late; output rates up to 192 kHz.  With a leveller ``limiter=True``
         needs no ``gain_db`` (the limiter then runs at 0 dB; a ``gain_db`` follows the leveller as it follows the converter
-        today); ``session.leveller_stats`` reports {"min_gain_db", "max_gain_db", "anchors", "gated"}."""
+        today); ``session.leveller_stats`` reports {"min_gain_db", "max_gain_db", "anchors", "gated"}.
+        Two more keywords, ``channels`` and ``channel_weights`` (both default None), are taken BY KEYWORD ONLY and handed to
+        ``RestoreSession``, whose signature ends with them (any other keyword is a TypeError): the named parameters of this
+        method stay the mono session's.
+        ``channels`` (default None: blocks are (k,), as ever, and a 2-D block raises): "all" restores EVERY channel (DESIGN.md
+        3.18) -- every block is (C, k), C in 1..8 fixed by the first one, ``push`` / ``finish`` return (C, j), a chunk goes
+        through the path as C adjacent rows of one batch, and the leveller and the limiter are LINKED: one gain curve per
+        programme, from the channels' energies weighted by ``channel_weights`` (C numbers >= 0; default BS.1770-4 Table 4;
+        needs channels="all") and from the envelope over all channels, so the balance between the channels stays -- what
+        ``level(..., channels="all")`` and ``limit(..., channels="all")`` give for the whole (C, N) output, bit for bit; the
+        stats are one record per programme.  "mix" / "first": a (C, k) block is averaged / cut to channel 0 on the host and
+        the session is the mono one."""
+        for key in programme:
+            if key not in ("channels", "channel_weights"):
+                raise TypeError("open_stream() got an unexpected keyword argument %r" % key)
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
                               output_sample_rate, bit_depth, dither, dither_seed, gain_db, peak_ceiling, true_peak, limiter,
-                              limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate)
+                              limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate, **programme)
 
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)

@@ -499,3 +499,29 @@ def level_reference(x, fs, target=-16.0, max_gain_db=12.0, gate=-50.0, stats=Non
         stats.update(r, min_gain_db=float(r["G"].min()), max_gain_db=float(r["G"].max()), anchors=int(r["G"].shape[0]),
                      gated=int(r["held"].sum()))
     return leveller_apply(x, r["a"], hop_length(fs))
+
+
+def leveller_energies_linked(x, fs, weights=None):
+    """The LINKED quarter energies of a programme x (C, N): E_q = sum_c w_c E_{q,c} with E_{q,c} =
+    ``leveller_energies(x[c], fs)`` and w = ``channel_weights(C, weights)``, in float64, c ascending from 0.0, every product and
+    every sum rounded on its own (what vfx_level_span_rows_f32 does with its per-channel energies)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("leveller_energies_linked: a programme is a (C, N) array (got shape %r)" % (x.shape,))
+    w = channel_weights(int(x.shape[0]), weights)
+    E = np.zeros(x.shape[1] // hop_length(fs))
+    for c in range(x.shape[0]):
+        E = E + np.float64(w[c]) * leveller_energies(x[c], fs)
+    return E
+
+
+def level_reference_linked(x, fs, target=-16.0, max_gain_db=12.0, gate=-50.0, weights=None, stats=None):
+    """``level_reference`` of a programme x (C, N) with ONE gain for all channels: the gains of ``leveller_gains`` on the linked
+    energies, the float32 ramp of step 4 applied to every channel.  Returns float32 (C, N); ``stats`` as there."""
+    x = np.asarray(x, dtype=np.float32)
+    r = leveller_gains(leveller_energies_linked(x, fs, weights), x.shape[1], fs, target, max_gain_db, gate)
+    if stats is not None:
+        stats.update(r, min_gain_db=float(r["G"].min()), max_gain_db=float(r["G"].max()), anchors=int(r["G"].shape[0]),
+                     gated=int(r["held"].sum()))
+    hop = hop_length(fs)
+    return np.stack([leveller_apply(x[c], r["a"], hop) for c in range(x.shape[0])])

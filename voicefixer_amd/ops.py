@@ -827,6 +827,51 @@ def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, tru
     return rec
 
 
+def _check_span_rows(name, xw, out, m0, m1):
+    """What the ``*_span_rows`` wrappers ask of their windows and their outputs: float32, 2-D with the same 1..8 rows, unit
+    stride along a row (any row stride), on the device, and room for the m1 - m0 outputs per row (VfxError otherwise).  Returns
+    (C, m0, m1, w_stride, out_stride) as ints."""
+    from . import loudness
+    _need_cuda(xw, out)
+    assert xw.dtype == torch.float32 and out.dtype == torch.float32 and xw.dim() == 2 and out.dim() == 2
+    C = loudness.check_channel_count(int(xw.shape[0]))
+    assert out.shape[0] == C
+    assert (xw.shape[1] <= 1 or xw.stride(1) == 1) and (out.shape[1] <= 1 or out.stride(1) == 1)
+    m0, m1 = int(m0), int(m1)
+    if m1 - m0 > out.shape[1]:
+        raise _lib.VfxError("%s: %d outputs per channel into a buffer of %d" % (name, m1 - m0, out.shape[1]))
+    # (one row: any stride that holds the row will do)
+    return (C, m0, m1, int(xw.stride(0)) if C > 1 else max(int(xw.stride(0)), int(xw.shape[1])),
+            int(out.stride(0)) if C > 1 else max(int(out.stride(0)), int(out.shape[1])))
+
+
+def limit_span_rows(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, true_peak=False, lookahead_ms=3.0):
+    """Outputs [m0, m1) of the LINKED fixed-gain limiter over a programme of C channels from a window of it
+    (vfx_limit_span_rows_f32): ``limit_span`` with xw (C, wlen) and out (C, >= m1 - m0), rows of unit stride and
+    any row stride.  One envelope, the maximum over the channels, hence one gain for all of them; the record is {min g, max |out|
+    over all channels}.  C = 1: the bits and the record of ``limit_span``.  Three launches, no synchronisation."""
+    from . import loudness
+    C_, m0, m1, ws_, os_ = _check_span_rows("limit_span_rows", xw, out, m0, m1)
+    gain_db = loudness.check_gain(gain_db)
+    if gain_db is None:
+        raise ValueError("limit_span_rows: the limiter needs a gain (gain_db=...)")
+    ceiling_db = loudness.check_ceiling(ceiling_db)
+    true_peak = loudness.check_true_peak(true_peak)
+    H = loudness.limiter_window(rate, lookahead_ms)[0]
+    if m1 == m0:
+        return torch.tensor([1.0, 0.0], dtype=torch.float64).to(xw.device)
+    R = loudness.oversampling(rate) if true_peak else 1
+    bank, J, c = true_peak_bank(xw.device, R) if R > 1 else (None, 1, 0)
+    h = _lib.lib()
+    nb = h.vfx_limit_span_rows_workspace_bytes(max(m1 - m0, 0), H, C_)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    rec = torch.empty((2,), dtype=torch.float64, device=xw.device)
+    check(h.vfx_limit_span_rows_f32(_ptr(xw), ws_, C_, int(g0), xw.shape[1], INT64_MAX if n_total is None else int(n_total), m0,
+                                    m1, 10.0 ** (gain_db / 20.0), ceiling_db, H, _ptr(bank), J, R, c, _ptr(out), os_, _ptr(rec),
+                                    _ptr(ws), nb, _stream()), "vfx_limit_span_rows_f32")
+    return rec
+
+
 _LEVELLER_MPOW = {}
 
 
@@ -862,6 +907,33 @@ def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12
     check(h.vfx_level_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total), m0, m1, int(rate),
                                coef, _ptr(mpow), p["S"], target, max_gain_db, gate, _ptr(state), _ptr(out), _ptr(ws), nb,
                                _stream()), "vfx_level_span_f32")
+
+
+def level_span_rows(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12.0, gate=-50.0, weights=None):
+    """Outputs [m0, m1) of the LINKED loudness leveller over a programme of C channels from a window of it
+    (vfx_level_span_rows_f32): ``level_span`` with xw (C, wlen) and out (C, >= m1 - m0), rows of unit stride and
+    any row stride, and ONE ``state``.  The quarter energies are summed over the channels with ``weights``
+    (loudness.channel_weights(C, weights): BS.1770-4 Table 4 by default), so one ramp multiplies every channel.  C = 1 with the
+    weight 1: the bits and the state of ``level_span``.  At most three launches, no synchronisation."""
+    from . import loudness
+    C_, m0, m1, ws_, os_ = _check_span_rows("level_span_rows", xw, out, m0, m1)
+    _need_cuda(state)
+    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
+    target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
+    wt = (C.c_double * C_)(*loudness.channel_weights(C_, weights))
+    p = loudness.leveller_plan(rate)
+    key = (str(xw.device), int(rate))
+    mpow = _LEVELLER_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
+        _LEVELLER_MPOW[key] = mpow
+    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
+    h = _lib.lib()
+    nb = h.vfx_level_span_rows_workspace_bytes(max(m1 - m0, 0), p["hop"], C_)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    check(h.vfx_level_span_rows_f32(_ptr(xw), ws_, C_, wt, int(g0), xw.shape[1], INT64_MAX if n_total is None else int(n_total),
+                                    m0, m1, int(rate), coef, _ptr(mpow), p["S"], target, max_gain_db, gate, _ptr(state), _ptr(out),
+                                    os_, _ptr(ws), nb, _stream()), "vfx_level_span_rows_f32")
 
 
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):

@@ -94,19 +94,23 @@ class _SpanStage:
     ``feed`` takes the next samples (device (k,)) and returns the outputs that became final with them, ``finish`` the rest
     with the row's end known, ``whole`` all outputs of a row that is there at once.  Kept between calls: ``win``, the
     samples [g0, g0 + wlen) of the row that later outputs still read, ``n_in``, the samples fed, and ``m_done``, the outputs
-    returned.  A subclass says what its operator needs:
+    returned.  The row may be a PROGRAMME of C channels: C rows of one length that arrive together -- ``feed``,
+    ``finish`` and ``whole`` then take and return (C, k), the window is (C, wlen), everything is concatenated, dropped and cloned
+    along the last axis, and ``n_in`` / ``m_done`` count samples per channel.  A subclass says what its operator needs:
 
         _ready(n)                 how many outputs are final once n samples of a row of unknown length are known
         _length(n)                how many outputs a row of n samples has (n, unless the stage changes the rate)
-        _run(a, b, n_total, y)    outputs [a, b), b > a, from ``win`` / ``g0`` into y (b - a,): its one ops.*_span call
-                                  (n_total: the row's length, None while it is unknown)
+        _run(a, b, n_total, y)    outputs [a, b), b > a, from ``win`` / ``g0`` into y (b - a,) -- (C, b - a), rows of unit
+                                  stride, for a programme: its one ops.*_span call (n_total: the row's length, None
+                                  while it is unknown)
         _keep(m1)                 the first sample that outputs from m1 on still read (may be negative)
 
     ``span``: the most outputs one ``_run`` call is given (None: no bound)."""
 
     def __init__(self, span=None):
         self.span = span
-        self.win = None      # device (wlen,): samples [g0, g0 + wlen) of the row
+        self.win = None      # device (wlen,) or (C, wlen): samples [g0, g0 + wlen) of the row
+        self.rows = None     # C once a programme has been fed (None: one row, 1-D)
         self.g0 = 0
         self.n_in = 0        # samples fed
         self.m_done = 0      # outputs returned
@@ -115,19 +119,21 @@ class _SpanStage:
         return n
 
     def feed(self, x):
-        self.win = x if self.win is None else torch.cat([self.win, x])
-        self.n_in += x.numel()
+        self.win = x if self.win is None else torch.cat([self.win, x], dim=-1)
+        self.rows = x.shape[0] if x.dim() == 2 else None
+        self.n_in += x.shape[-1]
         return self._emit(self._ready(self.n_in), None)
 
     def finish(self, device):
         if self.win is None:
-            return torch.empty((0,), dtype=torch.float32, device=device)
+            return torch.empty((0,) if self.rows is None else (self.rows, 0), dtype=torch.float32, device=device)
         return self._emit(self._length(self.n_in), self.n_in)
 
     def whole(self, x):
-        """All outputs of the complete row ``x`` (device (n,)), which serves as the window as it is: the end is known from
-        the first call on."""
-        self.win, self.g0, self.n_in = x, 0, x.numel()
+        """All outputs of the complete row ``x`` (device (n,) or (C, n)), which serves as the window as it is: the end is known
+        from the first call on."""
+        self.win, self.g0, self.n_in = x, 0, x.shape[-1]
+        self.rows = x.shape[0] if x.dim() == 2 else None
         return self._emit(self._length(self.n_in), self.n_in)
 
     def release(self):
@@ -136,16 +142,16 @@ class _SpanStage:
 
     def _emit(self, m1, n_total):
         m0, m1 = self.m_done, max(m1, self.m_done)
-        y = torch.empty((m1 - m0,), dtype=torch.float32, device=self.win.device)
+        y = torch.empty(tuple(self.win.shape[:-1]) + (m1 - m0,), dtype=torch.float32, device=self.win.device)
         step = self.span or max(m1 - m0, 1)
         for a in range(m0, m1, step):                     # (no outputs: no call)
             b = min(a + step, m1)
-            self._run(a, b, n_total, y[a - m0:b - m0])
+            self._run(a, b, n_total, y[..., a - m0:b - m0])
         self.m_done = m1
         # drop what no later output reads (one sample always stays: a window is never empty)
         keep = min(max(self._keep(m1), 0), self.n_in - 1)
         if keep > self.g0:
-            self.win = self.win[keep - self.g0:].clone()
+            self.win = self.win[..., keep - self.g0:].clone()
             self.g0 = keep
         return y
 
@@ -153,7 +159,8 @@ class _SpanStage:
 class _SpanConverter(_SpanStage):
     """Rate conversion (ops.resample_span): final are the outputs that read nothing beyond what has arrived
     (audio_io.ready_outputs); a row of n samples has ceil(n * up / down) of them.  Every output has the bits of
-    ops.resample_rows on the whole row.  The window holds at most J + down / up + 1 samples beyond a block."""
+    ops.resample_rows on the whole row.  The window holds at most J + down / up + 1 samples beyond a block.  A programme is
+    converted channel by channel: a row of a contiguous (C, wlen) window is a window."""
 
     def __init__(self, rate_in, rate_out):
         super().__init__()
@@ -168,6 +175,10 @@ class _SpanConverter(_SpanStage):
 
     def _run(self, a, b, n_total, y):
         from . import ops
+        if self.win.dim() == 2:
+            for c in range(self.win.shape[0]):
+                ops.resample_span(self.win[c], self.g0, n_total, self.up, self.down, a, b, y[c])
+            return
         ops.resample_span(self.win, self.g0, n_total, self.up, self.down, a, b, y)
 
     def _keep(self, m1):
@@ -178,7 +189,8 @@ class _SpanLimiter(_SpanStage):
     """The fixed-gain look-ahead limiter F (loudness.py; ops.limit_span): final are the outputs of
     loudness.limiter_ready.  Every output has the bits of one span over the whole row.  Output m reads from m - 2 H - Bk on, so
     the window holds at most 4 H + Bk + Fw + 1 samples beyond a block.  Kept as well: the calls' records {min g, max |out|} --
-    device scalars, folded exactly (min and max) and read by ``stats()`` only."""
+    device scalars, folded exactly (min and max) and read by ``stats()`` only.  A programme goes through the LINKED limiter
+    (ops.limit_span_rows): one gain curve from the envelope over all channels, one record."""
 
     def __init__(self, rate, gain_db, peak_ceiling=-1.0, true_peak=False, lookahead_ms=3.0, span=None):
         from . import loudness
@@ -193,8 +205,8 @@ class _SpanLimiter(_SpanStage):
 
     def _run(self, a, b, n_total, y):
         from . import ops
-        self.recs.append(ops.limit_span(self.win, self.g0, n_total, self.rate, self.gain_db, a, b, y, self.ceiling,
-                                        self.true_peak, self.ms))
+        run = ops.limit_span_rows if self.win.dim() == 2 else ops.limit_span
+        self.recs.append(run(self.win, self.g0, n_total, self.rate, self.gain_db, a, b, y, self.ceiling, self.true_peak, self.ms))
         if len(self.recs) >= 256:                             # (bounded, whatever the session's length)
             self.recs = [self._fold()]
 
@@ -219,13 +231,16 @@ class _SpanLeveller(_SpanStage):
     Every output has the bits of one call over the whole row.  The window starts at the first output not yet returned or, if
     that is earlier, at the region of the next quarter to be measured, two quarters before it: fewer than 11 quarters, 1.1 s,
     beyond a block (the energies behind them live in the device state).  Kept as well: that state with the record, created by
-    the first output -- nothing touches the device before -- and read by ``stats()`` only."""
+    the first output -- nothing touches the device before -- and read by ``stats()`` only.  A programme goes through the LINKED
+    leveller (ops.level_span_rows): the quarter energies summed over the channels with ``weights``
+    (loudness.channel_weights), one gain for all channels, still ONE state."""
 
-    def __init__(self, rate, target, max_gain_db=12.0, gate=-50.0, span=None):
+    def __init__(self, rate, target, max_gain_db=12.0, gate=-50.0, span=None, weights=None):
         from . import loudness
         super().__init__(LEVEL_SPAN if span is None else int(span))
         self.target, self.max_gain_db, self.gate = loudness.check_leveller(target, max_gain_db, gate, rate)
         self.rate, self.hop = int(rate), loudness.hop_length(rate)
+        self.weights = weights     # (of a programme; checked against its channel count by whoever knows it)
         self.state = None    # device float64 (loudness.LEVELLER_STATE,)
 
     def _ready(self, n):
@@ -236,6 +251,10 @@ class _SpanLeveller(_SpanStage):
         from . import ops
         if self.state is None:
             self.state = ops.level_state(self.win.device)
+        if self.win.dim() == 2:
+            ops.level_span_rows(self.win, self.g0, n_total, self.rate, self.target, a, b, y, self.state, self.max_gain_db,
+                                self.gate, self.weights)
+            return
         ops.level_span(self.win, self.g0, n_total, self.rate, self.target, a, b, y, self.state, self.max_gain_db, self.gate)
 
     def _keep(self, m1):
@@ -273,8 +292,7 @@ class RestoreSession:
     stretches, which therefore never visit the host).  Held between calls: the 44.1 kHz samples from the next chunk's
     start on, one overlap, two filter windows -- O(chunk + the largest block), whatever has been pushed.  A chunk is
     settled once more than chunk + min_tail samples (1024; mode 1: 1535) beyond its start are known at 44.1 kHz: the
-    session's latency.  Loudness normalisation to a TARGET and a trim need the whole file and are not offered here (nor are
-    several channels); a FIXED gain (``gain_db``) is, alone or followed by the fixed-gain look-ahead limiter (``limiter=True``;
+    session's latency.  Loudness normalisation to a TARGET and a trim need the whole file and are not offered here; a FIXED gain (``gain_db``) is, alone or followed by the fixed-gain look-ahead limiter (``limiter=True``;
     loudness.py) under ``peak_ceiling`` at the output rate, carried across stretches like the converters and
     2 H + 93 samples late; ``limiter_stats`` is then {"max_reduction_db", "peak_out_db"} over what has been delivered (None
     without a limiter).  The limiter bounds every sample by the ceiling, the inter-sample peak only approximately: lower
@@ -285,16 +303,38 @@ class RestoreSession:
     converters and less than 1.1 s late; with it ``limiter=True`` needs no ``gain_db`` (the limiter then runs at 0 dB) and
     ``leveller_stats`` is {"min_gain_db", "max_gain_db", "anchors", "gated"} (None without a leveller).  The stages behind the
     stitcher, a chain of ``_SpanStage``: output converter, leveller, limiter (or the gain alone); then word length, host.
+    ``channels="all"`` (default None: the session above, a 2-D block raises): every block is float32 (C, k), C in
+    1..8 fixed by the first block (another C, a 1-D block or more than 8 channels: ValueError before the device is touched), and
+    ``push`` / ``finish`` return (C, j); ``position`` counts samples per channel.  Each channel has its own input converter,
+    cross-fade and output converter; a settled chunk goes through the path as C adjacent rows of one batch (``batch_size`` keeps
+    counting chunks).  The leveller and the limiter are the LINKED ones (ops.level_span_rows: the quarter energies summed over the
+    channels with ``channel_weights`` -- loudness.channel_weights(C), BS.1770-4 Table 4 by default; needs channels="all" -- and
+    ops.limit_span_rows: one envelope, the maximum over the channels): one gain curve per programme, so the balance between the
+    channels stays -- ``level(Z, ..., channels="all")`` and ``limit(..., channels="all")`` of the plain (C, N) output Z, bit for bit,
+    with one stats record per programme; the fixed gain alone is float32(gL) y; ``bit_depth`` gives ``quantize`` of the (C, N)
+    array (channel c draws the dither of channel c).  Every channel is within 2e-5 rms of the mono session on it, not its bits: the
+    path's bits depend on the batch's composition.  "mix" / "first": a (C, k) block is averaged (float32 mean) / cut to channel 0
+    on the host and the session is the mono one.  Held: O(C (chunk + the largest block)).
     Every argument is checked in the constructor, before the device is touched.
     A context manager; leaving it without ``finish`` discards what is pending."""
 
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                  sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0, gain_db=None,
                  peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0, leveller=None,
-                 leveller_max_gain_db=12.0, leveller_gate=-50.0):
+                 leveller_max_gain_db=12.0, leveller_gate=-50.0, channels=None, channel_weights=None):
         from . import loudness as ld
         from .api import _Output, _check_rate, _output_rate
         _check_stream_mode(mode, "open_stream")
+        self._channels = ld.check_channels(channels)
+        if channel_weights is not None:
+            if self._channels != "all":
+                raise ValueError('open_stream: channel_weights weigh the channels of a programme and need channels="all"')
+            if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
+                    or not 1 <= len(channel_weights) <= ld.MAX_CHANNELS:
+                raise ValueError("channel_weights must be a list of 1..8 numbers >= 0, one per channel (got %r)" % (channel_weights,))
+            channel_weights = ld.channel_weights(len(channel_weights), channel_weights)
+        self._weights = channel_weights
+        self._C = None           # channels="all": the channel count, fixed by the first block
         self._word = _Output(bit_depth=bit_depth, dither=dither, dither_seed=dither_seed)     # (checks the three)
         self._dtype = {None: np.float32, 16: np.int16, 24: np.int32}[self._word.bit_depth]
         self._rate_in, self._rate_out = _check_rate(sample_rate), _output_rate(output_sample_rate)
@@ -306,7 +346,7 @@ class RestoreSession:
                                       "session's fixed-gain limiter, or use restore_inmem or restore_folder")
         self._gain = None if gain_db is None else float(np.float32(10.0 ** (gain_db / 20.0)))
         # (check_leveller: ValueError for an output rate above 192 kHz too; nothing touches the device before the first stretch)
-        self._lev = (_SpanLeveller(self._rate_out, leveller, leveller_max_gain_db, leveller_gate)
+        self._lev = (_SpanLeveller(self._rate_out, leveller, leveller_max_gain_db, leveller_gate, weights=channel_weights)
                      if leveller is not None else None)
         # (limiter_reach: ValueError for a look-ahead outside [1, 4096] samples at the output rate; behind a leveller and
         # without a gain the limiter runs at 0 dB)
@@ -324,7 +364,7 @@ class RestoreSession:
         conv_out = _SpanConverter(44100, self._rate_out) if self._rate_out != 44100 else None
         self._stages = [s for s in (conv_out, self._lev, self._lim) if s is not None]      # behind the stitcher, in this order
         self._n_in = 0           # samples pushed
-        self._buf = None         # device (k,): 44.1 kHz samples [b0, b0 + k)
+        self._buf = None         # device (k,) -- (C, k) with channels="all", here and below: 44.1 kHz samples [b0, b0 + k)
         self._b0 = 0
         self._tail = None        # device (ov,): the previous chunk's stitched last ``ov`` samples
         self._fade = None        # device (ov,): restore_stream's fade-in ramp, uploaded once
@@ -360,21 +400,42 @@ class RestoreSession:
     @torch.no_grad()
     def push(self, block):
         """The next ``block`` (float32 (k,), k >= 0, at the session's input rate) -> the output that became final with it:
-        float32 numpy (1, j) at the output rate, j >= 0."""
+        float32 numpy (1, j) at the output rate, j >= 0.  With channels="all": (C, k) -> (C, j), C in 1..8 the same for every
+        block; with "mix" / "first" a (C, k) block is averaged / cut to channel 0 first."""
         if self._closed:
             raise RuntimeError("RestoreSession: push after finish / close")
-        block = np.asarray(block, dtype=np.float32)
-        if block.ndim != 1:
-            raise ValueError("push: a block is a 1-D array of samples (got shape %r)" % (block.shape,))
-        if block.shape[0] == 0:
-            return np.zeros((1, 0), self._dtype)
+        block = self._as_block(np.asarray(block, dtype=np.float32))
+        if block.shape[-1] == 0:
+            return np.zeros((self._C or 1, 0), self._dtype)
         pipe = self._vf._get_pipe()
         x = torch.from_numpy(np.ascontiguousarray(block)).to(pipe.device)
-        self._n_in += block.shape[0]
+        self._n_in += block.shape[-1]
         if self._conv_in is not None:
             x = self._conv_in.feed(x)
-        self._buf = x if self._buf is None else torch.cat([self._buf, x])
-        return self._deliver(pipe, self._restore(pipe, self._planner.feed(x.numel()), False), False)
+        self._buf = x if self._buf is None else torch.cat([self._buf, x], dim=-1)
+        return self._deliver(pipe, self._restore(pipe, self._planner.feed(x.shape[-1]), False), False)
+
+    def _as_block(self, block):
+        """A pushed array under the session's ``channels``: (k,) for the mono session, (C, k) with "all" (ValueError otherwise,
+        before the device is touched)."""
+        from . import loudness as ld
+        if self._channels == "all":
+            if block.ndim != 2:
+                raise ValueError('push: with channels="all" a block is a (channels, k) array (got shape %r)' % (block.shape,))
+            C = ld.check_channel_count(int(block.shape[0]))
+            if self._C is None:
+                if self._weights is not None:
+                    ld.channel_weights(C, self._weights)         # (ValueError: another number of weights)
+                self._C = C
+            elif C != self._C:
+                raise ValueError("push: this session has %d channels (got a block of shape %r)" % (self._C, block.shape))
+            return block
+        if self._channels is not None and block.ndim == 2:
+            ld.check_channel_count(int(block.shape[0]))
+            return block.mean(axis=0, dtype=np.float32) if self._channels == "mix" else block[0]
+        if block.ndim != 1:
+            raise ValueError("push: a block is a 1-D array of samples (got shape %r)" % (block.shape,))
+        return block
 
     @torch.no_grad()
     def finish(self):
@@ -392,8 +453,8 @@ class RestoreSession:
             n_new = 0
             if self._conv_in is not None:
                 x = self._conv_in.finish(pipe.device)
-                self._buf = torch.cat([self._buf, x])
-                n_new = x.numel()
+                self._buf = torch.cat([self._buf, x], dim=-1)
+                n_new = x.shape[-1]
             plan = self._planner.feed(n_new) + self._planner.finish()
             return self._deliver(pipe, self._restore(pipe, plan, True), True)
         finally:
@@ -403,30 +464,37 @@ class RestoreSession:
         """The settled chunks ``plan`` through the path and the stitcher; returns their final 44.1 kHz stretches (device)."""
         from . import ops
         from .api import VoiceFixer
-        ov, out, i = self._ov, [], 0
+        ov, out, i, C = self._ov, [], 0, self._C
         while i < len(plan):
             length = plan[i][1]
             grp = [c for c in plan[i:i + self._batch] if c[1] == length]
-            seg = torch.stack([self._buf[a - self._b0:a - self._b0 + length] for a, _ in grp])
+            if C is None:
+                seg = torch.stack([self._buf[a - self._b0:a - self._b0 + length] for a, _ in grp])
+            else:                       # a chunk of C channels: C adjacent rows of the batch
+                seg = torch.cat([self._buf[:, a - self._b0:a - self._b0 + length] for a, _ in grp])
             res = pipe.run_checked(lambda: VoiceFixer._restore_segments(pipe, seg, length, self._mode, self._voc))
             got = res.shape[1]          # == length in mode 0; 512 * (length // 512) in mode 1
             for k, (a, _) in enumerate(grp):
-                y = res[k]
+                y = res[k] if C is None else res[k * C:(k + 1) * C]
                 if a > 0 and ov > 0:    # cross-fade with what the previous chunk left in the overlap, in place
-                    ops.xfade(self._tail, y[:ov], self._fade, y[:ov])
+                    if C is None:
+                        ops.xfade(self._tail, y[:ov], self._fade, y[:ov])
+                    else:
+                        for c in range(C):
+                            ops.xfade(self._tail[c], y[c, :ov], self._fade, y[c, :ov])
                 last = at_end and i + k == len(plan) - 1
                 if last:
                     out.append(y)
                 else:
-                    out.append(y[:got - ov])
+                    out.append(y[..., :got - ov])
                     if ov > 0:
                         if self._fade is None:
                             self._fade = torch.from_numpy(np.arange(ov, dtype=np.float32) / max(ov, 1)).to(pipe.device)
-                        self._tail = y[got - ov:].clone()
+                        self._tail = y[..., got - ov:].clone()
             i += len(grp)
         # the next chunk starts at the planner's start: nothing before it is read again
         if not at_end and self._planner.start > self._b0:
-            self._buf = self._buf[self._planner.start - self._b0:].clone()
+            self._buf = self._buf[..., self._planner.start - self._b0:].clone()
             self._b0 = self._planner.start
         return out
 
@@ -440,10 +508,13 @@ class RestoreSession:
         if self._gain is not None and self._lim is None:
             stretches = [y * self._gain for y in stretches]      # (float32(gL) y: one rounding per sample)
         if not stretches:
-            return np.zeros((1, 0), self._dtype)
-        y = (stretches[0] if len(stretches) == 1 else torch.cat(stretches))[None]
-        if self._word.bit_depth is not None and y.shape[1] > 0:
-            y, _ = self._word.quantize(y, [y.shape[1]], None, self.position)
+            return np.zeros((self._C or 1, 0), self._dtype)
+        y = stretches[0] if len(stretches) == 1 else torch.cat(stretches, dim=-1)
+        if self._C is None:
+            y = y[None]
+        if self._word.bit_depth is not None and y.shape[1] > 0:     # (a row's channel is its index: quantize of the (C, N) array)
+            y, _ = self._word.quantize(y.contiguous(), [y.shape[1]] * y.shape[0], None if self._C is None else [self._C],
+                                       self.position)
         y = y.cpu().numpy().astype(self._dtype, copy=False)
         self.position += y.shape[1]
         return y
