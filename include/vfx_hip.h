@@ -575,7 +575,8 @@ int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_tota
 #define VFX_LEVEL_STATE 64 /* float64 values of the caller's state */
 
 /* Bytes of the workspace of vfx_level_span_f32 for spans of up to n_span outputs at quarters of hop samples (0 on bad arguments:
- * n_span < 0 or > 2^30, hop outside [400, 19200]): 12 bytes per quarter of the span and a few more. */
+ * n_span < 0 or > 2^30, hop outside [400, 19200]): vfx_level_span_rows_workspace_bytes(n_span, hop, 1), 20 bytes per quarter of
+ * the span and a few more -- ask for the size; the row runs the programme's kernels as a programme of one channel. */
 size_t vfx_level_span_workspace_bytes(int64_t n_span, int hop);
 
 /* Outputs [m0, m1) of the loudness leveller over ONE row of n_total samples at fs Hz (INT64_MAX: the row's end is not known yet)
@@ -630,7 +631,7 @@ int vfx_limit_span_rows_f32(const float* xw, int64_t w_stride, int C, int64_t g0
                             int64_t out_stride, double* record, void* ws, size_t ws_bytes, vfx_stream_t stream);
 
 /* Bytes of the workspace of vfx_level_span_rows_f32 (0 on bad arguments: those of vfx_level_span_workspace_bytes, or C outside
- * [1, 8]): 8 bytes per quarter of the span and channel on top of the mono size. */
+ * [1, 8]): 12 bytes per quarter of the span, and 8 more per quarter and channel. */
 size_t vfx_level_span_rows_workspace_bytes(int64_t n_span, int hop, int C);
 
 /* Outputs [m0, m1) of the LINKED loudness leveller over a programme of C channels: vfx_level_span_f32 with the quarter energy

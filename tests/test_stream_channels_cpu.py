@@ -439,9 +439,13 @@ def test_entry_points_declared_mapped_and_bound():
     assert list(inspect.signature(ops.level_span_rows).parameters) == list(inspect.signature(ops.level_span).parameters) + ["weights"]
     mk = open(os.path.join(ROOT, "voicefixer_amd", "csrc", "Makefile")).read()
     src = open(os.path.join(ROOT, "voicefixer_amd", "csrc", "vfx_loudness.hip")).read()
-    for inc in ("vfx_limit_span_rows.inc", "vfx_level_span_rows.inc"):
+    for stage in ("limit", "level"):                          # one file per stage defines the mono and the linked entry point
+        inc = "vfx_%s_span.inc" % stage
         assert inc in mk and '#include "%s"' % inc in src
-        assert os.path.exists(os.path.join(ROOT, "voicefixer_amd", "csrc", inc))
+        body = open(os.path.join(ROOT, "voicefixer_amd", "csrc", inc)).read()
+        for entry in ("vfx_%s_span_f32" % stage, "vfx_%s_span_rows_f32" % stage):
+            assert re.search(r'extern "C" int %s\(' % entry, body), entry
+        assert not os.path.exists(os.path.join(ROOT, "voicefixer_amd", "csrc", "vfx_%s_span_rows.inc" % stage))
 
 
 def test_span_stage_carries_a_programme():

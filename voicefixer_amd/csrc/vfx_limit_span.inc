@@ -1,26 +1,34 @@
-// vfx_limit_span.inc -- the fixed-gain look-ahead limiter of a streaming session, carried across blocks (vfx_limit_span_f32;
-// definition, ready rule, resources and measured cost: DESIGN.md 3.16; included by vfx_loudness.hip behind vfx_limit.inc, whose
-// tile sizes, reductions and true-peak sums it shares).
+// vfx_limit_span.inc -- the fixed-gain look-ahead limiter of a streaming session, carried across blocks, for one row
+// (vfx_limit_span_f32; DESIGN.md 3.16) and LINKED over the C = 1..8 channels of a programme (vfx_limit_span_rows_f32; DESIGN.md
+// 3.18): one set of kernels, the row being the programme of one channel.  Included by vfx_loudness.hip behind vfx_limit.inc,
+// whose tile sizes, reductions and true-peak sums it shares.
 //
-// F is steps 2-6 of the whole-row limiter (vfx_limit.inc) with a GIVEN gain gL: no measurement, no bound test, no trim.  The
-// span form writes outputs [m0, m1) of F over a row of n_total samples from the window xw[k] = x[g0 + k].  Every value is a
-// function of GLOBAL positions: clipping and clamping are done against [0, n_total), never against the window, so output n has
-// the bits the single span [0, n_total) gives it.  n_total = INT64_MAX: the end is not known yet, nothing is clipped at the top.
+// F is steps 2-6 of the whole-row limiter (vfx_limit.inc) with a GIVEN gain gL: no measurement, no bound test, no trim.  F_C is
+// F with ONE envelope for the C channels: e[n] = max_c e_c[n], then c, m and g from it, and out_c[n] = x_c[n] (float(gL) g[n]).
+// The span form writes outputs [m0, m1) of F_C over rows of n_total samples from the windows xw[ch w_stride + k] = x_ch[g0 + k]
+// to out[ch out_stride + n - m0]; g0, wlen and n_total are the programme's.  Every value is a function of GLOBAL positions:
+// clipping and clamping are done against [0, n_total), never against the window, so output n has the bits the single span
+// [0, n_total) gives it.  n_total = INT64_MAX: the end is not known yet, nothing is clipped at the top.
 //   1. ls_env_kernel<R> (R = 2, 4; ls_env1_kernel at R = 1): the required gain c[n] = e[n] > thr ? thr / e[n] : 1 over
-//      [a, b) = [m0 - 2 H, m1 + 2 H) within the row into the scratch (cbuf[n - a]), one flag per tile.  R > 1: tp_tile_sums on
-//      the window (row pointer and tile origin both moved by g0, so a sample lands in the LDS slot, and every chain has the
-//      order, of the whole-row kernels); positions outside the window are zeros and reach only values nobody asks for (the
-//      host check: the window covers [a - Bk, b - 1 + Fw] within the row).  There is no measured partial to tell a quiet tile
-//      by, so the shortcut is a bound: no interpolated value exceeds max |x| over what the tile reads times the largest l1 norm
-//      of a phase; where that (with a margin over the rounding of the sums) stays at or under thr the tile writes ones, clears
-//      its flag and forms no sum.  The interpolated values behind the last sample go to ctail, as there; only once n_total is
-//      known.
-//   2. ls_limit_kernel: lk_limit_kernel for one row and global positions: tiles of LM_TILE outputs from m0; no flag over the
-//      tile and 2 H around it: out = float(gL) x; otherwise c over the tile and 2 H around it in LDS, doubling minima, one
-//      ascending fp32 chain per output, and g = min(1 - sum, c[n]) -- the exact sum never exceeds c[n], the fp32 one may by
-//      its rounding, and nothing behind this kernel would trim it.  Per tile: min g and max |out|.
+//      [a, b) = [m0 - 2 H, m1 + 2 H) within the row into the scratch (cbuf[n - a]), one flag per tile.  R > 1: a workgroup owns
+//      a tile and walks the channels: tp_tile_sums on the channel's window (row pointer and tile origin both moved by g0, so a
+//      sample lands in the LDS slot, and every chain has the order, of the whole-row kernels); positions outside the window
+//      are zeros and reach only values nobody asks for (the host check: the window covers [a - Bk, b - 1 + Fw] within the
+//      row); e is folded with fmaxf in registers.  There is no measured partial to tell a quiet tile by, so the shortcut is a
+//      bound, per channel: no interpolated value exceeds max |x_c| over what the tile reads times the largest l1 norm of a
+//      phase (the norms and the channels' maxima are reduced by one tree in LDS); where that (with a margin over the rounding
+//      of the sums) stays at or under thr the channel is skipped -- every e_c of it is <= thr, so it changes c nowhere -- and
+//      a tile whose channels are all quiet writes ones and clears its flag.
+//      One cbuf, one flag per tile (the OR over the channels), one ctail per programme: the interpolated values behind the last
+//      sample, only once n_total is known.  16-byte loads are decided per channel: w_stride need not keep the alignment.
+//   2. ls_limit_kernel: lk_limit_kernel for global positions: tiles of LM_TILE outputs from m0; no flag over the tile and 2 H
+//      around it: out_c = float(gL) x_c; otherwise c over the tile and 2 H around it in LDS, doubling minima, one ascending
+//      fp32 chain per output, and g = min(1 - sum, c[n]) -- the exact sum never exceeds c[n], the fp32 one may by its rounding,
+//      and nothing behind this kernel would trim it.  g is computed ONCE per output and applied to the C rows in a channel loop
+//      (the 2 H + 1 FMAs per output and the doubling minima are the kernel's cost and do not depend on the channel; a second
+//      grid dimension would repeat them C times).  Per tile: min g, max |out| over the rows.
 //   3. ls_fold_kernel: one workgroup: record = {min g, max |out|} over [m0, m1) (exact folds: no order to fix).
-// Three launches per call, whatever the span.
+// Three launches per call, whatever the span and whatever C.
 struct ls_span {
     long long g0, wl, wh;         // the window's origin; window and row intersect in [wl, wh) (global)
     long long n;                  // n_total (INT64_MAX: unknown)
@@ -36,7 +44,9 @@ struct ls_span {
 };
 
 #define LS_SPAN_MAX (1LL << 30)   // outputs per call
+#define LS_CMAX 8
 
+// (one envelope per programme: the layout does not depend on C)
 static void ls_layout(long long n_span, int H, size_t* total, ls_span* m, char* base) {
     const long long nc = n_span + 4LL * H;
     const long long nte = nc / TP_TILE + 3;               // (any anchoring of the tiles, and the tail's)
@@ -61,81 +71,90 @@ static void ls_layout(long long n_span, int H, size_t* total, ls_span* m, char* 
 // n = K - c / R collects the R interpolated values of K and |x[n]|.  q = c / R, rem = c mod R: value (K, p) lies in the row iff
 // (n > 0 or n == 0 and p >= rem) and (n < N or n == N and p < rem) -- lk_env_kernel's c <= K R + p < c + R N without the
 // product, which does not fit 64 bits when N is unknown.
-template <int R, bool VEC>
-__global__ __launch_bounds__(TP_T) void ls_env_kernel(const float* __restrict__ xw, const float* __restrict__ bank, int J, int Jp,
-                                                      int c, long long Kal, float thr, ls_span s) {
+template <int R>
+__global__ __launch_bounds__(TP_T) void ls_env_kernel(const float* __restrict__ xw, long long w_stride, int C,
+                                                      const float* __restrict__ bank, int J, int Jp, int c, long long Kal,
+                                                      float thr, ls_span s) {
     extern __shared__ float4 tp_lds[];
-    float* red = reinterpret_cast<float*>(tp_lds);        // [(R + 1) TP_T] before the sums stage their tile over it
+    float* red = reinterpret_cast<float*>(tp_lds);        // [(R + C) TP_T] before the sums stage their tile over it
     const int l = threadIdx.x;
     const int q = c / R, rem = c - q * R;
     const long long K0 = Kal + (s.tlo + (long long)blockIdx.x) * TP_TILE;
     const long long nb = K0 + TP_KPL * l - q;             // the sample of this lane's first K
-    float mx = 0.f;                                       // max |x| over what the sums of this tile read
-    for (int i = l; i < TP_TILE + Jp; i += TP_T) {
-        const long long j = K0 - Jp + 1 + i;
-        if (j >= s.wl && j < s.wh) mx = fmaxf(mx, fabsf(xw[j - s.g0]));
-    }
-    float xv[TP_KPL];
-#pragma unroll
-    for (int k = 0; k < TP_KPL; ++k) {
-        const long long nn = nb + k;
-        xv[k] = nn >= s.a && nn < s.b ? fabsf(xw[nn - s.g0]) : 0.f;
-    }
 #pragma unroll
     for (int p = 0; p < R; ++p) {
         float v = 0.f;
         for (int i = l; i < J; i += TP_T) v += fabsf(bank[p * J + i]);
         red[p * TP_T + l] = v;
     }
-    red[R * TP_T + l] = mx;
+    for (int ch = 0; ch < C; ++ch) {
+        const float* xc = xw + (long long)ch * w_stride;
+        float mx = 0.f;                                   // max |x_c| over what the sums of this tile read
+        for (int i = l; i < TP_TILE + Jp; i += TP_T) {
+            const long long j = K0 - Jp + 1 + i;
+            if (j >= s.wl && j < s.wh) mx = fmaxf(mx, fabsf(xc[j - s.g0]));
+        }
+        red[(R + ch) * TP_T + l] = mx;
+    }
     __syncthreads();
-    for (int h = TP_T / 2; h > 0; h >>= 1) {
+    for (int h = TP_T / 2; h > 0; h >>= 1) {              // one tree: the phases' l1 norms and the channels' maxima
         if (l < h) {
 #pragma unroll
             for (int p = 0; p < R; ++p) red[p * TP_T + l] += red[p * TP_T + l + h];
-            red[R * TP_T + l] = fmaxf(red[R * TP_T + l], red[R * TP_T + l + h]);
+            for (int ch = R; ch < R + C; ++ch) red[ch * TP_T + l] = fmaxf(red[ch * TP_T + l], red[ch * TP_T + l + h]);
         }
         __syncthreads();
     }
     float l1 = 1.f;                                       // (the sample itself counts with weight 1)
 #pragma unroll
     for (int p = 0; p < R; ++p) l1 = fmaxf(l1, red[p * TP_T]);
-    const bool hot = red[R * TP_T] * l1 * 1.001f > thr;   // (uniform; 1.001 is far above the rounding of J fp32 FMAs)
+    unsigned hot = 0;                                     // (uniform; 1.001 is far above the rounding of J fp32 FMAs)
+    for (int ch = 0; ch < C; ++ch) hot |= (unsigned)(red[(R + ch) * TP_T] * l1 * 1.001f > thr) << ch;
     __syncthreads();                                      // (red is read: the sums may stage)
-    if (!hot) {
+    float xv[TP_KPL], ev[TP_KPL];                         // max_c |x_c[n]|, max_c of the interpolated values of n
+#pragma unroll
+    for (int k = 0; k < TP_KPL; ++k) { xv[k] = 0.f; ev[k] = 0.f; }
+    const int any = hot != 0;
+    for (int ch = 0; ch < C; ++ch) {
+        if (!(hot >> ch & 1u)) continue;
+        const float* xc = xw + (long long)ch * w_stride;
 #pragma unroll
         for (int k = 0; k < TP_KPL; ++k) {
             const long long nn = nb + k;
-            if (nn >= s.a && nn < s.b) s.cbuf[nn - s.a] = 1.f;
-            else if (s.tail && nn == s.n) *s.ctail = 1.f;
+            if (nn >= s.a && nn < s.b) xv[k] = fmaxf(xv[k], fabsf(xc[nn - s.g0]));
         }
-        if (l == 0) s.flag[blockIdx.x] = 0;
-        return;
+        float aa[R][TP_KPL], ab[R][TP_KPL];
+        const bool vec = ((((uintptr_t)xc >> 2) - (uintptr_t)s.g0) & 3u) == 0;      // (uniform; the values do not depend on it)
+        if (vec) tp_tile_sums<R, true>(xc, s.wh - s.g0, bank, J, Jp, K0 - s.g0, tp_lds, aa, ab);
+        else tp_tile_sums<R, false>(xc, s.wh - s.g0, bank, J, Jp, K0 - s.g0, tp_lds, aa, ab);
+#pragma unroll
+        for (int k = 0; k < TP_KPL; ++k) {
+            const long long nn = nb + k;
+#pragma unroll
+            for (int p = 0; p < R; ++p) {
+                const bool lo_ok = nn > 0 || (nn == 0 && p >= rem);
+                const bool hi_ok = !s.known || nn < s.n || (nn == s.n && p < rem);
+                if (lo_ok && hi_ok) ev[k] = fmaxf(ev[k], fabsf(aa[p][k] + ab[p][k]));
+            }
+        }
+        __syncthreads();                                  // (the staged tile is read: the next channel may stage its own)
     }
-    float aa[R][TP_KPL], ab[R][TP_KPL];
-    tp_tile_sums<R, VEC>(xw, s.wh - s.g0, bank, J, Jp, K0 - s.g0, tp_lds, aa, ab);
 #pragma unroll
     for (int k = 0; k < TP_KPL; ++k) {
         const long long nn = nb + k;
-        float ev = 0.f;
-#pragma unroll
-        for (int p = 0; p < R; ++p) {
-            const bool lo_ok = nn > 0 || (nn == 0 && p >= rem);
-            const bool hi_ok = !s.known || nn < s.n || (nn == s.n && p < rem);
-            if (lo_ok && hi_ok) ev = fmaxf(ev, fabsf(aa[p][k] + ab[p][k]));
-        }
         if (nn >= s.a && nn < s.b) {
-            const float e = fmaxf(xv[k], ev);
-            s.cbuf[nn - s.a] = e > thr ? thr / e : 1.f;
+            const float e = fmaxf(xv[k], ev[k]);
+            s.cbuf[nn - s.a] = any && e > thr ? thr / e : 1.f;
         } else if (s.tail && nn == s.n) {
-            *s.ctail = ev > thr ? thr / ev : 1.f;
+            *s.ctail = any && ev[k] > thr ? thr / ev[k] : 1.f;
         }
     }
-    if (l == 0) s.flag[blockIdx.x] = 1;
+    if (l == 0) s.flag[blockIdx.x] = any;
 }
 
-// The envelope at R = 1 (and of the sample-peak mode): e[n] = |x[n]|; tile t holds samples from a + t TP_TILE.
-__global__ __launch_bounds__(TP_T) void ls_env1_kernel(const float* __restrict__ xw, float thr, ls_span s) {
+// The envelope at R = 1 (and of the sample-peak mode): e[n] = max_c |x_c[n]|; tile t holds samples from a + t TP_TILE.
+__global__ __launch_bounds__(TP_T) void ls_env1_kernel(const float* __restrict__ xw, long long w_stride, int C, float thr,
+                                                       ls_span s) {
     const int l = threadIdx.x;
     const long long n0 = s.a + (long long)blockIdx.x * TP_TILE;
     int hot = 0;
@@ -143,7 +162,8 @@ __global__ __launch_bounds__(TP_T) void ls_env1_kernel(const float* __restrict__
     for (int k = 0; k < TP_KPL; ++k) {
         const long long nn = n0 + l + k * TP_T;
         if (nn < s.b) {
-            const float e = fabsf(xw[nn - s.g0]);
+            float e = 0.f;
+            for (int ch = 0; ch < C; ++ch) e = fmaxf(e, fabsf(xw[(long long)ch * w_stride + (nn - s.g0)]));
             s.cbuf[nn - s.a] = e > thr ? thr / e : 1.f;
             hot |= e > thr;
         }
@@ -154,8 +174,9 @@ __global__ __launch_bounds__(TP_T) void ls_env1_kernel(const float* __restrict__
 
 // off: envelope tile of sample j is (j + off) / TP_TILE - tlo (c / R - Kal at R > 1) or (j - a) / TP_TILE (R = 1: off = -a,
 // tlo = 0).  lev, the dynamic LDS and the arithmetic: lk_limit_kernel's.
-__global__ __launch_bounds__(LM_T) void ls_limit_kernel(const float* __restrict__ xw, float gL, int H, int lev, long long off,
-                                                        ls_span s, float* __restrict__ out) {
+__global__ __launch_bounds__(LM_T) void ls_limit_kernel(const float* __restrict__ xw, long long w_stride, int C, float gL, int H,
+                                                        int lev, long long off, ls_span s, float* __restrict__ out,
+                                                        long long out_stride) {
     extern __shared__ float lm_lds[];
     float* ra = lm_lds;                                   // (lm_minmax starts with a barrier: cs and ds are done with by then)
     float* rb = lm_lds + LM_T;
@@ -174,13 +195,17 @@ __global__ __launch_bounds__(LM_T) void ls_limit_kernel(const float* __restrict_
     }
     float gm = 1.f, vm = 0.f;
     if (!active) {
+        for (int ch = 0; ch < C; ++ch) {
+            const float* xc = xw + (long long)ch * w_stride;
+            float* oc = out + (long long)ch * out_stride;
 #pragma unroll
-        for (int e = 0; e < LM_PER; ++e) {
-            const long long nn = n0 + l + e * LM_T;
-            if (nn < s.m1) {
-                const float v = xw[nn - s.g0] * gL;
-                out[nn - s.m0] = v;
-                vm = fmaxf(vm, fabsf(v));
+            for (int e = 0; e < LM_PER; ++e) {
+                const long long nn = n0 + l + e * LM_T;
+                if (nn < s.m1) {
+                    const float v = xc[nn - s.g0] * gL;
+                    oc[nn - s.m0] = v;
+                    vm = fmaxf(vm, fabsf(v));
+                }
             }
         }
     } else {
@@ -229,19 +254,33 @@ __global__ __launch_bounds__(LM_T) void ls_limit_kernel(const float* __restrict_
 #pragma unroll
             for (int e = 0; e < LM_PER; ++e) acc[e] = fmaf(w, ds[l + e * LM_T + kk], acc[e]);
         }
+        float gg[LM_PER];                                 // float(gL) g of this lane's outputs, the same for every channel
 #pragma unroll
         for (int e = 0; e < LM_PER; ++e) {
             const long long nn = n0 + l + e * LM_T;
+            gg[e] = gL;
             if (nn < s.m1) {
                 // g <= c[n] holds for the exact sum (every m under the window covers n); the fp32 chain drifts by up to
-                // (2 H + 1) 2^-24, and a session has no trim behind it: the minimum keeps every SAMPLE under the ceiling
+                // (2 H + 1) 2^-24, and a session has no trim behind it: the minimum keeps every SAMPLE of every channel under
+                // the ceiling
                 float cn = s.cbuf[nn - s.a];
                 if (s.tail && nn == n - 1) cn = fminf(cn, *s.ctail);
                 const float g = fminf(1.f - acc[e], cn);
-                const float v = xw[nn - s.g0] * (gL * g);
-                out[nn - s.m0] = v;
+                gg[e] = gL * g;
                 gm = fminf(gm, g);
-                vm = fmaxf(vm, fabsf(v));
+            }
+        }
+        for (int ch = 0; ch < C; ++ch) {
+            const float* xc = xw + (long long)ch * w_stride;
+            float* oc = out + (long long)ch * out_stride;
+#pragma unroll
+            for (int e = 0; e < LM_PER; ++e) {
+                const long long nn = n0 + l + e * LM_T;
+                if (nn < s.m1) {
+                    const float v = xc[nn - s.g0] * gg[e];
+                    oc[nn - s.m0] = v;
+                    vm = fmaxf(vm, fabsf(v));
+                }
             }
         }
     }
@@ -267,18 +306,18 @@ __global__ __launch_bounds__(LM_T) void ls_fold_kernel(ls_span s, double* __rest
     }
 }
 
-extern "C" size_t vfx_limit_span_workspace_bytes(int64_t n_span, int H) {
-    if (n_span < 0 || n_span > LS_SPAN_MAX || H < 1 || H > LM_HMAX) return 0;
-    size_t total = 0;
-    ls_layout(n_span, H, &total, nullptr, nullptr);
-    return total;
-}
-
-extern "C" int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0, int64_t m1, double gain,
-                                  double ceiling_db, int H, const float* bank, int J, int R, int c, float* out, double* record,
-                                  void* ws, size_t ws_bytes, vfx_stream_t stream) {
+// Validation, geometry and the three launches of both entry points.  ``rows``: the linked entry, which also checks C and the
+// strides and refuses an overlap of the blocks of windows and outputs BEFORE it accepts an empty span; the mono entry accepts
+// the empty span first (each keeps the order it had as a file of its own).  Nothing is launched where anything is refused.
+static int ls_run(bool rows, const float* xw, int64_t w_stride, int C, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0,
+                  int64_t m1, double gain, double ceiling_db, int H, const float* bank, int J, int R, int c, float* out,
+                  int64_t out_stride, double* record, void* ws, size_t ws_bytes, vfx_stream_t stream) {
     if (!xw || !out || !record || !ws || g0 < 0 || wlen < 0 || n_total < 0 || m0 < 0 || m1 < m0 || m1 > n_total) return VFX_EINVAL;
+    if (!rows) out_stride = m1 - m0;                      // (the one row: C = 1, w_stride = wlen from the entry point)
     if (H < 1 || H > LM_HMAX || (R != 1 && R != 2 && R != 4) || g0 > INT64_MAX - wlen || m1 - m0 > LS_SPAN_MAX) return VFX_EINVAL;
+    if (rows && (C < 1 || C > LS_CMAX || w_stride < wlen || out_stride < m1 - m0 || w_stride > (INT64_MAX >> 6) ||
+                 out_stride > (INT64_MAX >> 6)))
+        return VFX_EINVAL;
     if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite(ceiling_db)) return VFX_EINVAL;
     if (R > 1 && (!bank || J < 1 || J > TP_JMAX || c < 0 || (long long)c >= (long long)R * J)) return VFX_EINVAL;
     const double cl = pow(10.0, ceiling_db / 20.0);
@@ -288,7 +327,13 @@ extern "C" int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int
     ls_span s = {};
     ls_layout(m1 - m0, H, &need, &s, (char*)ws);
     if (ws_bytes < need || ((uintptr_t)ws & 15u)) return VFX_EINVAL;
+    // the block of the outputs may not overlap the block of the windows
+    const uintptr_t xb = (uintptr_t)xw, xe = (uintptr_t)(xw + (C - 1) * w_stride + wlen);
+    const uintptr_t ob = (uintptr_t)out, oe = (uintptr_t)(out + (C - 1) * out_stride + (m1 - m0));
+    const bool overlap = !(xe <= ob || oe <= xb);
+    if (rows && overlap) return VFX_EINVAL;
     if (m0 == m1) return VFX_OK;
+    if (overlap) return VFX_EINVAL;
     const long long q = R > 1 ? c / R : 0;
     const long long Fw = q, Bk = R > 1 ? (long long)J - 1 - q : 0;
     const long long reach = 2LL * H;
@@ -304,10 +349,6 @@ extern "C" int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int
     if (need_lo < g0 || need_hi - g0 >= wlen) return VFX_EINVAL;
     s.wl = g0;
     s.wh = n_total - g0 < wlen ? n_total : g0 + wlen;
-    {   // out may not overlap the window
-        const uintptr_t xb = (uintptr_t)xw, xe = (uintptr_t)(xw + wlen), ob = (uintptr_t)out, oe = (uintptr_t)(out + (m1 - m0));
-        if (!(xe <= ob || oe <= xb)) return VFX_EINVAL;
-    }
     s.tail = R > 1 && s.known && s.b == n_total;
     s.nto = (m1 - m0 + LM_TILE - 1) / LM_TILE;
     hipStream_t st = (hipStream_t)stream;
@@ -319,26 +360,50 @@ extern "C" int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int
         s.nte = ((s.tail ? n_total : s.b - 1) + off) / TP_TILE - s.tlo + 1;
         const int Jp = tp_jp(J);
         size_t tp_bytes = (size_t)(TP_TILE + Jp + R * Jp) * sizeof(float);
-        if (tp_bytes < (size_t)(R + 1) * TP_T * sizeof(float)) tp_bytes = (size_t)(R + 1) * TP_T * sizeof(float);   // (red, at a tiny J)
-        const bool vx = ((uintptr_t)xw & 3u) == 0 && ((((uintptr_t)xw >> 2) - (uintptr_t)g0) & 3u) == 0;
+        if (tp_bytes < (size_t)(R + C) * TP_T * sizeof(float)) tp_bytes = (size_t)(R + C) * TP_T * sizeof(float);     // (red)
         const dim3 gt((unsigned)s.nte);
-#define LS_ENV_LAUNCH(RR, VV) hipLaunchKernelGGL((ls_env_kernel<RR, VV>), gt, dim3(TP_T), tp_bytes, st, xw, bank, J, Jp, c, Kal, thr, s)
-        if (R == 4) { if (vx) LS_ENV_LAUNCH(4, true); else LS_ENV_LAUNCH(4, false); }
-        else { if (vx) LS_ENV_LAUNCH(2, true); else LS_ENV_LAUNCH(2, false); }
-#undef LS_ENV_LAUNCH
+        if (R == 4) hipLaunchKernelGGL((ls_env_kernel<4>), gt, dim3(TP_T), tp_bytes, st, xw, (long long)w_stride, C, bank, J, Jp, c, Kal, thr, s);
+        else hipLaunchKernelGGL((ls_env_kernel<2>), gt, dim3(TP_T), tp_bytes, st, xw, (long long)w_stride, C, bank, J, Jp, c, Kal, thr, s);
     } else {
         off = -s.a;
         s.tlo = 0;
         s.nte = (s.b - s.a + TP_TILE - 1) / TP_TILE;
-        hipLaunchKernelGGL(ls_env1_kernel, dim3((unsigned)s.nte), dim3(TP_T), 0, st, xw, thr, s);
+        hipLaunchKernelGGL(ls_env1_kernel, dim3((unsigned)s.nte), dim3(TP_T), 0, st, xw, (long long)w_stride, C, thr, s);
     }
     VFX_LAUNCHED();
     int lev = 0;
     while ((2 << lev) <= 2 * H + 1) ++lev;
     const size_t lds = (size_t)(LM_TILE + 4 * H + LM_TILE + 2 * H + H + 1) * sizeof(float);
-    int err = vfx_launch<ls_limit_kernel>(dim3((unsigned)s.nto), dim3(LM_T), lds, st, xw, gLf, H, lev, off, s, out);
+    int err = vfx_launch<ls_limit_kernel>(dim3((unsigned)s.nto), dim3(LM_T), lds, st, xw, (long long)w_stride, C, gLf, H, lev, off, s,
+                                          out, (long long)out_stride);
     if (err != VFX_OK) return err;
     hipLaunchKernelGGL(ls_fold_kernel, dim3(1), dim3(LM_T), 0, st, s, record);
     VFX_LAUNCHED();
     return vfx_last_error();
+}
+
+extern "C" size_t vfx_limit_span_workspace_bytes(int64_t n_span, int H) {
+    if (n_span < 0 || n_span > LS_SPAN_MAX || H < 1 || H > LM_HMAX) return 0;
+    size_t total = 0;
+    ls_layout(n_span, H, &total, nullptr, nullptr);
+    return total;
+}
+
+extern "C" size_t vfx_limit_span_rows_workspace_bytes(int64_t n_span, int H, int C) {
+    return C < 1 || C > LS_CMAX ? 0 : vfx_limit_span_workspace_bytes(n_span, H);
+}
+
+extern "C" int vfx_limit_span_f32(const float* xw, int64_t g0, int64_t wlen, int64_t n_total, int64_t m0, int64_t m1, double gain,
+                                  double ceiling_db, int H, const float* bank, int J, int R, int c, float* out, double* record,
+                                  void* ws, size_t ws_bytes, vfx_stream_t stream) {
+    return ls_run(false, xw, wlen, 1, g0, wlen, n_total, m0, m1, gain, ceiling_db, H, bank, J, R, c, out, 0, record, ws, ws_bytes,
+                  stream);
+}
+
+extern "C" int vfx_limit_span_rows_f32(const float* xw, int64_t w_stride, int C, int64_t g0, int64_t wlen, int64_t n_total,
+                                       int64_t m0, int64_t m1, double gain, double ceiling_db, int H, const float* bank, int J, int R,
+                                       int c, float* out, int64_t out_stride, double* record, void* ws, size_t ws_bytes,
+                                       vfx_stream_t stream) {
+    return ls_run(true, xw, w_stride, C, g0, wlen, n_total, m0, m1, gain, ceiling_db, H, bank, J, R, c, out, out_stride, record, ws,
+                  ws_bytes, stream);
 }

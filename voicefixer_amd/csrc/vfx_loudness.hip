@@ -901,9 +901,7 @@ extern "C" int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const in
                   out_stride, result, ws, ws_bytes, stream, G, group_start, weight, H);
 }
 
-/* ---- fixed-gain look-ahead limiter of a streaming session, span form -------------------------------------- */
+/* ---- the span stages of a streaming session, one row or the linked channels of a programme ----------- */
 
 #include "vfx_limit_span.inc"
 #include "vfx_level_span.inc"
-#include "vfx_limit_span_rows.inc"
-#include "vfx_level_span_rows.inc"

@@ -798,18 +798,15 @@ def loudness_limit(x, n_rows, rate, target, ceiling_db=-1.0, true_peak=True, loo
     return res
 
 
-def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, true_peak=False, lookahead_ms=3.0):
-    """Outputs [m0, m1) of the fixed-gain look-ahead limiter over ONE row from a window of it (vfx_limit_span_f32; loudness.py,
-    DESIGN.md 3.16): xw (wlen,) device holds samples [g0, g0 + wlen) of a row of ``n_total`` samples at ``rate`` Hz (None: its
-    end is not known yet), out (>= m1 - m0,) receives output n at out[n - m0] -- the bits the single span [0, n_total) over the
-    whole row writes for it.  The window must cover [m0 - 2 H - Bk, m1 - 1 + 2 H + Fw] clipped to the row
-    (loudness.limiter_reach), or VfxError.  Returns the record, a device float64 (2,) of {min g, max |out|} over the span
-    ({1, 0} for an empty one).  Three launches, no synchronisation."""
+def _limit_span_impl(name, rows, xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db, true_peak, lookahead_ms):
+    """``limit_span`` and ``limit_span_rows`` (``name``) behind their checks of the window and the output: rows = (C, w_stride,
+    out_stride) of xw (C, wlen) and out (C, >= m1 - m0) -- a row is (1, wlen, m1 - m0), its 1-D tensors taken as they are (only
+    their pointers and the last dimension are used, so no 2-D view is made); m0 and m1 are ints.  Only the entry point depends on
+    ``name``: a row keeps the mono entry point, its order of refusals and its name in an error."""
     from . import loudness
-    m0, m1 = _check_span("limit_span", xw, out, m0, m1)
     gain_db = loudness.check_gain(gain_db)
     if gain_db is None:
-        raise ValueError("limit_span: the limiter needs a gain (gain_db=...)")
+        raise ValueError("%s: the limiter needs a gain (gain_db=...)" % name)
     ceiling_db = loudness.check_ceiling(ceiling_db)
     true_peak = loudness.check_true_peak(true_peak)
     H = loudness.limiter_window(rate, lookahead_ms)[0]
@@ -818,13 +815,26 @@ def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, tru
     R = loudness.oversampling(rate) if true_peak else 1
     bank, J, c = true_peak_bank(xw.device, R) if R > 1 else (None, 1, 0)
     h = _lib.lib()
-    nb = h.vfx_limit_span_workspace_bytes(max(m1 - m0, 0), H)
+    nb = h.vfx_limit_span_rows_workspace_bytes(m1 - m0, H, rows[0])
     ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
     rec = torch.empty((2,), dtype=torch.float64, device=xw.device)
-    check(h.vfx_limit_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total), m0, m1,
-                               10.0 ** (gain_db / 20.0), ceiling_db, H, _ptr(bank), J, R, c, _ptr(out), _ptr(rec), _ptr(ws), nb,
-                               _stream()), "vfx_limit_span_f32")
+    span = (int(g0), xw.shape[-1], INT64_MAX if n_total is None else int(n_total), m0, m1, 10.0 ** (gain_db / 20.0), ceiling_db, H,
+            _ptr(bank), J, R, c, _ptr(out))
+    tail = (_ptr(rec), _ptr(ws), nb, _stream())
+    check(h.vfx_limit_span_f32(_ptr(xw), *span, *tail) if name == "limit_span" else
+          h.vfx_limit_span_rows_f32(_ptr(xw), rows[1], rows[0], *span, rows[2], *tail), "vfx_%s_f32" % name)
     return rec
+
+
+def limit_span(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0, true_peak=False, lookahead_ms=3.0):
+    """Outputs [m0, m1) of the fixed-gain look-ahead limiter over ONE row from a window of it (vfx_limit_span_f32; loudness.py,
+    DESIGN.md 3.16): xw (wlen,) device holds samples [g0, g0 + wlen) of a row of ``n_total`` samples at ``rate`` Hz (None: its
+    end is not known yet), out (>= m1 - m0,) receives output n at out[n - m0] -- the bits the single span [0, n_total) over the
+    whole row writes for it.  The window must cover [m0 - 2 H - Bk, m1 - 1 + 2 H + Fw] clipped to the row
+    (loudness.limiter_reach), or VfxError.  Returns the record, a device float64 (2,) of {min g, max |out|} over the span
+    ({1, 0} for an empty one).  Three launches, no synchronisation."""
+    m0, m1 = _check_span("limit_span", xw, out, m0, m1)
+    return _limit_span_impl("limit_span", (1, xw.numel(), m1 - m0), xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db, true_peak, lookahead_ms)
 
 
 def _check_span_rows(name, xw, out, m0, m1):
@@ -850,26 +860,9 @@ def limit_span_rows(xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db=-1.0
     (vfx_limit_span_rows_f32): ``limit_span`` with xw (C, wlen) and out (C, >= m1 - m0), rows of unit stride and
     any row stride.  One envelope, the maximum over the channels, hence one gain for all of them; the record is {min g, max |out|
     over all channels}.  C = 1: the bits and the record of ``limit_span``.  Three launches, no synchronisation."""
-    from . import loudness
     C_, m0, m1, ws_, os_ = _check_span_rows("limit_span_rows", xw, out, m0, m1)
-    gain_db = loudness.check_gain(gain_db)
-    if gain_db is None:
-        raise ValueError("limit_span_rows: the limiter needs a gain (gain_db=...)")
-    ceiling_db = loudness.check_ceiling(ceiling_db)
-    true_peak = loudness.check_true_peak(true_peak)
-    H = loudness.limiter_window(rate, lookahead_ms)[0]
-    if m1 == m0:
-        return torch.tensor([1.0, 0.0], dtype=torch.float64).to(xw.device)
-    R = loudness.oversampling(rate) if true_peak else 1
-    bank, J, c = true_peak_bank(xw.device, R) if R > 1 else (None, 1, 0)
-    h = _lib.lib()
-    nb = h.vfx_limit_span_rows_workspace_bytes(max(m1 - m0, 0), H, C_)
-    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
-    rec = torch.empty((2,), dtype=torch.float64, device=xw.device)
-    check(h.vfx_limit_span_rows_f32(_ptr(xw), ws_, C_, int(g0), xw.shape[1], INT64_MAX if n_total is None else int(n_total), m0,
-                                    m1, 10.0 ** (gain_db / 20.0), ceiling_db, H, _ptr(bank), J, R, c, _ptr(out), os_, _ptr(rec),
-                                    _ptr(ws), nb, _stream()), "vfx_limit_span_rows_f32")
-    return rec
+    return _limit_span_impl("limit_span_rows", (C_, ws_, os_), xw, g0, n_total, rate, gain_db, m0, m1, out, ceiling_db, true_peak,
+                            lookahead_ms)
 
 
 _LEVELLER_MPOW = {}
@@ -881,6 +874,31 @@ def level_state(device):
     return torch.zeros((loudness.LEVELLER_STATE,), dtype=torch.float64, device=device)
 
 
+def _level_span_impl(name, rows, xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db, gate, weights):
+    """``level_span`` and ``level_span_rows`` (``name``) behind their checks of the window and the output: rows, xw, out, m0, m1
+    as in ``_limit_span_impl``.  Only the entry point, which for a row takes no weights, depends on ``name``."""
+    from . import loudness
+    _need_cuda(state)
+    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
+    target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
+    wt = None if name == "level_span" else (C.c_double * rows[0])(*loudness.channel_weights(rows[0], weights))
+    p = loudness.leveller_plan(rate)
+    key = (str(xw.device), int(rate))
+    mpow = _LEVELLER_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
+        _LEVELLER_MPOW[key] = mpow
+    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
+    h = _lib.lib()
+    nb = h.vfx_level_span_rows_workspace_bytes(max(m1 - m0, 0), p["hop"], rows[0])
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    span = (int(g0), xw.shape[-1], INT64_MAX if n_total is None else int(n_total), m0, m1, int(rate), coef, _ptr(mpow), p["S"], target,
+            max_gain_db, gate, _ptr(state), _ptr(out))
+    tail = (_ptr(ws), nb, _stream())
+    check(h.vfx_level_span_f32(_ptr(xw), *span, *tail) if name == "level_span" else
+          h.vfx_level_span_rows_f32(_ptr(xw), rows[1], rows[0], wt, *span, rows[2], *tail), "vfx_%s_f32" % name)
+
+
 def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12.0, gate=-50.0):
     """Outputs [m0, m1) of the streaming loudness leveller over ONE row from a window of it (vfx_level_span_f32; loudness.py,
     DESIGN.md 3.17): xw (wlen,) device holds samples [g0, g0 + wlen) of a row of ``n_total`` samples at ``rate`` Hz (None: its
@@ -889,24 +907,8 @@ def level_span(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12
     before) on one ``state`` (``level_state``), which carries the last quarters' energies, the held gain and the record
     state[:4] = {min G, max G, anchors, gated}.  The window must cover [m0, m1) and the regions of the quarters that become
     measurable (loudness.leveller_counts), or VfxError.  At most three launches, no synchronisation."""
-    from . import loudness
     m0, m1 = _check_span("level_span", xw, out, m0, m1)
-    _need_cuda(state)
-    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
-    target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
-    p = loudness.leveller_plan(rate)
-    key = (str(xw.device), int(rate))
-    mpow = _LEVELLER_MPOW.get(key)
-    if mpow is None:
-        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
-        _LEVELLER_MPOW[key] = mpow
-    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
-    h = _lib.lib()
-    nb = h.vfx_level_span_workspace_bytes(max(m1 - m0, 0), p["hop"])
-    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
-    check(h.vfx_level_span_f32(_ptr(xw), int(g0), xw.numel(), INT64_MAX if n_total is None else int(n_total), m0, m1, int(rate),
-                               coef, _ptr(mpow), p["S"], target, max_gain_db, gate, _ptr(state), _ptr(out), _ptr(ws), nb,
-                               _stream()), "vfx_level_span_f32")
+    _level_span_impl("level_span", (1, xw.numel(), m1 - m0), xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db, gate, None)
 
 
 def level_span_rows(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db=12.0, gate=-50.0, weights=None):
@@ -915,25 +917,8 @@ def level_span_rows(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_
     any row stride, and ONE ``state``.  The quarter energies are summed over the channels with ``weights``
     (loudness.channel_weights(C, weights): BS.1770-4 Table 4 by default), so one ramp multiplies every channel.  C = 1 with the
     weight 1: the bits and the state of ``level_span``.  At most three launches, no synchronisation."""
-    from . import loudness
     C_, m0, m1, ws_, os_ = _check_span_rows("level_span_rows", xw, out, m0, m1)
-    _need_cuda(state)
-    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.LEVELLER_STATE and state.stride(0) == 1
-    target, max_gain_db, gate = loudness.check_leveller(target, max_gain_db, gate, rate)
-    wt = (C.c_double * C_)(*loudness.channel_weights(C_, weights))
-    p = loudness.leveller_plan(rate)
-    key = (str(xw.device), int(rate))
-    mpow = _LEVELLER_MPOW.get(key)
-    if mpow is None:
-        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
-        _LEVELLER_MPOW[key] = mpow
-    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
-    h = _lib.lib()
-    nb = h.vfx_level_span_rows_workspace_bytes(max(m1 - m0, 0), p["hop"], C_)
-    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
-    check(h.vfx_level_span_rows_f32(_ptr(xw), ws_, C_, wt, int(g0), xw.shape[1], INT64_MAX if n_total is None else int(n_total),
-                                    m0, m1, int(rate), coef, _ptr(mpow), p["S"], target, max_gain_db, gate, _ptr(state), _ptr(out),
-                                    os_, _ptr(ws), nb, _stream()), "vfx_level_span_rows_f32")
+    _level_span_impl("level_span_rows", (C_, ws_, os_), xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db, gate, weights)
 
 
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):
