@@ -650,6 +650,66 @@ int vfx_level_span_rows_f32(const float* xw, int64_t w_stride, int C, const doub
                             double target, double max_gain_db, double gate, double* state, float* out, int64_t out_stride,
                             void* ws, size_t ws_bytes, vfx_stream_t stream);
 
+/* ---- streaming loudness meter of a session: the span form and its report (voicefixer_amd/loudness.py) --------- */
+
+#define VFX_METER_STATE 16 /* float64 values of the caller's state */
+
+/* Bytes of the workspace of vfx_meter_span_rows_f32 for spans of up to n_span samples per channel at quarters of hop samples (0
+ * on bad arguments: n_span < 0 or > 2^30, hop outside [400, 19200], C outside [1, 8]): 8 bytes per quarter of the span and
+ * channel, 8 bytes per 1024 samples, and a few more. */
+size_t vfx_meter_span_workspace_bytes(int64_t n_span, int hop, int C);
+
+/* Folds the samples [m0, m1) of a programme of C channels of n_total samples each at fs Hz (INT64_MAX: the end is not known
+ * yet) into the caller's meter: state and qlog.  Channel ch's window is xw + ch w_stride, xw[ch w_stride + k] = x_ch[g0 + k],
+ * k < wlen; g0, wlen, n_total, m0, m1 hold for every channel.  hop = (fs + 5) / 10, nq(m) = m / hop.  After [0, m):
+ *   qlog[q], q < nq(m) = sum_c weight[c] E_{q,c}   (float64, c ascending from 0.0, every product and every sum rounded on its
+ *         own), E_{q,c} the quarter energy of vfx_level_span_f32: the linked quarter energy of vfx_level_span_rows_f32, bit for bit;
+ *   state: [0] P = max_c max |x_c[n]|, n < m   [1] TP = max(P, the largest |y| among the interpolated values that BELONG to a
+ *         sample n < m)   [2] quarters logged = nq(m)   [3] samples metered = m   [4] 1 once a call came out of order (sticky)
+ *         [5..16) zero.  y: the R-phase interpolation of vfx_loudness_tp_rows_f32 (bank / J / c as there; R = 1: nothing is
+ *         interpolated, TP = P, bank may be NULL); value (K, p) belongs to sample n = K - c / R, reads x[n - Bk .. n + Fw], Fw =
+ *         c / R, Bk = J - 1 - c / R (both 0 at R = 1), and counts iff it lies in the row, by the tests of vfx_limit_span_f32's
+ *         envelope.  The R - 1 values behind the last sample (n = n_total) are folded by the call with m1 == n_total, so that
+ *         after it TP is the true peak of vfx_loudness_tp_rows_f32 over the whole programme, bit for bit.
+ * Every value is a function of global positions and every fold is a maximum: state and qlog have the bits of one call over
+ * the whole row, whatever the split, the window, g0, the stride or the alignment.  Calls come IN ORDER: the first has m0 = 0
+ * (which initialises state; a zeroed state is that of a programme with nothing metered), every other the m1 of the one before; a
+ * call out of order sets state[4] and stays inside its buffers.  Ready rule while the end is unknown: m1 <= n_known - Fw
+ * (n_known = g0 + wlen).  Every channel's window must cover [max(0, m0 - Bk), min(n_total - 1, m1 - 1 + Fw)] and, when nq(m1) >
+ * nq(m0), [max(0, nq(m0) - 2) hop, nq(m1) hop); nothing else is read.  weight: C HOST doubles, finite and >= 0.  coef / mpow / S:
+ * as vfx_level_span_f32 takes them.  qlog: device float64[qcap], the caller's: 8 bytes per 100 ms of the programme.  ws: >=
+ * vfx_meter_span_workspace_bytes(m1 - m0, hop, C) bytes, 16-byte aligned.  At most three launches (new quarters of all channels;
+ * one {max |x|, max |y|} per tile of 1024 samples; the weighted sums and the fold, one workgroup), no float atomics, no host
+ * synchronisation.  An empty span (m0 == m1) is VFX_OK and launches nothing.
+ * VFX_EINVAL, nothing launched: a NULL xw, weight, coef, mpow, state, qlog or ws; g0, wlen, m0 < 0, m0 > m1, m1 > n_total, m1 -
+ * m0 > 2^30; fs outside [4000, 192000]; S not the chunk length of fs; a coefficient that is not finite; a weight that is not
+ * finite or < 0; C outside [1, 8]; w_stride < wlen; R not in {1, 2, 4}; at R > 1 a NULL bank, J outside [1, 2048] or c outside
+ * [0, R J); qcap < 0 or nq(m1) > qcap; m1 beyond the ready bound while the end is unknown; a window that does not cover the
+ * ranges above; ws too small or misaligned; state or qlog not 8-byte aligned. */
+int vfx_meter_span_rows_f32(const float* xw, int64_t w_stride, int C, const double* weight, int64_t g0, int64_t wlen,
+                            int64_t n_total, int64_t m0, int64_t m1, int fs, const double* coef, const double* mpow, int S,
+                            const float* bank, int J, int R, int c, double* state, double* qlog, int64_t qcap, void* ws,
+                            size_t ws_bytes, vfx_stream_t stream);
+
+/* Bytes of the workspace of vfx_meter_report_f32 for a meter whose log holds `quarters` quarters (0 on a negative count): 8
+ * bytes per quarter, at least 8.  Pass the log's capacity: ws_bytes / 8 is also the most quarters the report reads from qlog,
+ * whatever state says. */
+size_t vfx_meter_report_workspace_bytes(int64_t quarters);
+
+/* The EBU R 128 figures of a meter: report (device float64[10]) = {integrated loudness L, loudness range, maximum momentary,
+ * maximum short-term loudness, P, TP (both linear), momentary and short-term loudness of the LAST 4 / 30 quarters, quarters,
+ * flag}, from state and qlog[0 .. state[2]) by the recipe of vfx_loudness_report_groups_f32 on these quarter sums: z_j = (q_j +
+ * q_{j+1} + q_{j+2} + q_{j+3}) / (4 hop), L over the z_j that pass -70 LUFS and the relative gate 10 LU under their mean,
+ * maximum momentary over ALL z_j; short-term energies (30 quarters, from every quarter) with the -70 LUFS / -20 LU gates and the
+ * nearest-rank indices ((n - 1) + 5) / 10 and ((n - 1) 95 + 50) / 100, selected by counting over float64 bit patterns; fixed-order
+ * reductions.  -inf: no block (LRA then 0.0).  One launch of one workgroup, which reads the log from memory; it writes report
+ * and ws and NOTHING else, so a report in the middle of a session changes nothing that follows.  flag: state[4], or 2 where
+ * state[2] is not a count that fits ws (ws_bytes / 8 quarters): the figures are then those of an empty log.
+ * VFX_EINVAL, nothing launched: a NULL pointer; hop outside [400, 19200]; a pointer that is not 8-byte aligned; report overlapping
+ * state. */
+int vfx_meter_report_f32(const double* state, const double* qlog, int hop, double* report, void* ws, size_t ws_bytes,
+                         vfx_stream_t stream);
+
 /* ---- word-length reduction: 16- / 24-bit PCM with seeded dither (voicefixer_amd/wordlength.py) ----------------- */
 
 /* The last stage of the output chain (the reference's save_wave truncates to int16 on the host, voicefixer/tools/wav.py:27-34;

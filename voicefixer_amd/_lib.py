@@ -119,6 +119,11 @@ SIGNATURES = {
     "vfx_level_span_rows_f32": (_I, [_P, C.c_int64, _I, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I, _P, _P, _I,
                                      C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
     "vfx_quantize_rows_f32": (_I, [_P, C.c_int64, _P, _I, C.c_int64, _P, _P, _I, _I, C.c_uint64, _P, C.c_int64, _P, _P]),
+    "vfx_meter_span_workspace_bytes": (C.c_size_t, [C.c_int64, _I, _I]),
+    "vfx_meter_span_rows_f32": (_I, [_P, C.c_int64, _I, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I, _P, _P, _I,
+                                     _P, _I, _I, _I, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
+    "vfx_meter_report_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "vfx_meter_report_f32": (_I, [_P, _P, _I, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -27,8 +27,8 @@ import torch.nn as nn
 from . import audio_io, engine, weights
 from ._lib import VfxError
 # the overlap-add streaming mode lives in stream.py; its names stay reachable here
-from .stream import (LEVEL_SPAN, LIMIT_SPAN, RestoreSession, StreamPlanner, _SpanConverter, _SpanLeveller,  # noqa: F401
-                     _SpanLimiter, _check_stream_mode, _stream_geometry, plan_stream_chunks)
+from .stream import (LEVEL_SPAN, LIMIT_SPAN, LoudnessMeter, RestoreSession, StreamPlanner, _SpanConverter,  # noqa: F401
+                     _SpanLeveller, _SpanLimiter, _SpanMeter, _check_stream_mode, _stream_geometry, plan_stream_chunks)
 
 SEG_LENGTH = 44100 * 30  # voicefixer/base.py:117
 
@@ -1249,7 +1249,7 @@ class VoiceFixer(nn.Module):
     def open_stream(self, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                     sample_rate=44100, output_sample_rate=None, limiter=False, limiter_lookahead_ms=3.0, bit_depth=None,
                     dither="tpdf", dither_seed=0, gain_db=None, peak_ceiling=-1.0, true_peak=False, leveller=None,
-                    leveller_max_gain_db=12.0, leveller_gate=-50.0, **programme):
+                    leveller_max_gain_db=12.0, leveller_gate=-50.0, meter=False, **programme):
         """A push-style session of the overlap-add long-form mode (``RestoreSession``): blocks of any size go in at
         ``sample_rate``, finished stretches come out at ``output_sample_rate`` (default 44.1 kHz), nothing but the current
         chunk is held.  The results of all ``push`` calls and of ``finish``, concatenated, are what ``restore_stream``
@@ -1274,6 +1274,10 @@ class VoiceFixer(nn.Module):
         for the whole output, bit for bit, less than 1.1 s late; output rates up to 192 kHz.  With a leveller ``limiter=True``
         needs no ``gain_db`` (the limiter then runs at 0 dB; a ``gain_db`` follows the leveller as it follows the converter
         today); ``session.leveller_stats`` reports {"min_gain_db", "max_gain_db", "anchors", "gated"}.
+        ``meter`` (default False): a streaming loudness meter (loudness.py) taps the final float signal -- behind
+        converter, leveller and limiter / gain, ahead of the word-length reduction -- and ``session.loudness_report`` gives the EBU R
+        128 figures of what has been delivered (``loudness_report``'s six keys, the live ``momentary`` and ``short_term``, and
+        ``seconds``) at any time, also after ``finish``; it delays and alters nothing; output rates up to 192 kHz.
         Two more keywords, ``channels`` and ``channel_weights`` (both default None), are taken BY KEYWORD ONLY and handed to
         ``RestoreSession``, whose signature ends with them (any other keyword is a TypeError): the named parameters of this
         method stay the mono session's.
@@ -1290,7 +1294,7 @@ class VoiceFixer(nn.Module):
                 raise TypeError("open_stream() got an unexpected keyword argument %r" % key)
         return RestoreSession(self, chunk_seconds, overlap_seconds, batch_size, mode, your_vocoder_func, sample_rate,
                               output_sample_rate, bit_depth, dither, dither_seed, gain_db, peak_ceiling, true_peak, limiter,
-                              limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate, **programme)
+                              limiter_lookahead_ms, leveller, leveller_max_gain_db, leveller_gate, meter, **programme)
 
     # shortest restorable file: the reflect-padded STFT needs > 1024 samples (mode 1: after the cut to 512 * (n // 512)); mode 2:
     # train-mode BatchNorm needs more than 64 frames (engine.check_train_frames)

@@ -905,3 +905,4 @@ extern "C" int vfx_loudness_limit_f32(const float* x, int64_t x_stride, const in
 
 #include "vfx_limit_span.inc"
 #include "vfx_level_span.inc"
+#include "vfx_meter_span.inc"

@@ -525,3 +525,149 @@ def level_reference_linked(x, fs, target=-16.0, max_gain_db=12.0, gate=-50.0, we
                      gated=int(r["held"].sum()))
     hop = hop_length(fs)
     return np.stack([leveller_apply(x[c], r["a"], hop) for c in range(x.shape[0])])
+
+
+# ---- streaming loudness meter --------------------------------------------------------------------------------
+# ``open_stream(meter=True)``, ``voicefixer_amd.LoudnessMeter``; ``vfx_meter_span_rows_f32``, ``vfx_meter_report_f32``.  What a
+# session delivered, in EBU R 128 terms, without keeping it: per programme x (C, N) at fs <= 192 kHz (a row is the programme of one
+# channel with the weight 1), hop = ``hop_length(fs)``, the meter carries
+#   * the quarter energies E_q, q < N // hop: the leveller's LINKED quarter energies (``leveller_energies_linked``), 8 bytes per
+#     100 ms, from which ``meter_report`` takes every loudness figure by the recipe of the whole-row report (module docstring) --
+#     the 400 ms blocks z_j = (E_j + E_{j+1} + E_{j+2} + E_{j+3}) / (4 hop), both gates, the 3 s blocks from every quarter, the LRA
+#     -- and the two live figures ``momentary`` / ``short_term``: the loudness of the last 4 / 30 complete quarters;
+#   * the sample peak P = max_c max |x_c| and the true peak TP = max(P, max |y|) of DESIGN.md 3.11, exact maxima.
+# The filter of a quarter starts from zero two quarters earlier (the leveller's definition, which makes a quarter a function of
+# 3 hop samples); the whole-row measurement filters the row once.  The two differ by the decayed state only (``transition(fs)^(2
+# hop)`` < 1.4e-16), far below the bounds of DESIGN.md 3.10.
+METER_STATE = 16              # float64 values of the device state (VFX_METER_STATE)
+METER_KEYS = ("integrated", "loudness_range", "max_momentary", "max_short_term", "sample_peak", "true_peak", "momentary",
+              "short_term", "seconds")
+
+
+def check_meter(meter, fs=None):
+    """``meter`` is a bool; ``fs`` (when given) an integer rate in [4000, 192000] -- the meter's quarters are the leveller's."""
+    if not isinstance(meter, (bool, np.bool_)):
+        raise ValueError("meter must be True or False (got %r)" % (meter,))
+    if fs is not None and _check_rate(fs) > LEVELLER_MAX_RATE:
+        raise ValueError("meter: rates above %d Hz are refused -- the two-quarter warm-up of the K-weighting no longer decays "
+                         "below fp32 resolution (got %r)" % (LEVELLER_MAX_RATE, fs))
+    return bool(meter)
+
+
+def meter_reach(fs):
+    """(R, Bk, Fw) of the meter's true peak at ``fs`` Hz: the oversampling and how far the interpolated values that belong to a
+    sample read behind and ahead of it (``limiter_reach`` with true_peak=True: 94 and 93 at R = 4 and at R = 2, 0 and 0 at R = 1)."""
+    R = oversampling(fs)
+    if R == 1:
+        return 1, 0, 0
+    from . import audio_io
+    _, J, c = audio_io.hq_bank(R, 1)
+    return R, J - 1 - c // R, c // R
+
+
+def meter_counts(m, hop):
+    """nq: the quarters in the log once the samples [0, m) are metered: m // hop (never more than the row's N // hop)."""
+    return max(int(m), 0) // int(hop)
+
+
+def meter_ready(n_known, Fw):
+    """How many samples can be metered once ``n_known`` samples of a row of unknown length are known: max(0, n_known - Fw) --
+    the interpolated values of a sample read Fw samples ahead of it."""
+    return max(0, int(n_known) - int(Fw))
+
+
+def meter_keep(m1, hop, Bk):
+    """The first sample that metering from m1 on still reads: max(0, min(m1 - Bk, (m1 // hop - 2) hop)) -- the interpolated values
+    of sample m1 reach Bk behind it, the next quarter's filter starts two quarters before it."""
+    m1, hop = int(m1), int(hop)
+    return max(0, min(m1 - int(Bk), (m1 // hop - LEVELLER_WARMUP) * hop))
+
+
+def _programme(x, what):
+    x = np.asarray(x)
+    if x.ndim == 1:
+        x = x[None]
+    if x.ndim != 2:
+        raise ValueError("%s: a row is (N,), a programme (C, N) (got shape %r)" % (what, x.shape))
+    check_channel_count(int(x.shape[0]))
+    return x
+
+
+def meter_energies(x, fs, weights=None):
+    """The meter's quarter energies E_q, q < N // hop, of a row (N,) or a programme (C, N), float64: the leveller's linked quarter
+    energies (``leveller_energies_linked``; one channel of weight 1: ``leveller_energies``, since 0 + 1 E = E)."""
+    check_meter(True, fs)
+    return leveller_energies_linked(_programme(x, "meter_energies"), fs, weights)
+
+
+def _lufs(z):
+    return -0.691 + 10.0 * math.log10(z) if z > 0.0 else -math.inf
+
+
+def meter_report(E, hop):
+    """The loudness figures of the quarter energies E[0..Q) at quarters of ``hop`` samples, float64, in the order of the device
+    report (vfx_meter_report_f32): dict with ``integrated`` (both gates over the 400 ms blocks; -inf: no block passes),
+    ``loudness_range`` (0.0: no short-term block survives), ``max_momentary`` (all blocks, ungated), ``max_short_term`` (-inf
+    without a block) and the live ``momentary`` / ``short_term`` (the last 4 / 30 quarters; -inf with fewer)."""
+    E = np.asarray(E, dtype=np.float64).reshape(-1)
+    Q, hop = E.shape[0], int(hop)
+    inv4, inv30 = 1.0 / (4.0 * hop), 1.0 / (30.0 * hop)
+    z = np.array([(((E[j] + E[j + 1]) + E[j + 2]) + E[j + 3]) * inv4 for j in range(max(Q - 3, 0))])
+    st = np.zeros(max(Q - 29, 0))
+    for j in range(st.shape[0]):
+        a = 0.0
+        for i in range(30):
+            a += float(E[j + i])
+        st[j] = a * inv30
+    lz = np.array([_lufs(v) for v in z])
+    ls = np.array([_lufs(v) for v in st])
+    L = -math.inf
+    g1 = lz > -70.0
+    if g1.any():
+        gr = _lufs(float(z[g1].sum()) / int(g1.sum())) - 10.0
+        g2 = g1 & (lz > gr)
+        if g2.any():
+            L = _lufs(float(z[g2].sum()) / int(g2.sum()))
+    lra = 0.0
+    g1 = ls > -70.0
+    if g1.any():
+        gr = _lufs(float(st[g1].sum()) / int(g1.sum())) - 20.0
+        s = np.sort(st[g1 & (ls > gr)])
+        n = s.shape[0]
+        if n:
+            lra = _lufs(float(s[((n - 1) * 95 + 50) // 100])) - _lufs(float(s[((n - 1) + 5) // 10]))
+    return {"integrated": L, "loudness_range": lra,
+            "max_momentary": _lufs(float(z.max())) if z.size else -math.inf,
+            "max_short_term": _lufs(float(st.max())) if st.size else -math.inf,
+            "momentary": float(lz[-1]) if z.size else -math.inf, "short_term": float(ls[-1]) if st.size else -math.inf}
+
+
+def meter_reference(x, fs, weights=None, final=True):
+    """The meter on the host, float64: the nine figures (``METER_KEYS``; peaks in dB as in ``loudness_report``) of a row (N,) or
+    a programme (C, N) at ``fs``.  ``final=True``: the row is complete -- ``true_peak`` includes the interpolated values behind
+    the last sample, as the whole-row measurement does.  ``final=False``: the report while the end is unknown, after N samples
+    have been fed: quarters and sample peak cover every complete quarter and every sample, but ``true_peak`` covers only the
+    interpolated values whose taps have all arrived, those that belong to the samples below N - Fw (``meter_reach``): the
+    interpolator is a symmetric filter that reads Fw = 93 samples ahead of a value, and a value computed with zeros in place of
+    samples still to come would be WRONG, not early -- so the mid-stream true peak is Fw samples late (2.1 ms at 44.1 kHz;
+    never below the sample peak, which is not late)."""
+    from scipy.signal import upfirdn
+    from . import audio_io
+    x = _programme(x, "meter_reference").astype(np.float64)
+    C_, N = x.shape
+    hop = hop_length(fs)
+    out = meter_report(meter_energies(x, fs, weights), hop)
+    P = float(np.abs(x).max()) if N else 0.0
+    TP = P
+    R, _, Fw = meter_reach(fs)
+    if R > 1 and N:
+        g = audio_io.hq_filter(R, 1)[1].astype(np.float64)
+        c = (g.shape[0] - 1) // 2
+        # value m in [0, R N) sits at c + m of the full convolution and belongs to sample (c + m) // R - c // R
+        m1 = R * N if final else max(0, min(R * N, R * (N - Fw + c // R) - c))
+        for ch in range(C_):
+            y = upfirdn(g, x[ch], up=R)[c:c + m1]
+            if y.size:
+                TP = max(TP, float(np.abs(y).max()))
+    out.update(sample_peak=to_db(P), true_peak=to_db(TP), seconds=N / float(fs))
+    return {k: out[k] for k in METER_KEYS}

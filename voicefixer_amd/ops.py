@@ -921,6 +921,73 @@ def level_span_rows(xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_
     _level_span_impl("level_span_rows", (C_, ws_, os_), xw, g0, n_total, rate, target, m0, m1, out, state, max_gain_db, gate, weights)
 
 
+def meter_state(device):
+    """A fresh state of the streaming loudness meter for one programme: device float64 (loudness.METER_STATE,) of zeros -- the
+    state of a programme nothing of which has been metered; the first call (m0 = 0) fills it."""
+    from . import loudness
+    return torch.zeros((loudness.METER_STATE,), dtype=torch.float64, device=device)
+
+
+def meter_span_rows(xw, g0, n_total, rate, m0, m1, state, qlog, weights=None, true_peak=True):
+    """Folds the samples [m0, m1) of a programme of C channels into a streaming loudness meter (vfx_meter_span_rows_f32;
+    loudness.py): xw (C, wlen) device -- or (wlen,), one channel -- holds samples [g0, g0 + wlen) of rows of
+    ``n_total`` samples at ``rate`` Hz (None: the end is not known yet, and m1 may not pass loudness.meter_ready(g0 + wlen, Fw)).
+    Calls come in order (m0 = 0 first, then the m1 of the call before) on one ``state`` (``meter_state``) and one ``qlog``, a
+    device float64 tensor of at least m1 // hop values that the caller owns and grows (by doubling) BETWEEN calls: 8 bytes per
+    100 ms of the programme.  Afterwards qlog[:m1 // hop] are the linked quarter energies (``weights``:
+    loudness.channel_weights(C, weights)) and state[:5] = {sample peak, true peak, quarters logged, samples metered, flag}: the
+    bits of one call over the whole row.  The window must cover [m0 - Bk, m1 - 1 + Fw] clipped to the row (loudness.meter_reach)
+    and the regions of the quarters that become complete, or VfxError.  ``true_peak=False``: the sample-peak form (the entry
+    point's R = 1: nothing is interpolated, the samples count for both peaks, Bk = Fw = 0) -- how a report in the middle of a
+    session accounts for the samples whose interpolated values are not known yet.  At most three launches, no synchronisation."""
+    from . import loudness
+    _need_cuda(xw, state, qlog)
+    assert xw.dtype == torch.float32 and xw.dim() in (1, 2) and (xw.shape[-1] <= 1 or xw.stride(-1) == 1)
+    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.METER_STATE and state.stride(0) == 1
+    assert qlog.dtype == torch.float64 and qlog.dim() == 1 and (qlog.numel() <= 1 or qlog.stride(0) == 1)
+    loudness.check_meter(True, rate)
+    Cn = loudness.check_channel_count(int(xw.shape[0])) if xw.dim() == 2 else 1
+    wlen = int(xw.shape[-1])
+    w_stride = int(xw.stride(0)) if Cn > 1 else wlen      # (one row: any stride that holds the row will do)
+    wt = (C.c_double * Cn)(*loudness.channel_weights(Cn, weights))
+    m0, m1 = int(m0), int(m1)
+    p = loudness.leveller_plan(rate)
+    key = (str(xw.device), int(rate))
+    mpow = _LEVELLER_MPOW.get(key)
+    if mpow is None:
+        mpow = torch.from_numpy(p["mpow"]).to(xw.device)
+        _LEVELLER_MPOW[key] = mpow
+    coef = (C.c_double * 10)(*[float(v) for v in p["coef"]])
+    R = loudness.oversampling(rate) if loudness.check_true_peak(true_peak) else 1
+    bank, J, c = true_peak_bank(xw.device, R) if R > 1 else (None, 1, 0)
+    h = _lib.lib()
+    nb = h.vfx_meter_span_workspace_bytes(max(m1 - m0, 0), p["hop"], Cn)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=xw.device)
+    check(h.vfx_meter_span_rows_f32(_ptr(xw), w_stride, Cn, wt, int(g0), wlen, INT64_MAX if n_total is None else int(n_total), m0, m1,
+                                    int(rate), coef, _ptr(mpow), p["S"], _ptr(bank), J, R, c, _ptr(state), _ptr(qlog),
+                                    int(qlog.numel()), _ptr(ws), nb, _stream()), "vfx_meter_span_rows_f32")
+
+
+def meter_report(state, qlog, rate):
+    """The EBU R 128 figures of a streaming loudness meter (vfx_meter_report_f32): a device float64 (10,) of
+    {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample peak, true peak (both linear),
+    momentary and short-term loudness of the last 4 / 30 quarters, quarters, flag} from ``state`` and ``qlog`` as
+    ``meter_span_rows`` left them.  Writes neither: a report in the middle of a session changes nothing that follows.  One
+    launch, no synchronisation (the caller's read of the result is the one)."""
+    from . import loudness
+    _need_cuda(state, qlog)
+    assert state.dtype == torch.float64 and state.dim() == 1 and state.numel() >= loudness.METER_STATE and state.stride(0) == 1
+    assert qlog.dtype == torch.float64 and qlog.dim() == 1 and (qlog.numel() <= 1 or qlog.stride(0) == 1)
+    loudness.check_meter(True, rate)
+    h = _lib.lib()
+    nb = h.vfx_meter_report_workspace_bytes(int(qlog.numel()))
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=state.device)
+    rep = torch.empty((10,), dtype=torch.float64, device=state.device)
+    check(h.vfx_meter_report_f32(_ptr(state), _ptr(qlog), loudness.hop_length(rate), _ptr(rep), _ptr(ws), nb, _stream()),
+          "vfx_meter_report_f32")
+    return rep
+
+
 def loudness_report_groups(x, n_rows, groups, fs, weights=None):
     """Loudness report of programmes of several channels (vfx_loudness_report_groups_f32; arguments as loudness_groups): a
     device float64 (G, 6) of {integrated loudness, loudness range, maximum momentary, maximum short-term loudness, sample

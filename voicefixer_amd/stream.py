@@ -1,6 +1,6 @@
 """The overlap-add streaming mode: the chunk plan (``plan_stream_chunks``, ``StreamPlanner``), the stages that work on a row
-that arrives in pieces (``_SpanStage`` and its three subclasses) and the push-style session that chains them
-(``RestoreSession``).  ``api`` imports this module and re-exports its names; what this module needs of ``api``
+that arrives in pieces (``_SpanStage``, its three subclasses and the meter that taps them) and the push-style session that chains them
+(``RestoreSession``; ``LoudnessMeter``, the meter on its own).  ``api`` imports this module and re-exports its names; what this module needs of ``api``
 it imports inside the functions that need it."""
 import numpy as np
 import torch
@@ -272,6 +272,97 @@ class _SpanLeveller(_SpanStage):
         return {"min_gain_db": float(v[0]), "max_gain_db": float(v[1]), "anchors": int(v[2]), "gated": int(v[3])}
 
 
+class _SpanMeter(_SpanStage):
+    """The streaming loudness meter (loudness.py; ops.meter_span_rows / ops.meter_report) on ``_SpanStage``'s
+    window bookkeeping.  A TAP, not a stage: ``feed`` and ``finish`` return nothing, and what is fed goes on to whoever delivers
+    it, neither delayed nor altered.  A session feeds it its final FLOAT signal: behind the output converter, the leveller and
+    the limiter (or the fixed gain), ahead of the word-length reduction.  It meters what it can -- up to loudness.meter_ready: the
+    interpolated values of a sample read Fw samples ahead -- and keeps the rest in its own window, which starts at
+    loudness.meter_keep: Bk samples behind the first sample not yet metered or, if that is earlier, two quarters before the next
+    quarter to be measured; fewer than 3 quarters, 0.3 s, beyond a block.  Kept as well: the device state (16 float64) and the
+    log of the quarter energies, 8 bytes per 100 ms per programme (288 KB per hour), grown by doubling between calls -- the one
+    thing of a session that grows with its length.  A programme (C, k) is metered with ``weights`` (loudness.channel_weights)."""
+
+    QLOG0 = 1024             # quarters of the first log (102 s)
+
+    def __init__(self, rate, weights=None, span=None):
+        from . import loudness
+        super().__init__(LEVEL_SPAN if span is None else int(span))
+        loudness.check_meter(True, rate)
+        self.rate, self.hop = int(rate), loudness.hop_length(rate)
+        self.R, self.Bk, self.Fw = loudness.meter_reach(rate)
+        self.weights = weights
+        self.state = None    # device float64 (loudness.METER_STATE,)
+        self.qlog = None     # device float64 (capacity,)
+        self.final = False   # the end has been metered
+
+    def _ready(self, n):
+        from . import loudness
+        return loudness.meter_ready(n, self.Fw)
+
+    def _keep(self, m1):
+        from . import loudness
+        return loudness.meter_keep(m1, self.hop, self.Bk)
+
+    def _room(self, quarters, device):
+        """State and log on ``device``, the log with room for ``quarters``."""
+        from . import ops
+        if self.state is None:
+            self.state = ops.meter_state(device)
+            self.qlog = torch.zeros((self.QLOG0,), dtype=torch.float64, device=device)
+        if quarters > self.qlog.numel():
+            grown = torch.zeros((max(quarters, 2 * self.qlog.numel()),), dtype=torch.float64, device=device)
+            grown[:self.qlog.numel()] = self.qlog
+            self.qlog = grown
+
+    def _run(self, a, b, n_total, y=None):
+        from . import ops
+        self._room(b // self.hop, self.win.device)
+        ops.meter_span_rows(self.win, self.g0, n_total, self.rate, a, b, self.state, self.qlog, self.weights)
+
+    def _emit(self, m1, n_total):
+        m0, m1 = self.m_done, max(m1, self.m_done)
+        for a in range(m0, m1, self.span):                # (nothing to meter: no call)
+            self._run(a, min(a + self.span, m1), n_total)
+        self.m_done = m1
+        self.final = n_total is not None
+        keep = min(self._keep(m1), self.n_in - 1)
+        if keep > self.g0:
+            self.win = self.win[..., keep - self.g0:].clone()
+            self.g0 = keep
+
+    def finish(self, device=None):
+        if self.win is not None:
+            self._emit(self.n_in, self.n_in)
+        self.final = True
+
+    def report(self):
+        """The dict of loudness.METER_KEYS over what has been fed (reads the device report: the one synchronisation).  Before
+        ``finish``: the figures of loudness.meter_reference(..., final=False) -- the samples fed but not yet metered (fewer than
+        Fw) and the quarter they may complete are folded into a COPY of the state by the sample-peak form of the span call
+        (they count for the sample peak and for their quarter; their interpolated values are not known yet); the quarter is
+        written where the next call writes the same bits.  After it: the final figures.  VfxError if the spans did not come in order."""
+        from . import loudness, ops
+        out = {"integrated": -np.inf, "loudness_range": 0.0, "max_momentary": -np.inf, "max_short_term": -np.inf,
+               "sample_peak": -np.inf, "true_peak": -np.inf, "momentary": -np.inf, "short_term": -np.inf,
+               "seconds": self.n_in / float(self.rate)}
+        if self.win is None and self.state is None:       # (nothing has been fed, or it was dropped before anything was metered)
+            return out
+        state = self.state
+        if not self.final and self.win is not None and self.n_in > self.m_done:
+            self._room(self.n_in // self.hop, self.win.device)
+            state = self.state.clone()
+            ops.meter_span_rows(self.win, self.g0, None, self.rate, self.m_done, self.n_in, state, self.qlog, self.weights,
+                                true_peak=False)
+        v = ops.meter_report(state, self.qlog, self.rate).cpu().numpy()
+        if v[9] != 0.0:
+            raise VfxError("meter: the spans of a row did not come in order" if v[9] == 1.0 else
+                           "meter: the state does not belong to this log")
+        out.update(integrated=float(v[0]), loudness_range=float(v[1]), max_momentary=float(v[2]), max_short_term=float(v[3]),
+                   sample_peak=loudness.to_db(v[4]), true_peak=loudness.to_db(v[5]), momentary=float(v[6]), short_term=float(v[7]))
+        return out
+
+
 class RestoreSession:
     """``VoiceFixer.open_stream``: the overlap-add long-form mode as a push-style session on the device.
 
@@ -312,7 +403,12 @@ class RestoreSession:
     ops.limit_span_rows: one envelope, the maximum over the channels): one gain curve per programme, so the balance between the
     channels stays -- ``level(Z, ..., channels="all")`` and ``limit(..., channels="all")`` of the plain (C, N) output Z, bit for bit,
     with one stats record per programme; the fixed gain alone is float32(gL) y; ``bit_depth`` gives ``quantize`` of the (C, N)
-    array (channel c draws the dither of channel c).  Every channel is within 2e-5 rms of the mono session on it, not its bits: the
+    array (channel c draws the dither of channel c).  ``meter=True``: a loudness meter taps the session's final
+    float signal -- behind the output converter, the leveller and the limiter or the gain, ahead of the word-length reduction -- and
+    ``loudness_report`` says what was delivered (integrated, momentary, short-term, LRA, sample and true peak), at any time; it
+    neither delays nor alters a sample, and holds 8 bytes per 100 ms of the programme (288 KB per hour), the one thing here that grows
+    with the session's length, and less than 0.3 s of samples.  With channels="all" the channels weigh ``channel_weights``; "mix" /
+    "first" / None meter the mono signal.  Every channel is within 2e-5 rms of the mono session on it, not its bits: the
     path's bits depend on the batch's composition.  "mix" / "first": a (C, k) block is averaged (float32 mean) / cut to channel 0
     on the host and the session is the mono one.  Held: O(C (chunk + the largest block)).
     Every argument is checked in the constructor, before the device is touched.
@@ -321,7 +417,7 @@ class RestoreSession:
     def __init__(self, vf, chunk_seconds=30.0, overlap_seconds=1.0, batch_size=1, mode=0, your_vocoder_func=None,
                  sample_rate=44100, output_sample_rate=None, bit_depth=None, dither="tpdf", dither_seed=0, gain_db=None,
                  peak_ceiling=-1.0, true_peak=False, limiter=False, limiter_lookahead_ms=3.0, leveller=None,
-                 leveller_max_gain_db=12.0, leveller_gate=-50.0, channels=None, channel_weights=None):
+                 leveller_max_gain_db=12.0, leveller_gate=-50.0, meter=False, channels=None, channel_weights=None):
         from . import loudness as ld
         from .api import _Output, _check_rate, _output_rate
         _check_stream_mode(mode, "open_stream")
@@ -363,6 +459,8 @@ class RestoreSession:
         self._conv_in = _SpanConverter(self._rate_in, 44100) if self._rate_in != 44100 else None
         conv_out = _SpanConverter(44100, self._rate_out) if self._rate_out != 44100 else None
         self._stages = [s for s in (conv_out, self._lev, self._lim) if s is not None]      # behind the stitcher, in this order
+        # (check_meter: ValueError for an output rate above 192 kHz; a tap on what _deliver is about to hand over)
+        self._meter = _SpanMeter(self._rate_out, channel_weights) if ld.check_meter(meter) else None
         self._n_in = 0           # samples pushed
         self._buf = None         # device (k,) -- (C, k) with channels="all", here and below: 44.1 kHz samples [b0, b0 + k)
         self._b0 = 0
@@ -382,8 +480,8 @@ class RestoreSession:
         """Drop what is pending (nothing more is delivered); ``push`` and ``finish`` raise afterwards."""
         self._closed = True
         self._buf = self._tail = self._fade = self._conv_in = None
-        for stage in self._stages:
-            stage.release()          # (the records stay: limiter_stats and leveller_stats outlive the session)
+        for stage in self._stages + ([self._meter] if self._meter is not None else []):
+            stage.release()          # (the records stay: limiter_stats, leveller_stats and loudness_report outlive the session)
 
     @property
     def limiter_stats(self):
@@ -396,6 +494,16 @@ class RestoreSession:
         """{"min_gain_db", "max_gain_db", "anchors", "gated"} of the leveller over what has been delivered -- exact folds, the
         values of ``level`` over the whole output -- or None without a leveller."""
         return None if self._lev is None else self._lev.stats()
+
+    @property
+    def loudness_report(self):
+        """What the session has delivered, in EBU R 128 terms (``meter=True``; None without a meter): the dict of
+        ``voicefixer_amd.loudness_report`` -- ``integrated``, ``loudness_range``, ``max_momentary``, ``max_short_term``,
+        ``sample_peak``, ``true_peak`` -- plus the live ``momentary`` and ``short_term`` (the last 400 ms / 3 s) and ``seconds``,
+        over the FLOAT signal ahead of the word-length reduction.  Readable at any time (one synchronisation): before ``finish``
+        the figures of loudness.meter_reference(..., final=False) -- the true peak is 93 samples late --, after it the final ones;
+        still readable after ``close``.  VfxError if the meter's spans did not come in order."""
+        return None if self._meter is None else self._meter.report()
 
     @torch.no_grad()
     def push(self, block):
@@ -508,8 +616,15 @@ class RestoreSession:
         if self._gain is not None and self._lim is None:
             stretches = [y * self._gain for y in stretches]      # (float32(gL) y: one rounding per sample)
         if not stretches:
+            if at_end and self._meter is not None:
+                self._meter.finish()
             return np.zeros((self._C or 1, 0), self._dtype)
         y = stretches[0] if len(stretches) == 1 else torch.cat(stretches, dim=-1)
+        if self._meter is not None:                          # (a tap: y goes on as it is)
+            if y.shape[-1] > 0:
+                self._meter.feed(y)
+            if at_end:
+                self._meter.finish()
         if self._C is None:
             y = y[None]
         if self._word.bit_depth is not None and y.shape[1] > 0:     # (a row's channel is its index: quantize of the (C, N) array)
@@ -518,3 +633,75 @@ class RestoreSession:
         y = y.cpu().numpy().astype(self._dtype, copy=False)
         self.position += y.shape[1]
         return y
+
+
+class LoudnessMeter:
+    """The streaming loudness meter of a session (``open_stream(meter=True)``; loudness.py) for any audio, with no
+    VoiceFixer: EBU R 128 figures of a signal that arrives in blocks, on the device, without keeping it.
+
+        m = LoudnessMeter(sample_rate=48000)
+        m.push(block)            # float32 (k,), any k >= 0
+        m.report()               # the dict below over what has been pushed, at any time; the true peak is 93 samples late
+        m.finish()               # the final dict; afterwards push raises RuntimeError, report keeps answering
+
+    The dict: ``integrated`` (LUFS), ``loudness_range`` (LU), ``max_momentary``, ``max_short_term`` (LUFS), ``sample_peak`` (dBFS),
+    ``true_peak`` (dBTP) -- the keys and, within the bounds of DESIGN.md 3.10 / 3.11, the values of ``loudness_report`` on the
+    concatenation, the true peak bit for bit -- plus ``momentary`` and ``short_term`` (the last 400 ms / 3 s; -inf with less) and
+    ``seconds``.  The figures do not depend on the block sizes, in any bit.  ``channels``: None -- blocks are (k,) -- or "all":
+    blocks are (C, k), C in 1..8 fixed by the first block, ONE programme weighted by ``channel_weights`` (default
+    loudness.channel_weights(C), BS.1770-4 Table 4; needs channels="all"); "mix" / "first": a (C, k) block is averaged / cut to
+    channel 0 on the host, as a session does, and metered as one channel.  ``sample_rate``: 4 kHz to 192 kHz (ValueError).  Held:
+    less than 0.3 s of samples beyond a block and 8 bytes per 100 ms pushed.  Every argument is checked in the constructor, before
+    the device is touched.  A context manager."""
+
+    def __init__(self, sample_rate=44100, channels=None, channel_weights=None):
+        from . import loudness as ld
+        ld.check_meter(True, sample_rate)
+        self._channels = ld.check_channels(channels)
+        if channel_weights is not None:
+            if self._channels != "all":
+                raise ValueError('LoudnessMeter: channel_weights weigh the channels of a programme and need channels="all"')
+            if isinstance(channel_weights, (str, bytes)) or not isinstance(channel_weights, (list, tuple, np.ndarray)) \
+                    or not 1 <= len(channel_weights) <= ld.MAX_CHANNELS:
+                raise ValueError("channel_weights must be a list of 1..8 numbers >= 0, one per channel (got %r)" % (channel_weights,))
+            channel_weights = ld.channel_weights(len(channel_weights), channel_weights)
+        self._weights = channel_weights
+        self._C = None
+        self._tap = _SpanMeter(int(sample_rate), channel_weights)
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        """Drop the samples held; ``push`` and ``finish`` raise afterwards, ``report`` keeps answering."""
+        self._closed = True
+        self._tap.release()
+
+    @torch.no_grad()
+    def push(self, block):
+        """Meter the next ``block``: float32 (k,), k >= 0 -- (C, k) with channels="all"; returns nothing."""
+        if self._closed:
+            raise RuntimeError("LoudnessMeter: push after finish / close")
+        from .api import _device
+        block = RestoreSession._as_block(self, np.asarray(block, dtype=np.float32))
+        if block.shape[-1]:
+            self._tap.feed(torch.from_numpy(np.ascontiguousarray(block)).to(_device()))
+
+    def report(self):
+        """The dict over what has been pushed so far (one synchronisation); before ``finish`` the true peak covers the samples
+        whose interpolated values are complete (loudness.meter_reference(..., final=False))."""
+        return self._tap.report()
+
+    @torch.no_grad()
+    def finish(self):
+        """The final dict: the end of the signal is known; the meter is closed afterwards."""
+        if self._closed:
+            raise RuntimeError("LoudnessMeter: finish called twice (or after close)")
+        self._tap.finish()
+        self.close()
+        return self._tap.report()
