@@ -151,7 +151,8 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(const double* __restric
 }
 
 // grid (ceil(L / 1024), C, B): four consecutive elements per thread (a float4 when both tensors allow it).  Map form:
-// positions below the row's extent in column P - 1 are written 0; positions at or past the extent are not touched.
+// positions below the row's extent in column P - 1 are written 0; positions at or past the extent are not touched: the
+// float4 instance may LOAD the whole last vector of a row (a span is padded to 4) but stores only what lies below the extent.
 template <bool VEC>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, long long x_bs, long long x_cs,
                                                        float* __restrict__ y, long long y_bs, long long y_cs,
@@ -182,9 +183,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         if (pmask != 0 && ((l0 + i) & pmask) == pmask) r = 0.f;
         e[i] = r;
     }
-    if (VEC) {
+    if (VEC && l0 + 4 <= valid) {
         *reinterpret_cast<float4*>(yp) = make_float4(e[0], e[1], e[2], e[3]);
-    } else {
+    } else {      // the scalar instance, and the last vector of a row whose extent is no multiple of 4
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (l0 + i < valid) yp[i] = e[i];
