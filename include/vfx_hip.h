@@ -61,7 +61,10 @@ typedef struct {
 #define VFX_PRE_NONE 0
 #define VFX_PRE_LRELU 1         /* leaky_relu(x, pre_slope) */
 #define VFX_PRE_AFFINE_LRELU 2  /* leaky_relu(x*pre_scale[c] + pre_shift[c], pre_slope): eval BatchNorm + (leaky)ReLU */
-/* post-activation applied in the epilogue, after bias and residual */
+/* post-activation applied in the epilogue, after bias and residual.  The kernels behind vfx_conv1d_f32, vfx_convtr1d_f32,
+ * vfx_conv2d_f32 and vfx_convtr2d_3x3s2_f32 start their accumulators at ZERO (both arithmetics): bias, then residual, are added to
+ * the finished sum of products, in the order torch adds them, so no partial sum rounds at their magnitude.  (The fused direct
+ * ResStack layer of vfx_resblock_f32 without w1_wino4 still starts its halves at b1 and at b2 + x.) */
 #define VFX_POST_NONE 0
 #define VFX_POST_LRELU 1        /* leaky_relu(., post_slope) */
 #define VFX_POST_ELU 2
@@ -73,7 +76,8 @@ typedef struct {
 #define VFX_MATH_F32 0     /* v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation (default) */
 #define VFX_MATH_BF16X3 1  /* opt-in: every fp32 operand split into two bf16 terms, x*w evaluated as
                               xh*wh + xh*wl + xl*wh on v_mfma_f32_32x32x16_bf16 with fp32 accumulation
-                              (relative product error <= 2^-16); needs w_x3 and an input guard band
+                              (relative product error <= 2^-15 (1 + 2^-19) in the worst case, ~2^-17 observed; bias and
+                              residual are added to the finished sum); needs w_x3 and an input guard band
                               (vfx_tensor.guard >= largest tap offset + tile width), falls back to fp32
                               per launch for geometries the bf16x3 kernel does not cover (Cin % 32,
                               reflect padding, more than 3 taps other than 3x3, mixed tap counts) */

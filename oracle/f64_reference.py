@@ -217,6 +217,55 @@ def post_lipschitz(post):
     return 2.0 if post == POST_LRELU_SNAKE else 1.0
 
 
+def conv_pre32(x, pre=PRE_NONE, slope=0.0, scale=None, shift=None):
+    """The pre-activated input x~ in float32 as conv_x3_kernel's staging code forms it: the affine part one fused
+    multiply-add (fmaf(x, scale, shift): the exact product plus the shift in float64, rounded to float32 -- a double rounding
+    that differs from the fused operation only on a tie of the float64 sum), then v > 0 ? v : v * slope with the slope as
+    float32."""
+    x = x.to(torch.float32)
+    if pre == PRE_AFFINE_LRELU:
+        shp = [1, -1] + [1] * (x.dim() - 2)
+        x = (x.double() * scale.to(torch.float32).double().reshape(shp) + shift.to(torch.float32).double().reshape(shp)).float()
+    if pre in (PRE_LRELU, PRE_AFFINE_LRELU):
+        x = torch.where(x > 0, x, x * torch.tensor(float(slope), dtype=torch.float32))
+    return x
+
+
+def split_bf16(v):
+    """v (float32) -> (hi, lo) float32 with hi = bf16(v), lo = bf16(v - hi), both round-to-nearest-even: the two planes of
+    VFX_MATH_BF16X3 (packing.pack_x3 writes the same planes of the weights; v - hi is exact in float32)."""
+    v = v.to(torch.float32)
+    hi = v.to(torch.bfloat16).to(torch.float32)
+    lo = (v - hi).to(torch.bfloat16).to(torch.float32)
+    return hi, lo
+
+
+def _terms(x, w, pre, pre_slope, scale, shift, magnitude, split):
+    """The (input, weight) float64 pairs whose convolutions add up to the bare sum.  split=None: one pair, pre(x) and w.
+    split="bf16x3" (the stated arithmetic of conv_x3_kernel, include/vfx_hip.h VFX_MATH_BF16X3): x~ = conv_pre32(x) and w
+    are split into bf16 planes and the sum is  xh wh + xh wl + xl wh  =  conv(xh, wh + wl) + conv(xl, wh),  every product and
+    the sum exact to float64.  The reference, not a model of the kernel: no tile, chunk or staging order appears.
+    magnitude: one pair (|x~|, |w|) either way."""
+    assert split in (None, "bf16x3")
+    if split is None:
+        xa, w64 = conv_pre(x, pre, pre_slope, scale, shift), w.to(torch.float64)
+        return [(xa.abs(), w64.abs())] if magnitude else [(xa, w64)]
+    xt = conv_pre32(x, pre, pre_slope, scale, shift)
+    if magnitude:
+        return [(xt.double().abs(), w.to(torch.float32).double().abs())]
+    (xh, xl), (wh, wl) = split_bf16(xt), split_bf16(w)
+    return [(xh.double(), wh.double() + wl.double()), (xl.double(), wh.double())]
+
+
+def bf16x3_tripled(x, w, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, cin_dim=1):
+    """The yardstick problem of the bf16x3 device bound: (cat[xh, xh, xl], cat[wh, wl, wh]) along the input channels, float32
+    (x~ already activated: run the operator without pre-activation).  Every product of two bf16 values is exact in fp32, so
+    torch's fp32 CPU operator on this pair scores fp32 accumulation of the same 3 K-term sum the statement adds exactly.
+    cin_dim: the weight's input-channel dimension (1 for Conv weights, 0 for ConvTranspose weights)."""
+    (xh, xl), (wh, wl) = split_bf16(conv_pre32(x, pre, pre_slope, scale, shift)), split_bf16(w)
+    return torch.cat([xh, xh, xl], dim=1), torch.cat([wh, wl, wh], dim=cin_dim)
+
+
 def _finish(acc, bias, res, post, post_slope, magnitude):
     """acc (B, Cout, ...) + bias + res -> post(...); or the magnitude |acc| + |bias| + |res| (acc then already is
     sum |x~| |w|)."""
@@ -247,78 +296,69 @@ def _by_rows(fn, x, res, lengths, out_len):
 
 
 def conv1d(x, w, bias=None, res=None, dilation=1, reflect=False, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None,
-           post=POST_NONE, post_slope=0.0, lengths=None, magnitude=False):
+           post=POST_NONE, post_slope=0.0, lengths=None, magnitude=False, split=None):
     """vfx_conv1d_f32: y[b,n,l] = post(bias[n] + res[b,n,l] + sum_{c,t} w[n,c,t] pre(x)[b,c,l + (t - (k-1)/2) dilation]),
     the pre-activated input padded with zeros, or mirrored about its first and last sample (ReflectionPad1d).
-    x (B, Cin, L), w (Cout, Cin, k) with k odd -> (B, Cout, L) float64."""
+    x (B, Cin, L), w (Cout, Cin, k) with k odd -> (B, Cout, L) float64.  `split`: see _terms."""
     if lengths is not None:
         return _by_rows(lambda xb, rb: conv1d(xb, w, bias, rb, dilation, reflect, pre, pre_slope, scale, shift, post,
-                                              post_slope, None, magnitude), x, res, lengths, lambda n: n)
+                                              post_slope, None, magnitude, split), x, res, lengths, lambda n: n)
     k = w.shape[2]
     assert k % 2 == 1
     L, p = x.shape[2], (k - 1) // 2 * dilation
-    xa = conv_pre(x, pre, pre_slope, scale, shift)
-    w64 = w.to(torch.float64)
-    if magnitude:
-        xa, w64 = xa.abs(), w64.abs()
-    if reflect:
-        assert p < L
-        idx = torch.arange(-p, L + p).abs()
-        idx = torch.where(idx > L - 1, 2 * (L - 1) - idx, idx)
-        xp = xa[:, :, idx]
-    else:
-        xp = torch.zeros((x.shape[0], x.shape[1], L + 2 * p), dtype=torch.float64)
-        xp[:, :, p:p + L] = xa
     acc = torch.zeros((x.shape[0], w.shape[0], L), dtype=torch.float64)
-    for t in range(k):
-        acc += torch.matmul(w64[:, :, t], xp[:, :, t * dilation:t * dilation + L])
+    for xa, w64 in _terms(x, w, pre, pre_slope, scale, shift, magnitude, split):
+        if reflect:
+            assert p < L
+            idx = torch.arange(-p, L + p).abs()
+            idx = torch.where(idx > L - 1, 2 * (L - 1) - idx, idx)
+            xp = xa[:, :, idx]
+        else:
+            xp = torch.zeros((x.shape[0], x.shape[1], L + 2 * p), dtype=torch.float64)
+            xp[:, :, p:p + L] = xa
+        for t in range(k):
+            acc += torch.matmul(w64[:, :, t], xp[:, :, t * dilation:t * dilation + L])
     return _finish(acc, bias, res, post, post_slope, magnitude)
 
 
 def convtr1d(x, w, bias=None, stride=2, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE,
-             post_slope=0.0, lengths=None, magnitude=False):
+             post_slope=0.0, lengths=None, magnitude=False, split=None):
     """vfx_convtr1d_f32 = ConvTranspose1d(Cin, Cout, kernel 2s, stride s, padding s // 2 + s % 2, output_padding s % 2):
     input sample i adds w[c,n,t] x[b,c,i] to position i s + t - padding; positions outside [0, s Lin) are dropped.
     x (B, Cin, Lin), w (Cin, Cout, 2s) -> (B, Cout, s Lin) float64."""
     if lengths is not None:
         return _by_rows(lambda xb, rb: convtr1d(xb, w, bias, stride, pre, pre_slope, scale, shift, post, post_slope,
-                                                None, magnitude), x, None, lengths, lambda n: n * stride)
+                                                None, magnitude, split), x, None, lengths, lambda n: n * stride)
     s = stride
     assert w.shape[2] == 2 * s
     Lin, pad = x.shape[2], s // 2 + s % 2
-    xa = conv_pre(x, pre, pre_slope, scale, shift)
-    w64 = w.to(torch.float64)
-    if magnitude:
-        xa, w64 = xa.abs(), w64.abs()
     full = torch.zeros((x.shape[0], w.shape[1], (Lin + 1) * s), dtype=torch.float64)   # positions i s + t, t < 2s
-    for t in range(2 * s):
-        full[:, :, t:t + Lin * s:s] += torch.matmul(w64[:, :, t].t(), xa)
+    for xa, w64 in _terms(x, w, pre, pre_slope, scale, shift, magnitude, split):
+        for t in range(2 * s):
+            full[:, :, t:t + Lin * s:s] += torch.matmul(w64[:, :, t].t(), xa)
     return _finish(full[:, :, pad:pad + s * Lin].clone(), bias, None, post, post_slope, magnitude)
 
 
 def conv2d(x, w, bias=None, res=None, pre=PRE_NONE, pre_slope=0.0, scale=None, shift=None, post=POST_NONE,
-           post_slope=0.0, lengths=None, magnitude=False):
+           post_slope=0.0, lengths=None, magnitude=False, split=None):
     """vfx_conv2d_f32 on dense maps: Conv2d(k x k, k = 1 or 3, stride 1, padding k // 2) of the pre-activated input,
     zero padding on all four sides (on the device the pad column of the pitch map IS the left / right padding, and
     the output's pad column is written as zero: see to_pitch).  x (B, Cin, H, W), w (Cout, Cin, k, k) -> (B, Cout, H, W)
     float64.  `lengths`: map rows per batch item."""
     if lengths is not None:
         return _by_rows(lambda xb, rb: conv2d(xb, w, bias, rb, pre, pre_slope, scale, shift, post, post_slope, None,
-                                              magnitude), x, res, lengths, lambda n: n)
+                                              magnitude, split), x, res, lengths, lambda n: n)
     k = w.shape[2]
     assert k in (1, 3) and w.shape[3] == k
     B, _, Hh, W = x.shape
     p = k // 2
-    xa = conv_pre(x, pre, pre_slope, scale, shift)
-    w64 = w.to(torch.float64)
-    if magnitude:
-        xa, w64 = xa.abs(), w64.abs()
-    xp = torch.zeros((B, x.shape[1], Hh + 2 * p, W + 2 * p), dtype=torch.float64)
-    xp[:, :, p:p + Hh, p:p + W] = xa
     acc = torch.zeros((B, w.shape[0], Hh, W), dtype=torch.float64)
-    for ky in range(k):
-        for kx in range(k):
-            acc += torch.einsum("nc,bchw->bnhw", w64[:, :, ky, kx], xp[:, :, ky:ky + Hh, kx:kx + W])
+    for xa, w64 in _terms(x, w, pre, pre_slope, scale, shift, magnitude, split):
+        xp = torch.zeros((B, x.shape[1], Hh + 2 * p, W + 2 * p), dtype=torch.float64)
+        xp[:, :, p:p + Hh, p:p + W] = xa
+        for ky in range(k):
+            for kx in range(k):
+                acc += torch.einsum("nc,bchw->bnhw", w64[:, :, ky, kx], xp[:, :, ky:ky + Hh, kx:kx + W])
     return _finish(acc, bias, res, post, post_slope, magnitude)
 
 

@@ -511,3 +511,125 @@ def test_f43_weights_1d_are_the_packed_ones():
     for grp in range(C // 8):
         un[:, :, grp * 8 + lane_ci] = blob[:, grp]
     assert torch.equal(un, U)
+
+
+# --------------------------------------------------------------------------------------
+# the bf16x3 statement (split="bf16x3": the reference of tests/test_conv_x3_gpu.py)
+# --------------------------------------------------------------------------------------
+# Round-to-nearest-even to bf16's 8 significant bits: for 2^e <= |v| < 2^(e+1) the spacing is 2^(e-7), so r = v - hi (exact in
+# float32) has |r| <= 2^(e-8) <= 2^-8 |v|; lo = bf16(r) is rounded at r's own spacing, at most 2^(e-16), so
+# |v - hi - lo| <= 2^(e-17) <= 2^-17 |v| (the kernel header's split residual; |r| = 2^(e-8) itself is representable).
+# With x~ = xh + xl + ex and w = wh + wl + ew:  x~ w - (xh wh + xh wl + xl wh) = xl wl + ex w + (xh + xl) ew, and
+# |xl wl| <= 2^-16 |x~ w|,  |ex w| <= 2^-17 |x~ w|,  |(x~ - ex) ew| <= (1 + 2^-17) 2^-17 |x~ w|:
+X3_SPLIT = 2.0 ** -17
+X3_C = 2.0 ** -16 + 2.0 ** -17 + (1.0 + 2.0 ** -17) * 2.0 ** -17             # = 2^-15 (1 + 2^-19) per product
+# the plain float64 statement pre-activates in float64, the split one in float32 (conv_pre32): one rounding of the slope and
+# one of the product (2^-23 of |x~|); the affine part adds one more rounding of a sum whose terms can cancel, so the affine
+# case is pinned on the float32 x~ itself
+X3_PRE = 2.0 ** -23
+
+X3_SHAPES = [  # op, Cin, Cout, extent, k / stride, dilation / pitch log2, pre, heavy
+    ("conv1d", 32, 64, 300, 3, 1, ref64.PRE_LRELU, False), ("conv1d", 512, 32, 200, 3, 27, ref64.PRE_LRELU, True),
+    ("conv1d", 96, 32, 64, 1, 1, ref64.PRE_NONE, True), ("convtr1d", 128, 64, 50, 7, 0, ref64.PRE_NONE, False),
+    ("convtr1d", 64, 32, 40, 2, 0, ref64.PRE_LRELU, True), ("conv2d", 64, 32, 5, 3, 3, ref64.PRE_AFFINE_LRELU, False),
+    ("conv2d", 160, 32, 3, 1, 2, ref64.PRE_NONE, True),
+]
+X3_IDS = ["%s-c%d-k%d-%d-pre%d%s" % (s[0], s[1], s[4], s[5], s[6], "-heavy" if s[7] else "") for s in X3_SHAPES]
+
+
+def _x3_operands(shape, seed):
+    op, cin, cout, ext, k, dl, pre, heavy = shape
+    B = 2
+    if op == "conv1d":
+        x, w = _rand((B, cin, ext), seed), _rand((cout, cin, k), seed + 1, (cin * k) ** -0.5)
+    elif op == "convtr1d":
+        x, w = _rand((B, cin, ext), seed), _rand((cin, cout, 2 * k), seed + 1, (2 * cin) ** -0.5)
+    else:
+        x, w = _rand((B, cin, ext, (1 << dl) - 1), seed), _rand((cout, cin, k, k), seed + 1, (cin * k * k) ** -0.5)
+    if heavy:
+        gain = torch.exp(1.5 * _rand((cout,), seed + 2) - 2.25)
+        w = w * gain.reshape([-1 if d == (1 if op == "convtr1d" else 0) else 1 for d in range(w.dim())])
+    bias = _rand((cout,), seed + 3, 1.0 if heavy else 0.3)
+    kw = dict(pre=pre, pre_slope=0.01)
+    if pre == ref64.PRE_AFFINE_LRELU:
+        kw.update(scale=0.8 + 0.4 * torch.rand(cin, generator=torch.Generator().manual_seed(seed + 4)), shift=_rand((cin,), seed + 5, 0.3))
+    return x, w, bias, kw
+
+
+def _x3_call(shape, x, w, bias, kw, **more):
+    op, k, dl = shape[0], shape[4], shape[5]
+    if op == "conv1d":
+        return ref64.conv1d(x, w, bias, None, dl, **kw, **more)
+    if op == "convtr1d":
+        return ref64.convtr1d(x, w, bias, k, **kw, **more)
+    return ref64.conv2d(x, w, bias, None, **kw, **more)
+
+
+def _x3_torch(shape, x, w, bias):
+    op, k, dl = shape[0], shape[4], shape[5]
+    if op == "conv1d":
+        return F.conv1d(x, w, bias, dilation=dl, padding=(k - 1) // 2 * dl)
+    if op == "convtr1d":
+        return F.conv_transpose1d(x, w, bias, stride=k, padding=k // 2 + k % 2, output_padding=k % 2)
+    return F.conv2d(x, w, bias, padding=k // 2)
+
+
+def test_split_bf16_planes_are_the_packed_ones():
+    """(a) hi / lo of the split helper are bit-equal to the planes packing.pack_x3 writes ([slab][Cin / 16][plane][k-half][Cout][8]),
+    and the split residual is within the derived 2^-17 |v|."""
+    from voicefixer_amd import packing
+    cout, cin, k = 32, 48, 3
+    w = _rand((cout, cin, k), 51, 0.1) * torch.exp(3.0 * _rand((cout, 1, 1), 52))
+    hi, lo = ref64.split_bf16(w)
+    blob = packing.pack_x3(packing.pack_conv1d(w))
+    assert blob.dtype == torch.bfloat16 and tuple(blob.shape) == (k, cin // 16, 2, 2, cout, 8)
+    planes = blob.permute(2, 4, 1, 3, 5, 0).reshape(2, cout, cin, k).float()       # [plane][Cout][chunk, k-half, k][slab]
+    assert torch.equal(planes[0].view(torch.int32), hi.view(torch.int32))
+    assert torch.equal(planes[1].view(torch.int32), lo.view(torch.int32))
+    resid = (w.double() - hi.double() - lo.double()).abs()
+    assert bool((resid <= X3_SPLIT * w.double().abs()).all())
+    assert float((resid / w.double().abs()).max()) > 0.25 * X3_SPLIT               # (the bound is not vacuous)
+    v = torch.tensor([1.0, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -(1.0 + 2.0 ** -8), 0.0, 2.0 ** -130])   # ties go to even
+    h2, l2 = ref64.split_bf16(v)
+    assert h2[:4].tolist() == [1.0, 1.0, 1.0 + 2.0 ** -6, -1.0] and l2[:4].tolist() == [0.0, 2.0 ** -8, -(2.0 ** -8), -(2.0 ** -8)]
+
+
+@pytest.mark.parametrize("shape", X3_SHAPES, ids=X3_IDS)
+def test_bf16x3_statement_is_within_the_derived_bound_of_float64(shape):
+    """(b) |statement - plain float64| <= c sum |x~| |w| with c = X3_C (+ X3_PRE where a leaky ReLU is formed in float32), the
+    derived worst case; the largest ratio seen is printed.  (c) zero weights return the bias.  magnitude=True is the plain
+    statement's (on the float32 x~)."""
+    x, w, bias, kw = _x3_operands(shape, 600)
+    pre = shape[6]
+    if pre == ref64.PRE_AFFINE_LRELU:       # pinned on the float32 x~ (see X3_PRE)
+        x, kw = ref64.conv_pre32(x, pre, kw["pre_slope"], kw["scale"], kw["shift"]), {}
+    stmt = _x3_call(shape, x, w, bias, kw, split="bf16x3")
+    plain = _x3_call(shape, x, w, bias, kw)
+    mag = _x3_call(shape, x, w, None, kw, magnitude=True)
+    mag3 = _x3_call(shape, x, w, bias, kw, magnitude=True, split="bf16x3")
+    assert stmt.dtype == torch.float64 and stmt.shape == plain.shape
+    c = X3_C + (X3_PRE if kw.get("pre", ref64.PRE_NONE) != ref64.PRE_NONE else 0.0)
+    ratio = float(((stmt - plain).abs() / mag).max())
+    print("X3-STATEMENT %s: max |statement - float64| / sum|x~||w| = %.3f x 2^-16 (bound %.3f x 2^-16)" % (
+        X3_IDS[X3_SHAPES.index(shape)], ratio * 2.0 ** 16, c * 2.0 ** 16))
+    assert 0.0 < ratio <= c
+    _close(mag3, (mag + bias.double().abs().reshape([1, -1] + [1] * (mag.dim() - 2))).float(), 1e-6)
+    zero = _x3_call(shape, x, torch.zeros_like(w), bias, kw, split="bf16x3")
+    assert torch.equal(zero, bias.double().reshape([1, -1] + [1] * (zero.dim() - 2)).expand_as(zero))
+
+
+@pytest.mark.parametrize("shape", X3_SHAPES, ids=X3_IDS)
+def test_bf16x3_yardstick_is_fp32_accumulation_of_the_same_sum(shape):
+    """(d) the yardstick of the device bound: torch's fp32 CPU operator on the tripled problem (cat[xh, xh, xl], cat[wh, wl, wh]
+    along Cin; every product exact in fp32) scored against the statement with conv_error: a few fp32 roundings, far below the
+    split's own 2^-16, and exact in float64."""
+    x, w, bias, kw = _x3_operands(shape, 700)
+    x3, w3 = ref64.bf16x3_tripled(x, w, cin_dim=0 if shape[0] == "convtr1d" else 1, **kw)
+    assert x3.dtype == w3.dtype == torch.float32 and x3.shape[1] == 3 * x.shape[1]
+    stmt = _x3_call(shape, x, w, bias, kw, split="bf16x3")
+    mag = _x3_call(shape, x, w, bias, kw, magnitude=True, split="bf16x3")
+    exact = _x3_torch(shape, x3.double(), w3.double(), bias.double())
+    assert float(((exact - stmt).abs() / mag).max()) <= 2.0 ** -45, "the tripled problem is not the statement's sum"
+    mx, ss, n = ref64.conv_error(_x3_torch(shape, x3, w3, bias), stmt, mag)
+    print("X3-YARDSTICK %s: max %.3e rms %.3e" % (X3_IDS[X3_SHAPES.index(shape)], mx, (ss / n) ** 0.5))
+    assert n == stmt.numel() and 0.0 < mx <= 16 * ULP

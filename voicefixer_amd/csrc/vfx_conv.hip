@@ -21,8 +21,9 @@
 // (16 VGPR each).  LDS is double buffered, the next K-chunk travels global -> VGPR while
 // the MFMAs of the current one run, one barrier per chunk; 33 KB of LDS and 127-155 VGPR
 // keep three to four workgroups per CU so that some stage while others compute.
-// conv_taps_kernel's accumulators start at zero and bias and residual are added to the finished
-// sum in the epilogue (conv_x3_kernel and convw_kernel start theirs at bias (+ residual)); interior
+// The accumulators of conv_taps_kernel, conv_x3_kernel and the unfused convw_kernel start at zero and bias
+// and residual are added to the finished sum in the epilogue (the fused layer, convw_kernel<.., FUSED>,
+// still starts its halves at b1 and at b2 + x: the stated follow-up); interior
 // tiles (guard bands) run a branch-free instance, instantiated per number of activation staging slots.
 #include "vfx_common.h"
 #include <cstdio>
@@ -128,8 +129,11 @@ struct ConvArgs {
     float* ws;
     int bl_step;            // tile step along q (= BL, or BL - span for exact-width halo tiles)
     int nxv;                // activation staging slots per thread this launch needs (host copy of the kernel's nxv)
-    int two_level;          // conv_taps_kernel: 1 = long K (>= 256 channels of 7 / 9 taps): partial sums of 64 channels (see the kernel)
-    int res_init;           // 1: plain output map (out = q) -> convw_kernel / conv_x3_kernel load the residual into the accumulators up front
+    int two_level;          // conv_taps_kernel: 1 = long K (>= 256 channels of 7 / 9 taps): partial sums of 64 channels (see the kernel);
+                            // convw_kernel's 3x3: the TWO_LEVEL instance was chosen (partial sums of 32 channels)
+    int res_init;           // 1: plain output map (out = q), a residual of element stride 1 whose offsets fit 32 bits -> the unfused
+                            // convw_kernel adds the residual on its lean store path (acc_store_rows: one buffer load per element, by the
+                            // lane that stores it); 0: conv_epilogue adds it.  The fused layer sets it for its own second half.
     // ---- bf16x3 instance (conv_x3_kernel) only
     const void* w3;         // weights as bf16 hi/lo planes: [slab][Cin/16][plane][k-half][Cout][8]
     const ConvTables* tab3; // tap tables in POSITIONS (no 4-alignment: the x3 staging moves single floats)
@@ -324,8 +328,19 @@ __device__ __forceinline__ void stage_write(StageState<MAXXV, MAXWV>& st, const 
         }
 }
 
-// ---- accumulators start at the bias (C/D layout of 32x32: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)):
-// the loads overlap the first K-chunk; in the epilogue they were 16 exposed load->use round trips per wave
+// ---- accumulator start values: zero for every stand-alone convolution ...
+template <int RM, int RL>
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[RM][RL]) {
+#pragma unroll
+    for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < RL; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// ... and the bias for the halves of the fused layer (convw_kernel<.., FUSED>).  C/D layout of 32x32: col = lane&31,
+// row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 template <int RM, int RL>
 __device__ __forceinline__ void acc_init_bias(f32x16 (&acc)[RM][RL], const float* __restrict__ bias, int nbase) {
 #pragma unroll
@@ -342,40 +357,20 @@ __device__ __forceinline__ void acc_init_bias(f32x16 (&acc)[RM][RL], const float
         }
 }
 
-// ... and, for plain output maps (out = q), at bias + residual: the residual tile of this workgroup is read while
-// the first K-chunk is staged instead of in 16 load->use round trips per wave after the K loop.  (In-place
-// residual updates stay safe: a workgroup reads and writes only its own tile.)
-template <int RM, int RL>
-__device__ __forceinline__ void acc_init_residual(f32x16 (&acc)[RM][RL], const float* __restrict__ rb, int rcs,
-                                                  int rls, int nbase, int qbase, int qend) {
-#pragma unroll
-    for (int j = 0; j < RL; ++j) {
-        const int q = qbase + j * 32;
-        if (q < qend) {
-#pragma unroll
-            for (int i = 0; i < RM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    acc[i][j][r] += rb[(nbase + i * 32 + (r & 3) + 8 * (r >> 2)) * rcs + q * rls];
-        }
-    }
-}
-
-// ---- epilogue of one tile.  SUM_FIRST = false: the accumulators started at the bias (and, with res_init, at the residual).
-// SUM_FIRST = true (conv_taps_kernel): they hold the bare sum of products, and bias and residual are added here, in the
-// order torch adds them.  An accumulator that starts at bias + residual rounds every one of the K partial sums at the
+// ---- epilogue of one tile (conv_taps_kernel, conv_x3_kernel, the unfused convw_kernel).  The accumulators hold the bare sum of
+// products; bias and residual are added here, in the order torch adds them.  An accumulator that starts at bias + residual rounds every one of the K partial sums at the
 // magnitude of bias + residual: where those dominate the sum (small weight-norm gains) the result carried ~sqrt(K) fp32
 // roundings of the residual's size, 10-30 x the error of the sum added last (profiles/conv_taps_parity.txt).
-template <int BM, int BL, int WGM, int WGL, bool SUM_FIRST = false>
+template <int BM, int BL, int WGM, int WGL>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[BM / WGM / 32][BL / WGL / 32], int q0,
                                               int m0, int b, int wm, int wl, int lo, int hi, int ooff, int qend) {
     constexpr int WMT = BM / WGM, WLT = BL / WGL, RM = WMT / 32, RL = WLT / 32;
     float* __restrict__ yb = a.y + (long long)b * a.y_bs;
-    const float* __restrict__ rb = (a.res && (SUM_FIRST || !a.res_init)) ? a.res + (long long)b * a.r_bs : nullptr;
+    const float* __restrict__ rb = a.res ? a.res + (long long)b * a.r_bs : nullptr;
     const int nbase = m0 + wm * WMT + 4 * hi;
     // the bias of this lane's 16 rows per 32-row block (the staging registers are dead by now)
     float4 bq[RM][4];
-    if (SUM_FIRST && a.post_act <= VFX_POST_LRELU) {
+    if (a.post_act <= VFX_POST_LRELU) {
 #pragma unroll
         for (int i = 0; i < RM; ++i)
 #pragma unroll
@@ -405,7 +400,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
                     for (int g = 0; g < 4; ++g) {
                         float v0 = acc[i][j][4 * g + 0], v1 = acc[i][j][4 * g + 1];
                         float v2 = acc[i][j][4 * g + 2], v3 = acc[i][j][4 * g + 3];
-                        if constexpr (SUM_FIRST) { v0 += bq[i][g].x; v1 += bq[i][g].y; v2 += bq[i][g].z; v3 += bq[i][g].w; }
+                        v0 += bq[i][g].x; v1 += bq[i][g].y; v2 += bq[i][g].z; v3 += bq[i][g].w;
                         if (rb) {
                             v0 += rb[ro + (8 * g + 0) * rcs];
                             v1 += rb[ro + (8 * g + 1) * rcs];
@@ -440,9 +435,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
                     const int n = nbase + i * 32 + (r & 3) + 8 * (r >> 2);
                     if (ok) {
                         float v = acc[i][j][r];
-                        if constexpr (SUM_FIRST) {
-                            if (a.bias) v += a.bias[n];
-                        }
+                        if (a.bias) v += a.bias[n];
                         if (rb) v += rb[(long long)n * a.r_cs + (long long)out * a.r_ls];
                         v = vfx_post(v, a.post_act, a.post_slope);
                         if (zero) v = 0.f;
@@ -583,10 +576,10 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
         st.w_off[j] = ((pt->tap_w[t] * a.CinPad + kc) * a.Cout + m0 + 4 * v) * (FAST ? 4 : 1);
     }
 
-    // the accumulators start at zero: bias and residual are added to the finished sum (conv_epilogue<.., SUM_FIRST>;
+    // the accumulators start at zero: bias and residual are added to the finished sum (conv_epilogue;
     // split-K: splitk_reduce_kernel), so that the K partial sums are rounded at their own magnitude
     f32x16 acc[RM][RL];
-    acc_init_bias<RM, RL>(acc, nullptr, m0 + wm * WMT + 4 * hi);
+    acc_zero<RM, RL>(acc);
     // Two-level sum where K is long: the 4-channel K-chunk (7 or 9 taps per channel: K = 9 Cin of the deep UNet levels) on
     // the small wave tiles (one or two 32x32 accumulators per wave: the 64x64, 128x64, 32x128 and 32x256 tiles those
     // launches choose), not cut by split-K.  Every 64 input channels the accumulators are added into a second set and
@@ -598,7 +591,7 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
     constexpr bool TWO_LEVEL = RM * RL <= 2 && KC == 4 && !SPLITK;
     constexpr int FLUSH = 64 / KC;   // K-chunks per partial sum (a power of two)
     f32x16 acc2[TWO_LEVEL ? RM : 1][TWO_LEVEL ? RL : 1];
-    if constexpr (TWO_LEVEL) acc_init_bias<RM, RL>(acc2, nullptr, 0);
+    if constexpr (TWO_LEVEL) acc_zero<RM, RL>(acc2);
 
     const int ooff = __builtin_amdgcn_readfirstlane(pt->ooff);
     const int a_col = wm * WMT + lo;  // column into the weight tile row
@@ -729,7 +722,7 @@ __global__ __launch_bounds__(64 * WGM * WGL, WGM * WGL / 2) void conv_taps_kerne
     const unsigned long long t_loop = __builtin_amdgcn_s_memtime();
 #endif
     if constexpr (SPLITK) conv_epilogue_partial<BM, BL, WGM, WGL>(a, acc, q0, m0, b, ks, wm, wl, lo, hi, qend);
-    else conv_epilogue<BM, BL, WGM, WGL, true>(a, acc, q0, m0, b, wm, wl, lo, hi, ooff, qend);
+    else conv_epilogue<BM, BL, WGM, WGL>(a, acc, q0, m0, b, wm, wl, lo, hi, ooff, qend);
 #if VFX_ABL & 8
     if (tid == 0 && FAST) {
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -835,13 +828,10 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
     }
     const int w_cstep = 4 * a.Cout * 16;  // bytes per 16-channel chunk in the packed weights
 
+    // the accumulators start at zero: bias and residual are added to the finished sum (conv_epilogue), so
+    // no partial sum of the 3 Cin taps-term chain rounds at their magnitude
     f32x16 acc[RM][RL];
-    acc_init_bias<RM, RL>(acc, a.bias, m0 + wm * WMT + 4 * hi);
-    if (a.res && a.res_init) {
-        const int qe0 = q0 + a.bl3;
-        acc_init_residual<RM, RL>(acc, a.res + (long long)b * a.r_bs, (int)a.r_cs, (int)a.r_ls, m0 + wm * WMT + 4 * hi,
-                                  q0 + wl * WLT + lo, qe0 < a.Lq ? qe0 : a.Lq);
-    }
+    acc_zero<RM, RL>(acc);
 
     const int ooff = __builtin_amdgcn_readfirstlane(pt->ooff);
     // (ROWS 3: the base sits one map row lower so that the scalar row offset dy * xrow3 is never negative --
@@ -1466,7 +1456,7 @@ static int conv_args(ConvArgs& a, const vfx_tensor* x, const float* w, const flo
     a.y_bs = y->bstride; a.y_cs = y->cstride; a.y_ls = y->lstride;
     if (res) { a.r_bs = res->bstride; a.r_cs = res->cstride; a.r_ls = res->lstride; }
     a.q_shift = q_shift; a.q_mask = q_mask; a.o_rs = o_rs; a.o_cs = o_cs;
-    a.res_init = res && plain_output_map(a, nphase, phs[0].ooff) &&
+    a.res_init = res && res->lstride == 1 && plain_output_map(a, nphase, phs[0].ooff) &&
                  (long long)Cout * res->cstride + (long long)Lq * res->lstride < (1ll << 31);
     a.pad_mode = pad_mode;
     a.pre_act = act ? act->pre_act : VFX_PRE_NONE;

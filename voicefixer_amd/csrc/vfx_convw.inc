@@ -242,22 +242,46 @@ __device__ __forceinline__ void acc_add_rows(f32x16 (&acc)[RM][RL], __amdgpu_buf
         }
 }
 
-template <int RM, int RL>
+// SUM_FIRST (the unfused launches): the accumulators hold the bare sum of products; the bias (row `nbase` + ... of this lane)
+// and, with `add_res`, the residual are added here, in the order torch adds them -- an accumulator that starts at bias
+// (+ residual) rounds every partial sum of the K loop at their magnitude (see conv_epilogue).  The residual of an element is
+// loaded by the lane that stores it, before the store: in-place updates stay safe.
+template <int RM, int RL, bool SUM_FIRST = false>
 __device__ __forceinline__ void acc_store_rows(const ConvArgs& a, f32x16 (&acc)[RM][RL], __amdgpu_buffer_rsrc_t rsrc,
-                                               int row0, int cs4, const int (&voff)[RL], const bool (&keep)[RL]) {
+                                               int row0, int cs4, const int (&voff)[RL], const bool (&keep)[RL], int nbase,
+                                               bool add_res, __amdgpu_buffer_rsrc_t rrsrc, int rcs4, const int (&rvoff)[RL]) {
     // keep[j]: false for a structural-zero (pad) column of a pitch map, which is written as 0 whatever was accumulated
     const int post = a.post_act;
     const float ps = a.post_slope;
     if (post <= VFX_POST_LRELU) {
         const float slope = post == VFX_POST_LRELU ? ps : 1.f;
+        float4 bq[RM][4];                         // the bias of this lane's 16 rows per 32-row block: four 16-byte loads
+        if constexpr (SUM_FIRST) {
+#pragma unroll
+            for (int i = 0; i < RM; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    bq[i][g] = a.bias ? *reinterpret_cast<const float4*>(a.bias + nbase + i * 32 + 8 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
 #pragma unroll
         for (int i = 0; i < RM; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int soff = (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * cs4;
+                float bv = 0.f;
+                if constexpr (SUM_FIRST) {
+                    const float4 q4 = bq[i][r >> 2];
+                    bv = (r & 3) == 0 ? q4.x : ((r & 3) == 1 ? q4.y : ((r & 3) == 2 ? q4.z : q4.w));
+                }
 #pragma unroll
                 for (int j = 0; j < RL; ++j) {
                     float v = acc[i][j][r];
+                    if constexpr (SUM_FIRST) {
+                        v += bv;
+                        if (add_res)
+                            v += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                                rrsrc, rvoff[j], (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * rcs4, 0));
+                    }
                     v = keep[j] ? (v > 0.f ? v : v * slope) : 0.f;
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc, voff[j], soff, 0);
                 }
@@ -271,8 +295,14 @@ __device__ __forceinline__ void acc_store_rows(const ConvArgs& a, f32x16 (&acc)[
 #pragma unroll 1
                 for (int r = 0; r < 16; ++r) {
                     const int soff = (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * cs4;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(keep[j] ? vfx_post(acc[i][j][r], post, ps) : 0.f), rsrc,
-                                                          voff[j], soff, 0);
+                    float v = acc[i][j][r];
+                    if constexpr (SUM_FIRST) {
+                        if (a.bias) v += a.bias[nbase + i * 32 + (r & 3) + 8 * (r >> 2)];
+                        if (add_res)
+                            v += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                                rrsrc, rvoff[j], (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * rcs4, 0));
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(keep[j] ? vfx_post(v, post, ps) : 0.f), rsrc, voff[j], soff, 0);
                 }
     }
 }
@@ -280,13 +310,14 @@ __device__ __forceinline__ void acc_store_rows(const ConvArgs& a, f32x16 (&acc)[
 // FUSED: 0 = one convolution; 1 = one ResStack layer, both convolutions as direct tap-GEMMs; 2 = the same with the
 // second (dilation 1) convolution as Winograd F(2,3) on the LDS tile (see vfx_convwg.inc for the algebra); 3 = the same with
 // F(4,3) for the second convolution (C = 64: 64 channels x 63 output quads per tile)
-template <int BM, int BL, int WGM, int WGL, int NT, int NXV, int FUSED>
+template <int BM, int BL, int WGM, int WGL, int NT, int NXV, int FUSED, bool TWO_LEVEL = false>
 __global__ __launch_bounds__(256, FUSED ? 2 : 3) void convw_kernel(const ConvArgs a) {
     constexpr int WMT = BM / WGM, WLT = BL / WGL, RM = WMT / 32, RL = WLT / 32;
     constexpr int NTHR = 256;
     constexpr int HALO = FUSED ? 1 : 0;           // accumulator column 0 of the (first) convolution sits HALO left of q0
     constexpr int NR = NT == 9 ? 3 : 1;           // NT == 9: 3x3 convolution on a pitch map = three kernel rows of three taps
     constexpr bool MAP2D = NT == 9;               // (eval-BatchNorm pre-activation, pad-column masks)
+    static_assert(!TWO_LEVEL || MAP2D, "the second accumulator set is the 3x3 instances'");
     static_assert(WGM * WGL == 4 && RM >= 1 && RL >= 1 && (NT == 2 || NT == 3 || NT == 9) && !(FUSED && MAP2D), "tile");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -473,9 +504,18 @@ __global__ __launch_bounds__(256, FUSED ? 2 : 3) void convw_kernel(const ConvArg
             yvoff[j] = (q < qend && out >= 0 && out < a.Lout) ? (4 * hi * (int)a.y_cs + out) * 4 : VFX_W_OOB;
             keep[j] = !(MAP2D && ((q & a.out_mask) == a.out_mask));
         }
+        // unfused launches: the accumulators start at zero, bias and residual are added to the finished sum (acc_store_rows /
+        // conv_epilogue); the fused layer's first half starts at its bias b1
         f32x16 acc[RM][RL];
-        acc_init_bias<RM, RL>(acc, a.bias, nbase);
-        if (!FUSED && a.res && a.res_init) acc_add_rows<RM, RL>(acc, rrsrc, row0, (int)a.r_cs * 4, rvoff);
+        if constexpr (FUSED) acc_init_bias<RM, RL>(acc, a.bias, nbase);
+        else acc_zero<RM, RL>(acc);
+        // 3x3 on a map: K = 9 Cin products in one chain.  A strictly sequential fp32 chain of 576 ... 4608 terms is up to 1.13 x the
+        // bound of tests/test_convw_gpu.py (4 x the CPU operator's blocked sum); the TWO_LEVEL instances (a.two_level) add the
+        // accumulators into a second set every 32 input channels (288 terms), as conv_taps_kernel's small tiles do every 64.  The
+        // set costs 32 registers on the small tiles; on the 128 x 128 tile it costs 64 and spills (the host asks for it there from
+        // 256 input channels on only)
+        f32x16 acc2[TWO_LEVEL ? RM : 1][TWO_LEVEL ? RL : 1];
+        if constexpr (TWO_LEVEL) acc_zero<RM, RL>(acc2);
 
         x_write(smem, q0, range_mask, 0);
         if (S > 1) x_load(q0, 1);
@@ -492,10 +532,30 @@ __global__ __launch_bounds__(256, FUSED ? 2 : 3) void convw_kernel(const ConvArg
                 mma_groups3<RM, RL, NR>(acc, ws, wrsrc, xs + hi * segw + b_col, segw, tap0, tapstep, kcx >> 3, kcx * segw);
             else mma_steps<RM, RL, NT>(acc, ws, wrsrc, xs + hi * segw + b_col, segw, tap0, tapstep, nsteps);
             __syncthreads();
+            if constexpr (TWO_LEVEL) {
+                if (((s + 1) & 3) == 0 && s + 1 < S) {
+#pragma unroll
+                    for (int i = 0; i < RM; ++i)
+#pragma unroll
+                        for (int j = 0; j < RL; ++j) {
+                            acc2[i][j] += acc[i][j];
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                        }
+                }
+            }
+        }
+        if constexpr (TWO_LEVEL) {
+#pragma unroll
+            for (int i = 0; i < RM; ++i)
+#pragma unroll
+                for (int j = 0; j < RL; ++j) acc[i][j] += acc2[i][j];
         }
 
         if constexpr (!FUSED) {
-            if (lean_out && !(a.res && !a.res_init)) acc_store_rows<RM, RL>(a, acc, yrsrc, row0, (int)a.y_cs * 4, yvoff, keep);
+            if (lean_out && !(a.res && !a.res_init))
+                acc_store_rows<RM, RL, true>(a, acc, yrsrc, row0, (int)a.y_cs * 4, yvoff, keep, nbase, a.res != nullptr, rrsrc,
+                                             (int)a.r_cs * 4, rvoff);
             else conv_epilogue<BM, BL, WGM, WGL>(a, acc, q0, m0, b, wm, wl, lo, hi, ooff, qend);
         } else if constexpr (FUSED == 3) {
             // ---- second convolution (k3, dilation 1) as Winograd F(4,3) on y = lrelu(conv1 + b1) kept in LDS: the output
@@ -921,26 +981,26 @@ __global__ __launch_bounds__(256, FUSED ? 2 : 3) void convw_kernel(const ConvArg
             __syncthreads();
             mma_groups3<RM, RL>(acc2, w2, w2rsrc, Y + hi * yp + b_col, yp, 0, 1, a.Cout >> 3);
             if (has_next) ws_start();             // conv-1 weight vectors of the next tile: in flight during the stores
-            acc_store_rows<RM, RL>(a, acc2, yrsrc, row0, (int)a.y_cs * 4, yvoff, keep);
+            acc_store_rows<RM, RL>(a, acc2, yrsrc, row0, (int)a.y_cs * 4, yvoff, keep, nbase, false, rrsrc, 0, rvoff);
             if (has_next) __syncthreads();        // Y is dead before the next tile's chunk 0 overwrites it
         }
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-template <int BM, int BL, int WGM, int WGL, int NT, int NXV, int FUSED>
+template <int BM, int BL, int WGM, int WGL, int NT, int NXV, int FUSED, bool TWO_LEVEL = false>
 static int launch_w_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-    return vfx_launch<convw_kernel<BM, BL, WGM, WGL, NT, NXV, FUSED>>(grid, dim3(256), lds, s, a);
+    return vfx_launch<convw_kernel<BM, BL, WGM, WGL, NT, NXV, FUSED, TWO_LEVEL>>(grid, dim3(256), lds, s, a);
 }
 
-template <int BM, int BL, int WGM, int WGL, int NT, int FUSED>
+template <int BM, int BL, int WGM, int WGL, int NT, int FUSED, bool TWO_LEVEL = false>
 static int launch_w_nxv(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     if constexpr (FUSED) {
         return a.nxv <= 5 ? launch_w_one<BM, BL, WGM, WGL, NT, 5, FUSED>(a, grid, lds, s)
                           : launch_w_one<BM, BL, WGM, WGL, NT, 6, FUSED>(a, grid, lds, s);
     } else if constexpr (NT == 9) {
-        return a.nxv <= 4 ? launch_w_one<BM, BL, WGM, WGL, NT, 4, false>(a, grid, lds, s)
-                          : launch_w_one<BM, BL, WGM, WGL, NT, 7, false>(a, grid, lds, s);
+        return a.nxv <= 4 ? launch_w_one<BM, BL, WGM, WGL, NT, 4, false, TWO_LEVEL>(a, grid, lds, s)
+                          : launch_w_one<BM, BL, WGM, WGL, NT, 7, false, TWO_LEVEL>(a, grid, lds, s);
     } else {
         return a.nxv <= 4   ? launch_w_one<BM, BL, WGM, WGL, NT, 4, false>(a, grid, lds, s)
                : a.nxv == 5 ? launch_w_one<BM, BL, WGM, WGL, NT, 5, false>(a, grid, lds, s)
@@ -1156,6 +1216,7 @@ static int try_launch_convw_2d(ConvArgs a, const vfx_tensor* x, int P, const flo
     a.w_nseg = 3; a.w_seg0 = -P - 1; a.w_segstep = P;
     a.tab = nullptr;
     a.stagger = 0; a.stagger_wgs = 0;
+    a.two_level = a.Cin >= (BM == 128 && BL == 128 ? 256 : 64);   // K = 9 Cin >= 576 (2304 on the 128 x 128 tile: see the kernel)
     // interior check: every staged vector inside [-guard, Lin + guard)
     const long long g = x->guard;
     if ((long long)P + 1 > g) return VFX_ENOTSUP;
@@ -1163,6 +1224,12 @@ static int try_launch_convw_2d(ConvArgs a, const vfx_tensor* x, int P, const flo
     const size_t lds = (2ull * a.xs_floats + 2ull * a.Cin) * sizeof(float) + 64;
     const dim3 grid(convw_grid_x(a, ntiles), gy, a.B);
     set_last_tile(BM, BL, TILE_CONVW_2D);
+    if (a.two_level) {
+        if (BM == 128 && BL == 64) return launch_w_one<128, 64, 2, 2, 9, 4, false, true>(a, grid, lds, stream);
+        if (BM == 128) return launch_w_nxv<128, 128, 2, 2, 9, false, true>(a, grid, lds, stream);
+        if (BM == 64) return launch_w_nxv<64, 128, 1, 4, 9, false, true>(a, grid, lds, stream);
+        return launch_w_nxv<32, 256, 1, 4, 9, false, true>(a, grid, lds, stream);
+    }
     if (BM == 128 && BL == 64) return launch_w_one<128, 64, 2, 2, 9, 4, false>(a, grid, lds, stream);
     if (BM == 128) return launch_w_nxv<128, 128, 2, 2, 9, false>(a, grid, lds, stream);
     if (BM == 64) return launch_w_nxv<64, 128, 1, 4, 9, false>(a, grid, lds, stream);
